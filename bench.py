@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Headline benchmark: cube-move steps/s, 3x3x3, batch 4M per GPU (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--cubes-per-gpu C] [--no-cpu] [--no-configs] [--force-dist] [--backend nccl|gloo]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--cubes-per-gpu C] [--dump-outputs DIR] [--full [--no-cpu] [--no-configs]]
+                    [--force-dist] [--backend nccl|gloo]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W [--cubes-per-gpu 1048576]
 
@@ -13,10 +14,19 @@ Inputs are resident in HBM before the timed region.  value = cubes * K * N / max
 Every rank owns its own batch and RNG stream (stream_id = rank); there is no collective on the
 env path ("scaling": "weak").
 
+PLAIN RUN AND --full.  A plain run sets up, warms up, times the K steps, writes --dump-outputs if asked and prints the line: the
+contract's keys (metric, value, unit, higher_is_better, dtype, ms_per_step = host wall clock of one timed step), `config` and, for
+N > 1, the short `per_gpu` list.  Everything else this file measures or checks runs only with --full: the roofline (its post-region
+launch batches, the device-copy ceiling), the per-rank sha256 samples, cpu_baseline, the other configs and the full record.
+
+--dump-outputs DIR (rank 0): what the last timed step computed, as a caller of rc_apply_moves receives it -- DIR/states.npy
+[k, 54] (stickers per cube) and DIR/done.npy [k] (solved flag), float32, for a fixed seeded sample of k = min(C, 2^17) cubes
+(dump_sample(); all C cubes in order when C <= 2^17).  Inputs are seeded, so the same arguments give the same arrays.
+
 OUTPUT.  stdout carries exactly ONE line, printed last by rank 0: the COMPACT record (compact_record(): the contract's keys,
-`roofline`, `cpu_baseline`, ten scalar `extras`, under 4 KB, no string over 120 characters -- round 5's 23.5 KB line came back from
-the driver unparsed).  The FULL record (every per-config roofline record, the notes, per-rank details) is written to --full-out
-(default bench_full.json next to this file; the builder's copies live under profiles/).  In the distributed branch the full record's
+`roofline`, `cpu_baseline`, ten scalar `extras` with --full, under 4 KB, no string over 120 characters -- round 5's 23.5 KB line came back from
+the driver unparsed).  With --full the FULL record (every per-config roofline record, the notes, per-rank details) is written to
+--full-out (default bench_full.json next to this file; the builder's copies live under profiles/).  In the distributed branch the full record's
 `per_gpu` carries each rank's stream_id, device index, PCI bus id, rate and a sha256 of its first 65536 scrambled cubes (the tests
 compare it with the oracle's (seed, rank) stream); the compact line carries the short form and `config.distinct_devices`.  One rank
 per GPU: a launch with more ranks than visible devices is REFUSED unless --share-gpu marks it as a rehearsal.  At N > 1 the other
@@ -38,7 +48,7 @@ the reference actually runs, end to end on the host clock: `adi_pipeline` (get_r
 own size, 20k x 30, 100k x 30, and the hipGraph replay), `config5_mcts_4096_leaves` (config 5: us per MCTS step eager / hipGraph,
 the lockstep search's device step + transfers and whole simulations split select / device / update), `rollout`
 (greedy validation rollouts), `reset_seeds_1M_k30` (reset(seed, 30) for 1M envs, numpy's legacy generator on the device) and the
-batch-1 facade latency.  --no-configs skips them.  RC_BENCH_DRY=1 (with --backend gloo) runs the N-rank plumbing without a GPU.
+batch-1 facade latency.  --full --no-configs skips them.  RC_BENCH_DRY=1 (with --backend gloo) runs the N-rank plumbing without a GPU.
 """
 import argparse
 import json
@@ -454,6 +464,27 @@ def pipeline_configs(torch, ops, _lib, dev):
 ADI_CODE_OUTPUTS = dict(parents=True, parent_code=True, child_code=True)
 SAMPLE_CUBES = 1 << 16      # per-rank sample whose sha256 the N>1 line carries (tests replay it through the oracle)
 SCRAMBLE_SEED, SCRAMBLE_DEPTH = 1234, 20
+DUMP_CUBES, DUMP_SEED = 1 << 17, 20261016     # --dump-outputs: 2^17 cubes x 55 float32 values = 28.8 MB
+
+
+def dump_sample(n):
+    """Indices of the cubes --dump-outputs writes: all n in order when n <= DUMP_CUBES, else a fixed seeded sample, ascending."""
+    import numpy as np
+    if n <= DUMP_CUBES:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_CUBES, replace=False))
+
+
+def dump_outputs(out_dir, states, done, n):
+    """What the caller of the timed step receives, for the dump_sample(n) cubes: states.npy [k, 54] stickers and done.npy [k]
+    solved flags, float32."""
+    import numpy as np
+    import torch
+    from rubiks_cube_solver_amd import ops
+    idx = torch.from_numpy(dump_sample(n)).to(states.device)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "states.npy"), ops.to_aos(states, n)[idx].float().cpu().numpy())
+    np.save(os.path.join(out_dir, "done.npy"), done[idx].float().cpu().numpy())
 
 
 def _free_port():
@@ -472,6 +503,52 @@ def per_config_summary(configs):
             for r in configs["records"]]
 
 
+def roofline(_lib, n, args, elapsed, dev_ms, launch_us, launch_min, launch_max, n_batches, copy_gbps, configs):
+    """The headline's roofline record (--full): fractions of the HBM peak from the post-region launch batches, the timed region and
+    the wall clock, beside the measured device-copy ceiling."""
+    kernel = _lib.describe(_lib.OP_STEP, CUBE, n, outputs=_lib.OUT_STATES | _lib.OUT_DONE)   # what the headline launches, from the library's own dispatch
+    launch_s = launch_us * 1e-6
+    achieved = BYTES_PER_STEP * n / launch_s / 1e9
+    traffic, traffic_source = None, None
+    tfile = os.path.join(ROOT, "profiles", "traffic.json")       # PMC-derived bytes per launch, if profiled
+    if os.path.exists(tfile) and n == N_CUBES:
+        try:
+            tj = json.load(open(tfile))
+            traffic = tj.get("k_step_bytes_per_launch")
+            traffic_source = (f"profiles/traffic.json: builder's rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of round {tj.get('round')} "
+                              "over this same command (not re-measured in this run)")
+        except Exception:
+            traffic = None
+    state_mb = n * 54 / 1e6
+    pol = kernel.split("POL=")[1][0] if "POL=" in kernel else "?"
+    served = {"0": f"working set {2 * state_mb:.0f} MB fits the 256 MB Infinity Cache: rows default-cached, served on-die, NOT an HBM figure",
+              "1": "input rows streamed (nt), output rows written through and kept (sc0 sc1): the next launch finds part of its input in the "
+                   "256 MB Infinity Cache, so DRAM traffic is below the fabric traffic the counters show; the nothing-cached figure is "
+                   "roofline.frac_hbm_only",
+              "2": "input rows streamed (nt), output rows streamed (sc0 sc1 nt): every byte comes from and goes to HBM"}.get(pol, "")
+    return {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+            "frac": achieved / HBM_PEAK_GBPS, "traffic": traffic, "traffic_source": traffic_source,
+            "kernel": kernel, "launch_us": launch_us, "launch_us_min": launch_min, "launch_us_max": launch_max,
+            "launch_us_timed_region": dev_ms / args.steps * 1e3,
+            "frac_basis": "launch_us: the median event-timed batch AFTER the timed region (the kernel's steady launch duration)",
+            "frac_timed_region": BYTES_PER_STEP * n / (dev_ms / args.steps * 1e-3) / 1e9 / HBM_PEAK_GBPS,
+            "frac_wall_clock": BYTES_PER_STEP * n / (elapsed / args.steps) / 1e9 / HBM_PEAK_GBPS,
+            "frac_note": "three durations, three fractions: frac (launch_us), frac_timed_region (HIP events around the K timed steps themselves), "
+                         "frac_wall_clock (ms_per_step: host clock incl. the barrier and synchronisation on both sides = what `value` uses)",
+            "launch_batches": n_batches, "launches_per_batch": args.steps,
+            "launch_note": "launch_us = median over `launch_batches` back-to-back batches of `launches_per_batch` launches, each bracketed by "
+                           "HIP events on the launch stream, run right after the timed region (N > 1: the slowest rank's median)",
+            "algorithmic_bytes_per_launch": BYTES_PER_STEP * n,
+            "achievable_GBps": HBM_ACHIEVABLE_GBPS, "frac_of_achievable": achieved / HBM_ACHIEVABLE_GBPS,
+            "achievable_note": "MI355X_MICROARCH.md: HBM 8 TB/s peak (spec), about 6.3 TB/s achievable",
+            "served_by": "hbm" if pol == "2" else "hbm + infinity cache" if pol == "1" else "infinity cache",
+            "frac_hbm_only": configs["hbm_only_frac"] if configs else None,
+            "frac_hbm_only_note": "the same kernel at 2^24 cubes (1.8 GB ping-pong, nothing cached): per_config '16M step (HBM only)'",
+            "device_copy_GBps": copy_gbps, "frac_of_device_copy": achieved / copy_gbps if copy_gbps else None,
+            "device_copy_note": f"hipMemcpy D2D (torch copy_) of the same {state_mb:.0f} MB state buffer, read + write bytes",
+            "note": served}
+
+
 def main():
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")      # before anything initialises the HIP runtime (RCCL / IPC, N > 1)
     ap = argparse.ArgumentParser()
@@ -480,9 +557,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=50)
     ap.add_argument("--cubes-per-gpu", type=int, default=N_CUBES,
                     help="batch per GPU (default 2^22 = the metric's batch; 1048576 = BASELINE config 4: 1M cubes per GPU x N GPUs)")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
-    ap.add_argument("--no-configs", action="store_true", help="skip the other BASELINE configs (timed outside the headline region)")
-    ap.add_argument("--extras", action="store_true", help="(kept for compatibility: the configs are on by default)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline: roofline, cpu_baseline, the other configs, the full record")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the cpu_baseline leg")
+    ap.add_argument("--no-configs", action="store_true", help="with --full: skip the other BASELINE configs (timed outside the headline region)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed (a fixed sample, float32 .npy) into DIR")
+    ap.add_argument("--extras", action="store_true", help="(kept for compatibility: --full runs the configs)")
     ap.add_argument("--backend", default="nccl", help="process-group backend of the distributed branch (nccl = RCCL; gloo only to rehearse on one GPU)")
     ap.add_argument("--force-dist", action="store_true",
                     help="run the distributed branch (process group, barrier, all_gather, MAX over ranks) even at world size 1")
@@ -490,12 +570,17 @@ def main():
                     help="rehearsal only: let ranks fold onto the same GPU (local_rank %% device_count) when world > device_count; without it "
                          "such a launch is refused")
     ap.add_argument("--configs", action="store_true", help="N > 1: run the other BASELINE configs on rank 0 too (default there: skipped, rank 0 exits with the others)")
-    ap.add_argument("--full-out", default=os.path.join(ROOT, "bench_full.json"),
-                    help="where the FULL record (per-config records, notes, per-rank details) is written; stdout carries only the compact line")
+    ap.add_argument("--full-out", default=None,
+                    help="where the FULL record (per-config records, notes, per-rank details) is written (default with --full: bench_full.json next "
+                         "to this file); stdout carries only the compact line")
     ap.add_argument("--batches", type=int, default=0, help="event-timed batches of --steps launches after the timed region (0 = max(7, 140 / steps))")
     args = ap.parse_args()
     if args.cubes_per_gpu < 1:
         sys.exit("--cubes-per-gpu must be positive")
+    if args.steps < 1 or args.warmup < 0:
+        sys.exit("--steps must be positive and --warmup not negative")
+    if args.full and args.full_out is None:
+        args.full_out = os.path.join(ROOT, "bench_full.json")
 
     import hashlib
 
@@ -522,6 +607,8 @@ def main():
     dry = os.environ.get("RC_BENCH_DRY") == "1"
     if dry and args.backend != "gloo":
         sys.exit("RC_BENCH_DRY=1 needs --backend gloo (no GPU is touched)")
+    if dry and args.dump_outputs:
+        sys.exit("--dump-outputs needs a real run: RC_BENCH_DRY=1 computes nothing")
     # one rank per GPU: rank r asks for device LOCAL_RANK and nothing else.  A launch with more ranks than devices is refused (it
     # would silently fold ranks onto one GPU and report an "8-GPU" line from fewer) unless --share-gpu says it is a rehearsal.
     n_devices = torch.cuda.device_count()
@@ -539,6 +626,8 @@ def main():
                 sys.exit(f"rank {rank}: LOCAL_RANK {local_rank} >= {n_devices} visible device(s); one rank per GPU is the contract "
                          "(--share-gpu folds ranks onto the same GPU for a rehearsal)")
         torch.cuda.set_device(dev_index)
+    if not args.full:
+        args.no_cpu = args.no_configs = True                          # a plain run measures the headline and nothing else
     if world > 1 and not args.configs:
         args.no_configs = True                                        # rank 0 leaves with the others; N = 1 carries the per-config records
     dev = torch.device("cuda", dev_index)
@@ -585,7 +674,7 @@ def main():
         b = torch.empty_like(a)
         ops.fill_solved(a, n, CUBE)
         ops.scramble(a, n, CUBE, SCRAMBLE_DEPTH, seed=SCRAMBLE_SEED, stream_id=stream_id)   # 20-move scrambles, rank-distinct streams
-        sample_sha = hashlib.sha256(ops.to_aos(a, k).contiguous().cpu().numpy().tobytes()).hexdigest()
+        sample_sha = hashlib.sha256(ops.to_aos(a, k).contiguous().cpu().numpy().tobytes()).hexdigest() if args.full else None
         g = torch.Generator(device=dev).manual_seed(1 + rank)
         acts = torch.randint(0, 12, (n,), generator=g, device=dev, dtype=torch.uint8)
         done = torch.empty(n, dtype=torch.uint8, device=dev)
@@ -614,20 +703,27 @@ def main():
         elapsed = time.perf_counter() - t0
         dev_ms = e0.elapsed_time(e1)                                     # HIP events on the launch stream
         assert _lib.read_status(dev) == 0
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, bufs[0], done, n)           # bufs[0] = what the last timed step wrote
         # The roofline's launch duration: R more batches of `steps` launches each, back to back, every batch bracketed by HIP events on
         # the launch stream (outside the timed region above, same buffers, same kernel): the MEDIAN batch is roofline.launch_us, so a
         # 20-step driver run does not hang the headline fraction on one 1.4 ms sample.
-        n_batches = args.batches if args.batches > 0 else max(7, -(-140 // max(1, args.steps)))
-        evs = [torch.cuda.Event(enable_timing=True) for _ in range(n_batches + 1)]
-        evs[0].record()
-        for bi in range(n_batches):
-            for _ in range(args.steps):
-                step()
-            evs[bi + 1].record()
-        torch.cuda.synchronize()
-        batch_us = sorted(evs[i].elapsed_time(evs[i + 1]) / args.steps * 1e3 for i in range(n_batches))
-        launch_us, launch_min, launch_max = batch_us[len(batch_us) // 2], batch_us[0], batch_us[-1]
-        assert _lib.read_status(dev) == 0
+        # A plain run reports no roofline: the timed region's own per-launch time stands in for the gathered figures.
+        if args.full:
+            n_batches = args.batches if args.batches > 0 else max(7, -(-140 // max(1, args.steps)))
+            evs = [torch.cuda.Event(enable_timing=True) for _ in range(n_batches + 1)]
+            evs[0].record()
+            for bi in range(n_batches):
+                for _ in range(args.steps):
+                    step()
+                evs[bi + 1].record()
+            torch.cuda.synchronize()
+            batch_us = sorted(evs[i].elapsed_time(evs[i + 1]) / args.steps * 1e3 for i in range(n_batches))
+            launch_us, launch_min, launch_max = batch_us[len(batch_us) // 2], batch_us[0], batch_us[-1]
+            assert _lib.read_status(dev) == 0
+        else:
+            n_batches = 0
+            launch_us = launch_min = launch_max = dev_ms / args.steps * 1e3
     per_rank = None
     if use_dist:
         t = torch.tensor([elapsed, dev_ms, launch_us, launch_min, launch_max], dtype=torch.float64, device=dev if args.backend == "nccl" else "cpu")
@@ -660,7 +756,7 @@ def main():
 
     # the measured device-copy ceiling SURVEY 8d asks for beside the vendor peak: the runtime's own D2D copy of the same buffers
     copy_gbps = None
-    if not dry:
+    if args.full and not dry:
         for _ in range(3):
             bufs[1].copy_(bufs[0])
         c0, c1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -670,7 +766,6 @@ def main():
         c1.record()
         torch.cuda.synchronize()
         copy_gbps = 2 * bufs[0].numel() / (c0.elapsed_time(c1) / 20 * 1e-3) / 1e9
-    kernel = _lib.describe(_lib.OP_STEP, CUBE, n, outputs=_lib.OUT_STATES | _lib.OUT_DONE)   # what the headline launches, from the library's own dispatch
     configs = None
     if not args.no_configs and not dry:
         del a, b, bufs
@@ -679,25 +774,6 @@ def main():
         assert _lib.read_status(dev) == 0
 
     steps_per_s = n * args.steps * world / elapsed
-    launch_s = launch_us * 1e-6
-    achieved = BYTES_PER_STEP * n / launch_s / 1e9
-    traffic, traffic_source = None, None
-    tfile = os.path.join(ROOT, "profiles", "traffic.json")       # PMC-derived bytes per launch, if profiled
-    if os.path.exists(tfile) and n == N_CUBES:
-        try:
-            tj = json.load(open(tfile))
-            traffic = tj.get("k_step_bytes_per_launch")
-            traffic_source = (f"profiles/traffic.json: builder's rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of round {tj.get('round')} "
-                              "over this same command (not re-measured in this run)")
-        except Exception:
-            traffic = None
-    state_mb = n * 54 / 1e6
-    pol = kernel.split("POL=")[1][0] if "POL=" in kernel else "?"
-    served = {"0": f"working set {2 * state_mb:.0f} MB fits the 256 MB Infinity Cache: rows default-cached, served on-die, NOT an HBM figure",
-              "1": "input rows streamed (nt), output rows written through and kept (sc0 sc1): the next launch finds part of its input in the "
-                   "256 MB Infinity Cache, so DRAM traffic is below the fabric traffic the counters show; the nothing-cached figure is "
-                   "roofline.frac_hbm_only",
-              "2": "input rows streamed (nt), output rows streamed (sc0 sc1 nt): every byte comes from and goes to HBM"}.get(pol, "")
     workload = (f"3x3x3 apply_move + solved flag, {n} cubes per GPU per launch x {world} GPU(s), uint8 SoA [54][N] in 32768-cube tiles, "
                 "ping-pong of two buffers; ")
     workload += ("configs[1] shape at the metric's batch 4M" if n == N_CUBES else
@@ -709,36 +785,18 @@ def main():
         "vs_baseline": None, "dtype": "u8", "data": "synthetic" if not dry else "synthetic (RC_BENCH_DRY=1: NO kernel ran, the numbers mean nothing)",
         "config": {"workload": workload, "cubes_per_gpu": n, "total_cubes": n * world, "bytes_per_step_algorithmic": BYTES_PER_STEP,
                    "parallelism": f"{world} independent ranks, stream_id = rank, no collective"},
-        "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                     "frac": achieved / HBM_PEAK_GBPS, "traffic": traffic, "traffic_source": traffic_source,
-                     "kernel": kernel, "launch_us": launch_us, "launch_us_min": launch_min, "launch_us_max": launch_max,
-                     "launch_us_timed_region": dev_ms / args.steps * 1e3,
-                     "frac_basis": "launch_us: the median event-timed batch AFTER the timed region (the kernel's steady launch duration)",
-                     "frac_timed_region": BYTES_PER_STEP * n / (dev_ms / args.steps * 1e-3) / 1e9 / HBM_PEAK_GBPS,
-                     "frac_wall_clock": BYTES_PER_STEP * n / (elapsed / args.steps) / 1e9 / HBM_PEAK_GBPS,
-                     "frac_note": "three durations, three fractions: frac (launch_us), frac_timed_region (HIP events around the K timed steps themselves), "
-                                  "frac_wall_clock (ms_per_step: host clock incl. the barrier and synchronisation on both sides = what `value` uses)",
-                     "launch_batches": n_batches, "launches_per_batch": args.steps,
-                     "launch_note": "launch_us = median over `launch_batches` back-to-back batches of `launches_per_batch` launches, each bracketed by "
-                                    "HIP events on the launch stream, run right after the timed region (N > 1: the slowest rank's median)",
-                     "algorithmic_bytes_per_launch": BYTES_PER_STEP * n,
-                     "achievable_GBps": HBM_ACHIEVABLE_GBPS, "frac_of_achievable": achieved / HBM_ACHIEVABLE_GBPS,
-                     "achievable_note": "MI355X_MICROARCH.md: HBM 8 TB/s peak (spec), about 6.3 TB/s achievable",
-                     "served_by": "hbm" if pol == "2" else "hbm + infinity cache" if pol == "1" else "infinity cache",
-                     "frac_hbm_only": configs["hbm_only_frac"] if configs else None,
-                     "frac_hbm_only_note": "the same kernel at 2^24 cubes (1.8 GB ping-pong, nothing cached): per_config '16M step (HBM only)'",
-                     "device_copy_GBps": copy_gbps, "frac_of_device_copy": achieved / copy_gbps if copy_gbps else None,
-                     "device_copy_note": f"hipMemcpy D2D (torch copy_) of the same {state_mb:.0f} MB state buffer, read + write bytes",
-                     "note": served},
     }
+    if args.full:
+        out["roofline"] = roofline(_lib, n, args, elapsed, dev_ms, launch_us, launch_min, launch_max, n_batches, copy_gbps, configs)
     if configs:
         out["roofline"]["per_config"] = per_config_summary(configs)
         out["roofline"]["per_config_note"] = ("every other workload of BASELINE.json / SURVEY 8d, timed outside the headline region (median of 3 event-timed "
                                               "batches): frac = bytes / (launch_us * 1e-6) / 8e12; full records under `configs`")
     if per_rank:
         out["per_gpu"] = per_rank
-        out["roofline"]["aggregate_GBps"] = sum(r["GBps"] for r in per_rank)
-        out["roofline"]["aggregate_frac_of_n_x_peak"] = out["roofline"]["aggregate_GBps"] / (HBM_PEAK_GBPS * world)
+        if args.full:
+            out["roofline"]["aggregate_GBps"] = sum(r["GBps"] for r in per_rank)
+            out["roofline"]["aggregate_frac_of_n_x_peak"] = out["roofline"]["aggregate_GBps"] / (HBM_PEAK_GBPS * world)
         out["config"]["process_group"] = args.backend
         # which card every rank ran on: distinct_devices < n_gpus means ranks shared a GPU (a --share-gpu rehearsal), never silently
         cards = {(r["pci_bus_id"] or f"requested:{r['requested_device_index']}") for r in per_rank}
@@ -773,7 +831,7 @@ COMPACT_LIMIT = 4096      # the driver parses the LAST stdout line and keeps 8 K
 
 
 def compact_record(full, full_path=None):
-    """The FINAL stdout line: the contract's keys, `roofline`, `cpu_baseline` and ten scalar extras -- no notes, no per-config table,
+    """The FINAL stdout line: the contract's keys and, from a --full run, `roofline`, `cpu_baseline` and ten scalar extras -- no notes, no per-config table,
     every string under 120 characters, the whole line under COMPACT_LIMIT bytes.  Everything else lives in the full record
     (--full-out, default bench_full.json next to this file; the builder's copies are under profiles/)."""
     def cut(v, n=118):
@@ -791,13 +849,14 @@ def compact_record(full, full_path=None):
                                      + ("configs[1] shape at the metric's batch 4M" if n == N_CUBES else "configs[3] shape: 1M cubes per GPU" if n == 1 << 20 else "custom batch"), 200),
                      **pick(full["config"], ("cubes_per_gpu", "total_cubes", "bytes_per_step_algorithmic", "parallelism", "process_group", "distinct_devices",
                                              "shared_gpu_rehearsal"))}
-    r = full["roofline"]
-    out["roofline"] = pick(r, ("bound", "achieved", "peak", "unit", "frac", "traffic", "kernel", "launch_us", "launch_us_min", "launch_us_max", "launch_us_timed_region",
-                               "launch_batches", "launches_per_batch", "frac_timed_region", "frac_wall_clock", "frac_hbm_only", "algorithmic_bytes_per_launch",
-                               "served_by", "achievable_GBps", "frac_of_achievable", "device_copy_GBps", "frac_of_device_copy", "aggregate_GBps",
-                               "aggregate_frac_of_n_x_peak"))
-    out["roofline"]["frac_basis"] = "launch_us = median event-timed batch of K launches after the timed region"
-    out["roofline"]["traffic_source"] = "profiles/traffic.json (builder's rocprofv3 --pmc passes)" if r.get("traffic") is not None else None
+    r = full.get("roofline", {})                                      # a plain run has none
+    if r:
+        out["roofline"] = pick(r, ("bound", "achieved", "peak", "unit", "frac", "traffic", "kernel", "launch_us", "launch_us_min", "launch_us_max",
+                                   "launch_us_timed_region", "launch_batches", "launches_per_batch", "frac_timed_region", "frac_wall_clock", "frac_hbm_only",
+                                   "algorithmic_bytes_per_launch", "served_by", "achievable_GBps", "frac_of_achievable", "device_copy_GBps",
+                                   "frac_of_device_copy", "aggregate_GBps", "aggregate_frac_of_n_x_peak"))
+        out["roofline"]["frac_basis"] = "launch_us = median event-timed batch of K launches after the timed region"
+        out["roofline"]["traffic_source"] = "profiles/traffic.json (builder's rocprofv3 --pmc passes)" if r.get("traffic") is not None else None
     if "cpu_baseline" in full:
         c = full["cpu_baseline"]
         out["cpu_baseline"] = pick(c, ("value", "unit", "cores", "kind", "single_core_steps_per_s", "numpy_env_1core_steps_per_s", "numpy_env_allcores_steps_per_s",
@@ -806,8 +865,11 @@ def compact_record(full, full_path=None):
     if not (world > 1 or full["config"].get("process_group")):
         out["config"]["pci_bus_id"] = full["per_gpu"][0]["pci_bus_id"] if full.get("per_gpu") else None
     else:
-        out["per_gpu"] = [{"rank": p["rank"], "dev": p["device_index"], "pci": p["pci_bus_id"], "stream": p["stream_id"], "launch_us": sig(p["launch_us"], 5),
-                           "gsteps_per_s": sig(p["steps_per_s"] / 1e9, 5), "sha12": p["initial_state_sha256_first_cubes"][:12]} for p in full["per_gpu"]]
+        out["per_gpu"] = [{"rank": p["rank"], "dev": p["device_index"], "pci": p["pci_bus_id"], "stream": p["stream_id"], "gsteps_per_s": sig(p["steps_per_s"] / 1e9, 5)}
+                          for p in full["per_gpu"]]
+        if r:                                                         # --full: the per-rank launch time and initial-state sample
+            for q, p in zip(out["per_gpu"], full["per_gpu"]):
+                q.update(launch_us=sig(p["launch_us"], 5), sha12=p["initial_state_sha256_first_cubes"][:12])
     cf = full.get("configs")
     if cf:                                                            # at most ten scalars of the other workloads; their records are in the full file
         pc = {x["name"]: x for x in r.get("per_config", [])}

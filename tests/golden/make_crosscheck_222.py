@@ -17,21 +17,23 @@ Two solvers, as test.py:103-158 runs them: the greedy arg-max policy (model.py:4
 the REFERENCE'S OWN MCTS class (mcts.py, imported unmodified; config.yaml:29-32: 50 simulations, cpuct 1, virtual loss 150,
 value_min -10) for seeds 0..19, on reset(seed, k) scrambles of depth k in DEPTHS.
 
-Runs only in the build container (needs /root/reference); writes tests/golden/crosscheck_222.npz holding ACTIONS, OUTCOMES AND
-RATES ONLY -- no weights, no reference source:
+Needs a checkout of the reference project (REF below) and its checkpoint; writes tests/golden/crosscheck_222_weights.npz (the checkpoint's
+float32 tensors by name: model weights, no code) and tests/golden/crosscheck_222.npz holding ACTIONS, OUTCOMES AND RATES ONLY:
     seeds, ks, scramble [N, 14] (no-op 6 padded), actions [N, T], cols [N, T, 7], done [N, T], solve_step [N]      greedy, shipped
     mcts_seeds, mcts_ks, mcts_scramble [M, 14], mcts_found [M], mcts_sims [M], mcts_solution [M, 56] (6 padded),
     mcts_cols [M, 56, 7]                                                                                         MCTS, shipped
     conventions [5], depths [9], greedy_rate [5, 9], mcts_rate [5, 9]                                            every convention
-The checkpoint is read statically (tests/test_crosscheck_222.py: pickle opcodes + raw float32 zip members, nothing is
+The checkpoint is read statically (read_state_dict_statically: pickle opcodes + raw float32 zip members, nothing is
 unpickled or executed).
 
     python tests/golden/make_crosscheck_222.py
 """
 import os
+import pickletools
 import random
 import sys
 import types
+import zipfile
 
 os.environ.setdefault("MPLBACKEND", "Agg")
 import numpy as np
@@ -41,7 +43,7 @@ ROOT = os.path.dirname(os.path.dirname(HERE))
 REF = "/root/reference"
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 
-from test_crosscheck_222 import CKPT, elu, policy_logits, read_state_dict_statically  # noqa: E402
+from test_crosscheck_222 import elu, policy_logits  # noqa: E402
 from oracle.oracle_np import OracleCubeEnv  # noqa: E402
 
 T = 30
@@ -51,6 +53,39 @@ LSOL = 56          # longest action list MCTS.train can return within 50 simulat
 CONVENTIONS = ("shipped", "ori_left", "ori_shifted", "pieces_reversed", "not_transposed")
 GREEDY_SEEDS, MCTS_SEEDS = range(40), range(20)
 MCTS_CFG = {"mcts": {"virtual_loss_const": 150, "cpuct": 1.0, "value_min": -10.0, "numMCTSSim": 50}, "test": {"cube_size": 2}}
+
+
+CKPT = os.path.join(REF, "pretrained", "222model.pt")
+
+
+def read_state_dict_statically(path):
+    z = zipfile.ZipFile(path)
+    pkl = [n for n in z.namelist() if n.endswith("data.pkl")][0]
+    prefix = pkl[: -len("data.pkl")]
+    ops = list(pickletools.genops(z.read(pkl)))
+    out, name, i = {}, None, 0
+    while i < len(ops):
+        op, arg, _ = ops[i]
+        if op.name == "BINUNICODE" and arg == "optimizer_state_dict":
+            break
+        if op.name == "BINUNICODE" and "_net." in str(arg):
+            name = arg
+        if op.name == "BINPERSID" and name is not None:
+            j = i - 1                                   # storage key = last all-digit string before the persid
+            while not (ops[j][0].name == "BINUNICODE" and str(ops[j][1]).isdigit()):
+                j -= 1
+            key = ops[j][1]
+            ints, k = [], i + 1                         # after persid: offset, then the shape tuple
+            while ops[k][0].name.startswith("BININT"):
+                ints.append(ops[k][1])
+                k += 1
+            assert ops[k][0].name.startswith("TUPLE")
+            offset, shape = ints[0], tuple(ints[1:])
+            raw = np.frombuffer(z.read(f"{prefix}data/{key}"), dtype="<f4")
+            out[name] = raw[offset: offset + int(np.prod(shape))].reshape(shape).copy()
+            name = None
+        i += 1
+    return out
 
 
 class ConventionEnv(OracleCubeEnv):
@@ -141,6 +176,7 @@ def mcts_trial(ref_mcts, net, env, seed, k):
 
 def main():
     sd = read_state_dict_statically(CKPT)
+    np.savez_compressed(os.path.join(HERE, "crosscheck_222_weights.npz"), **sd)
     ref_mcts = import_reference_mcts()
     net = StaticNet(sd)
     out = {}

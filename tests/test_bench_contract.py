@@ -1,5 +1,6 @@
-"""bench.py prints ONE compact JSON line (< 4 KB, the LAST stdout line, carrying `roofline` and `cpu_baseline`) and writes the full
-record to --full-out (GPU); its CPU leg and the compact-record builder work on their own (CPU)."""
+"""bench.py prints ONE compact JSON line (< 4 KB, the LAST stdout line).  A plain run carries the headline alone and can dump what its
+last timed step computed (--dump-outputs); with --full the line carries `roofline` and `cpu_baseline` and the full record goes to
+--full-out (GPU); its CPU leg and the compact-record builder work on their own (CPU)."""
 import json
 import os
 import subprocess
@@ -89,7 +90,7 @@ def test_cpu_baseline_leg_shape():
 
 @pytest.mark.gpu
 def test_bench_json_line(tmp_path):
-    c, d = _bench([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "3"], tmp_path, timeout=600)
+    c, d = _bench([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "20", "--warmup", "3"], tmp_path, timeout=600)
     # the compact line (what the driver parses): contract keys, roofline and cpu_baseline IN THAT LINE, ten scalar extras
     assert c["n_gpus"] == 1 and c["steps"] == 20 and c["unit"] == "steps/s" and c["dtype"] == "u8" and c["vs_baseline"] is None
     assert c["scaling"] == "weak" and c["higher_is_better"] is True and "workload" in c["config"] and "model" not in c["config"]
@@ -188,7 +189,7 @@ def test_bench_distributed_branch_world1_rccl(how, tmp_path):
     once through --force-dist and once under the launcher the driver uses.  (The reference's workers never exchange anything
     either: train.py:85-92,141-147.)"""
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
-    tail = ["--steps", "20", "--warmup", "3", "--no-cpu", "--no-configs", "--backend", "nccl", "--cubes-per-gpu", str(1 << 20)]
+    tail = ["--full", "--steps", "20", "--warmup", "3", "--no-cpu", "--no-configs", "--backend", "nccl", "--cubes-per-gpu", str(1 << 20)]
     if how == "force_dist":
         for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
             env.pop(k, None)
@@ -223,7 +224,7 @@ def test_bench_two_ranks_rehearsal(oracle, tmp_path):
     import hashlib
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", _free_port(), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "3", "--backend", "gloo",
+           "--master-port", _free_port(), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full", "--steps", "20", "--warmup", "3", "--backend", "gloo",
            "--cubes-per-gpu", str(1 << 20)]
     # two ranks, one visible GPU: refused without --share-gpu (the line must never report N GPUs from fewer cards without saying so)
     bad = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
@@ -264,7 +265,7 @@ def test_bench_many_ranks_rehearsal(oracle, tmp_path):
     ranks = GPU_PROCESS_LIMIT - 2
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(ranks), "--master-addr", "127.0.0.1",
-           "--master-port", _free_port(), os.path.join(ROOT, "bench.py"), "--gpus", str(ranks), "--steps", "20", "--warmup", "3",
+           "--master-port", _free_port(), os.path.join(ROOT, "bench.py"), "--gpus", str(ranks), "--full", "--steps", "20", "--warmup", "3",
            "--backend", "gloo", "--share-gpu", "--cubes-per-gpu", str(1 << 20)]
     c, d = _bench(cmd, tmp_path, env=env, timeout=900)
     assert c["config"]["distinct_devices"] == 1 and c["config"]["shared_gpu_rehearsal"] is True and len(c["per_gpu"]) == ranks
@@ -288,7 +289,7 @@ def test_bench_eight_ranks_dry_run(ranks, tmp_path):
     real 8-GPU run cannot fail on anything but the kernels (which the one-GPU tests cover).  Pattern: train.py:85-92."""
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", RC_BENCH_DRY="1", OMP_NUM_THREADS="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(ranks), "--master-addr", "127.0.0.1",
-           "--master-port", _free_port(), os.path.join(ROOT, "bench.py"), "--gpus", str(ranks), "--steps", "5", "--warmup", "1", "--backend", "gloo",
+           "--master-port", _free_port(), os.path.join(ROOT, "bench.py"), "--gpus", str(ranks), "--full", "--steps", "5", "--warmup", "1", "--backend", "gloo",
            "--cubes-per-gpu", str(1 << 20)]
     c, d = _bench(cmd, tmp_path, env=env, timeout=600)
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data",
@@ -311,3 +312,62 @@ def test_bench_eight_ranks_dry_run(ranks, tmp_path):
     env1 = {k: v for k, v in env.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
     bad = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--force-dist", "--backend", "nccl"], capture_output=True, text=True, timeout=300, cwd=ROOT, env=env1)
     assert bad.returncode != 0 and "RC_BENCH_DRY" in bad.stderr
+
+
+HEADLINE_KEYS = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config")
+
+
+def _plain(cmd, env=None, timeout=600):
+    """run a plain bench.py (no --full) -> its one JSON line, which carries the headline and nothing measured beyond it"""
+    out = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout, cwd=ROOT, env=env)
+    assert out.returncode == 0, out.stderr[-3000:]
+    lines = out.stdout.splitlines()
+    assert len([l for l in lines if l.startswith("{")]) == 1 and lines[-1].startswith("{")
+    c = _strict(lines[-1])
+    for k in HEADLINE_KEYS:
+        assert k in c, k
+    assert not {"roofline", "cpu_baseline", "extras", "full_record", "configs"} & set(c), sorted(c)
+    assert abs(c["value"] - c["config"]["total_cubes"] / (c["ms_per_step"] * 1e-3)) < 1e-6 * c["value"]      # ms_per_step = one timed step
+    return c
+
+
+def test_bench_plain_dry_run_is_lean():
+    """A plain N = 2 dry run: the headline keys and the short per-rank list, no roofline / cpu_baseline / extras / full record.  The dump
+    sample is fixed: the same 2^17 ascending distinct indices every time."""
+    env = dict(os.environ, MASTER_ADDR="127.0.0.1", RC_BENCH_DRY="1", OMP_NUM_THREADS="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
+    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
+           "--master-port", _free_port(), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "1", "--backend", "gloo",
+           "--cubes-per-gpu", str(1 << 20)]
+    c = _plain(cmd, env=env)
+    assert c["dry_run"] is True and c["n_gpus"] == 2 and c["steps"] == 5 and c["unit"] == "steps/s" and c["dtype"] == "u8"
+    assert [x["stream"] for x in c["per_gpu"]] == [0, 1] and not any("sha12" in x or "launch_us" in x for x in c["per_gpu"])
+    assert c["config"]["distinct_devices"] == 2
+    sys.path.insert(0, ROOT)
+    import bench
+    idx = bench.dump_sample(bench.N_CUBES)
+    assert len(idx) == bench.DUMP_CUBES == 1 << 17 and (np.diff(idx) > 0).all() and 0 <= idx[0] and idx[-1] < bench.N_CUBES
+    assert (bench.dump_sample(bench.N_CUBES) == idx).all() and (bench.dump_sample(1000) == np.arange(1000)).all()
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_dumps_last_step_outputs(oracle, tmp_path):
+    """bench.py without --full: the headline line alone, and --dump-outputs writes what the last of the warmup + timed steps computed for
+    the fixed sample of cubes -- replayed here through the oracle from the same seeded scramble and actions."""
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    n, steps, warmup = bench.DUMP_CUBES + 4097, 20, 3
+    out_dir = tmp_path / "outputs"
+    c = _plain([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(steps), "--warmup", str(warmup), "--cubes-per-gpu", str(n),
+                "--dump-outputs", str(out_dir)])
+    assert c["n_gpus"] == 1 and c["steps"] == steps and c["warmup"] == warmup and c["config"]["cubes_per_gpu"] == n and c["value"] > 0
+    assert sorted(os.listdir(out_dir)) == ["done.npy", "states.npy"]
+    states, done = np.load(out_dir / "states.npy"), np.load(out_dir / "done.npy")
+    idx = bench.dump_sample(n)
+    assert states.dtype == np.float32 and states.shape == (len(idx), 54) and done.dtype == np.float32 and done.shape == (len(idx),)
+    assert states.nbytes + done.nbytes <= 64 << 20
+    st = oracle.adi(3, n, bench.SCRAMBLE_DEPTH, seed=bench.SCRAMBLE_SEED, stream=0, threads=4, want_children=False)["parents"][:, -1]
+    acts = torch.randint(0, 12, (n,), generator=torch.Generator(device="cuda:0").manual_seed(1), device="cuda:0", dtype=torch.uint8).cpu().numpy()
+    for _ in range(warmup + steps):
+        st, _, d, _ = oracle.step(3, st, acts, threads=4)
+    assert (states == st[idx]).all() and (done == d[idx]).all()

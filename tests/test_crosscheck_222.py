@@ -4,48 +4,19 @@ The reference ships a trained 2x2x2 DeepCube checkpoint (pretrained/222model.pt)
 py222 module that defined its state encoding.  If our restated 2x2x2 tables / one-hot convention
 match the authors', their policy net must solve shallow scrambles of OUR cubes greedily.
 
-Runs only where /root/reference exists (the build container); the checkpoint never travels.
-The pickle is NOT executed: tensor names, storage keys and shapes are read from its opcodes with
-pickletools, the float32 payloads straight from the zip members."""
+The checkpoint's float32 weights are the fixture tests/golden/crosscheck_222_weights.npz (tensor name -> array), which
+tests/golden/make_crosscheck_222.py reads from the checkpoint statically: nothing is unpickled or executed."""
 import os
-import pickletools
-import zipfile
 
 import numpy as np
-import pytest
 
-CKPT = "/root/reference/pretrained/222model.pt"
-pytestmark = pytest.mark.skipif(not os.path.exists(CKPT), reason="reference checkpoint not present on this box")
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
-def read_state_dict_statically(path):
-    z = zipfile.ZipFile(path)
-    pkl = [n for n in z.namelist() if n.endswith("data.pkl")][0]
-    prefix = pkl[: -len("data.pkl")]
-    ops = list(pickletools.genops(z.read(pkl)))
-    out, name, i = {}, None, 0
-    while i < len(ops):
-        op, arg, _ = ops[i]
-        if op.name == "BINUNICODE" and arg == "optimizer_state_dict":
-            break
-        if op.name == "BINUNICODE" and "_net." in str(arg):
-            name = arg
-        if op.name == "BINPERSID" and name is not None:
-            j = i - 1                                   # storage key = last all-digit string before the persid
-            while not (ops[j][0].name == "BINUNICODE" and str(ops[j][1]).isdigit()):
-                j -= 1
-            key = ops[j][1]
-            ints, k = [], i + 1                         # after persid: offset, then the shape tuple
-            while ops[k][0].name.startswith("BININT"):
-                ints.append(ops[k][1])
-                k += 1
-            assert ops[k][0].name.startswith("TUPLE")
-            offset, shape = ints[0], tuple(ints[1:])
-            raw = np.frombuffer(z.read(f"{prefix}data/{key}"), dtype="<f4")
-            out[name] = raw[offset: offset + int(np.prod(shape))].reshape(shape).copy()
-            name = None
-        i += 1
-    return out
+def load_weights():
+    """the checkpoint's state dict (model weights only) from the fixture"""
+    with np.load(os.path.join(GOLDEN, "crosscheck_222_weights.npz")) as z:
+        return {k: z[k] for k in z.files}
 
 
 def elu(x):
@@ -62,7 +33,7 @@ def policy_logits(sd, x):
 
 def test_checkpoint_policy_solves_our_222_cubes():
     from oracle.oracle_np import OracleCubeEnv
-    sd = read_state_dict_statically(CKPT)
+    sd = load_weights()
     assert sd["encoder_net.1.weight"].shape == (512, 147) and sd["policy_net.2.weight"].shape == (6, 64)
     env = OracleCubeEnv(None, 2)
     rates = {}
@@ -83,7 +54,7 @@ def test_checkpoint_policy_solves_our_222_cubes():
 
 
 def _fixture():
-    return np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "crosscheck_222.npz"))
+    return np.load(os.path.join(GOLDEN, "crosscheck_222.npz"))
 
 
 def test_fixture_matches_live_checkpoint_run():
@@ -91,7 +62,7 @@ def test_fixture_matches_live_checkpoint_run():
     on the restated env today: regenerate a slice and compare."""
     from oracle.oracle_np import OracleCubeEnv
     g = _fixture()
-    sd = read_state_dict_statically(CKPT)
+    sd = load_weights()
     env = OracleCubeEnv(None, 2)
     for i in range(0, len(g["seeds"]), 7):
         state = env.reset(seed=int(g["seeds"][i]), scramble_count=int(g["ks"][i]))
@@ -107,9 +78,9 @@ def test_negative_controls_regenerate():
     equal what the fixture recorded for those seeds' population within sampling, and every control stays far below the
     shipped convention."""
     import sys
-    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden"))
+    sys.path.insert(0, GOLDEN)
     import make_crosscheck_222 as mk
-    sd = read_state_dict_statically(CKPT)
+    sd = load_weights()
     live = {}
     for conv in mk.CONVENTIONS:
         env = mk.ConventionEnv(conv)

@@ -1,8 +1,9 @@
 import os, sys, json
-sys.path.insert(0, "/root/repo")
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, ROOT)
 import torch
 from rubiks_cube_solver_amd import _lib, ops
-sys.path.insert(0, "/root/repo/tools")
+sys.path.insert(0, os.path.join(ROOT, "tools"))
 from microbench import timeit
 m = 1 << 20
 a = ops.alloc_states(m, 3, "cuda"); ops.fill_solved(a, m, 3); ops.scramble(a, m, 3, 20, seed=1)

@@ -5,7 +5,7 @@
 
 Writes
   profiles/<round>_bench.json               the bench.py JSON line of the session
-  profiles/<round>_kernel_stats.csv         rocprofv3 --kernel-trace --stats of `python3 bench.py --no-cpu --no-configs --steps 200 --warmup 20`
+  profiles/<round>_kernel_stats.csv         rocprofv3 --kernel-trace --stats of `python3 bench.py --full --no-cpu --no-configs --steps 200 --warmup 20`
   profiles/<round>_kernel_stats_configs.csv the same with the configs (k_adi, k_expand, dense kernels, ...)
   profiles/<round>_pmc.json                 mean FETCH_SIZE / WRITE_SIZE / SQ counters per kernel (separate --pmc passes)
   profiles/<round>_adi_fresh_processes.json k_adi / k_expand averages of FIVE fresh processes (rocprofv3 kernel stats each)
@@ -111,7 +111,7 @@ if HEAD in headline and "FETCH_SIZE" in headline[HEAD] and "WRITE_SIZE" in headl
     json.dump({"round": rnd, "kernel": HEAD, "k_step_bytes_per_launch": rd + wr, "read_bytes": rd, "write_bytes": wr,
                "launches_counted": {"FETCH_SIZE": s_["FETCH_SIZE"]["launches"], "WRITE_SIZE": s_["WRITE_SIZE"]["launches"]},
                "note": "FETCH_SIZE KiB x 1024 x 2 (gfx950 wide-read correction) + WRITE_SIZE KiB x 1024, separate --pmc passes over "
-                       "`python3 bench.py --no-cpu --no-configs --steps 10 --warmup 2` (2^22 cubes, move + done flag; the headline launches only); "
+                       "`python3 bench.py --full --no-cpu --no-configs --steps 10 --warmup 2` (2^22 cubes, move + done flag; the headline launches only); "
                        "algorithmic = 110 B x 2^22 = 461373440.  These are the L2's fabric-side request counters: Infinity-Cache hits are counted, "
                        "so this is fabric traffic, an upper bound of DRAM traffic"},
               open(os.path.join(P, "traffic.json"), "w"), indent=1)
