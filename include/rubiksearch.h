@@ -1,0 +1,90 @@
+/*
+ * rubiksearch.h -- C ABI of librubiksearch.so: the device half of a batched beam search guided by a value net (DESIGN.md
+ * "Beam search").  The net itself is the caller's (one forward per chunk of candidates, between rc_search_expand and
+ * rc_search_select); librubikhip's rc_onehot_from_code turns the candidate codes written here into its dense input.
+ *
+ * Conventions (those of include/rubikhip.h)
+ *   - Every buffer is DEVICE memory owned by the caller; the library allocates nothing.  Calls are stream-ordered, never
+ *     synchronise with the host, keep no state, and return 0 or a negative code (-1 bad argument, -2 HIP failure);
+ *     rc_search_last_error() gives the calling thread's last message.
+ *   - P problems, beam width W (1 <= W <= 65536).  Beam cube b = p * W + w (slot w of problem p) lives in a TILED state buffer
+ *     [tiles][S][pitch] with tiles = ceil(P * W / pitch) and a power-of-two pitch >= 512 (S * pitch < 2^32);
+ *     NBp = tiles * pitch.  Every per-slot array below has NBp entries.
+ *   - Candidate c = w * A + a of problem p (child a of slot w) is stored CHILD-MAJOR at j = a * NBp + b:
+ *       code   [A * tiles][SLOTS][pitch]   RC_FMT_CODE rows: one tiled code buffer of A * NBp cubes, ready for
+ *                                           rc_onehot_from_code (a chunk that starts on a tile boundary is a buffer of its own)
+ *       flags  [A][NBp]  uint8             RC_SEARCH_VALID | RC_SEARCH_SOLVED (expand), RC_SEARCH_SURVIVOR (select)
+ *       keys   [KW][A][NBp] uint64          the child's stickers, 3 bits each, 16 per word: the 48 non-centre stickers of a
+ *                                           3x3x3 (KW = 3), all 24 of a 2x2x2 (KW = 2): equal keys <=> equal sticker vectors
+ *       scores [A][NBp] float               the value net's output for the candidate (written by the caller)
+ *   - `depth` points at ONE device int32: the 1-based depth being searched.  The kernels read it, the caller advances it
+ *     (a captured depth step replays unchanged).
+ *   - Actions are the env's (include/rubikhip.h); the inverse of a is a ^ 1; A (12 | 6) is the no-op.
+ */
+#ifndef RUBIKSEARCH_H
+#define RUBIKSEARCH_H
+
+#include <stdint.h>
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define RC_SEARCH_VALID 1u     /* a live slot of an active problem, and a does not undo the move that made the slot */
+#define RC_SEARCH_SOLVED 2u    /* the child is solved (every face equals its first sticker) */
+#define RC_SEARCH_SURVIVOR 4u  /* valid and the lowest c among the valid candidates of its problem with the same stickers */
+
+/* First 16 hex digits of a sha256 over rc_search.hip, rc_device.h, rc_tables.h and this header (rubiks-cube-solver_amd/_build.py
+ * SEARCH_SOURCES), embedded at build time; "unhashed" for a build without -DRC_SRC_HASH.  Static storage. */
+const char *rc_search_build_id(void);
+
+/* Message of the calling thread's last failed call ("" if none). */
+const char *rc_search_last_error(void);
+
+/* Bytes of the workspace rc_search_select needs: its exact-dedup hash table, a power of two of 64-bit slots and at least
+ * 2 * A * P * W of them; -1 for bad arguments.  Host only. */
+int64_t rc_search_workspace_bytes(int cube_size, int64_t n_problems, int width);
+
+/* Roots.  Cube p of `roots` (a tiled state buffer of root_pitch, e.g. a VecCubeEnv's stickers; only read) becomes slot 0 of
+ * problem p: beam[p * W] = root, last_action[p * W] = A.  A solved root gets live = 0, active = 0, length = 0; any other
+ * live = 1, active = 1, length = -1.  solution[p] = -1. */
+int rc_search_init(const uint8_t *roots, int64_t n_problems, int64_t root_pitch, int cube_size, int width, uint8_t *beam,
+                   int64_t pitch, uint8_t *last_action, int32_t *live, uint8_t *active, int32_t *length, int32_t *solution,
+                   void *stream);
+
+/* Expand: all A children of every slot of the beam (live or not: dead slots are written too and must be ignored) -- code,
+ * flags and key at j = a * NBp + b.  A candidate is VALID iff active[p], w < live[p] and a != last_action[b] ^ 1. */
+int rc_search_expand(const uint8_t *beam, int64_t n_problems, int width, int64_t pitch, int cube_size, const uint8_t *last_action,
+                     const int32_t *live, const uint8_t *active, uint8_t *code, uint8_t *flags, uint64_t *keys, void *stream);
+
+/* Select, per active problem p (three launches: clear the workspace's hash table, insert every valid candidate with 64-bit
+ * atomics -- equal keys keep the lowest c by rule, not by timing -- then one workgroup per problem):
+ *   solved check  a valid solved candidate exists: p is solved at *depth -- solution[p] = the lowest such c,
+ *                 length[p] = *depth, active[p] = 0, sel_count[p] = 0;
+ *   otherwise     the survivors (flag RC_SEARCH_SURVIVOR is set on them) are ranked by score descending, then c ascending,
+ *                 NaN below -inf, -0 == +0; the best min(W, survivors) are kept and listed in ascending c:
+ *                 sel_parent[p * W + i] = w, sel_action[p * W + i] = a of the i-th kept candidate, sel_count[p] = their number.
+ * Inactive problems get sel_count 0.  workspace: rc_search_workspace_bytes(...) bytes or more, 16-byte aligned, scratch. */
+int rc_search_select(uint8_t *flags, const uint64_t *keys, const float *scores, int64_t n_problems, int width, int64_t pitch,
+                     int cube_size, const int32_t *live, uint8_t *active, int32_t *length, int32_t *solution, const int32_t *depth,
+                     uint16_t *sel_parent, uint8_t *sel_action, int32_t *sel_count, void *workspace, int64_t workspace_bytes,
+                     void *stream);
+
+/* Advance: slot i < sel_count[p] of the new beam (beam_out, tiled like beam_in; the two must not overlap) = beam_in slot
+ * sel_parent moved by sel_action; last_action = sel_action; history row *depth - 1 of hist_parent / hist_action
+ * [max_depth][NBp] records (sel_parent, sel_action); live[p] = sel_count[p].  Slots past sel_count get a copy of beam_in's
+ * slot and the no-op (deterministic, never read as live). */
+int rc_search_advance(const uint8_t *beam_in, uint8_t *beam_out, int64_t n_problems, int width, int64_t pitch, int cube_size,
+                      const uint16_t *sel_parent, const uint8_t *sel_action, const int32_t *sel_count, int32_t *live,
+                      uint8_t *last_action, uint16_t *hist_parent, uint8_t *hist_action, const int32_t *depth, int max_depth,
+                      void *stream);
+
+/* Backtrack: actions[d * n_problems + p] (uint8 [max_depth][P]) = the moves of problem p's solution in order, then the no-op A;
+ * all no-ops where length <= 0.  Reads length, solution and the history rows written by rc_search_advance. */
+int rc_search_backtrack(const uint16_t *hist_parent, const uint8_t *hist_action, int64_t n_problems, int width, int64_t pitch,
+                        int cube_size, int max_depth, const int32_t *length, const int32_t *solution, uint8_t *actions, void *stream);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* RUBIKSEARCH_H */

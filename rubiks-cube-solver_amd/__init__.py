@@ -18,7 +18,7 @@ __all__ = ["get_env_config", "get_tables", "ACTION_NAMES", "ops", "make_env", "C
 def __getattr__(name):  # torch-dependent parts load lazily
     import importlib
 
-    if name in ("ops", "_lib", "vec_env", "cube_env", "adi", "mcts_batched", "rollout", "dist", "py333", "py222", "replay"):
+    if name in ("ops", "_lib", "vec_env", "cube_env", "adi", "mcts_batched", "rollout", "dist", "py333", "py222", "replay", "search"):
         return importlib.import_module(f"{__name__}.{name}")
     if name == "VecCubeEnv":
         return importlib.import_module(f"{__name__}.vec_env").VecCubeEnv

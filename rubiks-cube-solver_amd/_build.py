@@ -16,6 +16,8 @@ MARKER = b"rc-build-id:"                     # the id is stored in the binary as
 HIP_SOURCES = (os.path.join(_HERE, "csrc", "rubikhip.hip"), os.path.join(_HERE, "csrc", "rc_device.h"), os.path.join(_HERE, "csrc", "rc_tables.h"),
                os.path.join(_ROOT, "include", "rubikhip.h"))
 TREE_SOURCES = (os.path.join(_HERE, "csrc", "rc_tree.cpp"), os.path.join(_ROOT, "include", "rubiktree.h"))
+SEARCH_SOURCES = (os.path.join(_HERE, "csrc", "rc_search.hip"), os.path.join(_HERE, "csrc", "rc_device.h"),
+                  os.path.join(_HERE, "csrc", "rc_tables.h"), os.path.join(_ROOT, "include", "rubiksearch.h"))
 
 
 def source_hash(paths) -> str | None:

@@ -1,0 +1,605 @@
+// rc_search.hip -- kernels and C ABI of librubiksearch.so (include/rubiksearch.h): the device half of the batched beam search
+// (DESIGN.md "Beam search").  gfx950 only.  Built on rc_device.h: packed moves (fixed_move, action_masks + apply_move), the solved
+// test (unsolved / done_bytes), the compact code (encode) and buffer row access.
+//
+//   k_init       roots -> slot 0 of every problem; solved roots end at length 0
+//   k_expand     all A children of every beam slot: RC_FMT_CODE rows, valid / solved flags, exact sticker keys
+//   k_insert     exact dedup: every valid candidate into a global open-addressing table (64-bit CAS); equal keys keep the lowest
+//                candidate by atomicMin, so the owner of a key does not depend on the order in which the atomics land
+//   k_select     one workgroup per problem: solved check, survivor marks, radix select of the W best (score desc, c asc), the kept
+//                candidates listed in ascending c
+//   k_advance    gather + move the kept parents into the other beam buffer, last action, history row
+//   k_backtrack  history -> actions [D][P]
+#include <hip/hip_runtime.h>
+
+#include <cstdio>
+#include <cstring>
+
+#include "../../include/rubiksearch.h"
+#include "rc_device.h"
+
+using namespace rc;
+
+namespace {
+
+constexpr int kWave = 64;
+constexpr int kSpan = kWave * 4;                 // cubes per wave in the packed kernels (4 per lane, one dword per sticker row)
+constexpr int kSelThreads = 256;
+constexpr uint64_t kEmpty = ~0ull;
+
+// Key layout: the stickers that can change, 3 bits each, 16 per 64-bit word (3x3x3: the 48 non-centre stickers; centres never move).
+template <class T>
+struct Key {
+    static constexpr int N = T::SIZE == 3 ? 48 : 24;
+    static constexpr int KW = (N + 15) / 16;
+    static constexpr int sticker(int k) { return T::SIZE == 3 ? (k / 8) * 9 + (k % 8 < 4 ? k % 8 : k % 8 + 1) : k; }
+};
+
+// byte offset of cube b's row 0 in a [tiles][rows][pitch] buffer (pitch = 1 << shift)
+__device__ __forceinline__ int64_t tiled(int64_t b, int64_t pitch, int shift, int rows) {
+    return (b >> shift) * rows * pitch + (b & (pitch - 1));
+}
+
+// ------------------------------------------------------------------------------------------------- roots
+template <class T>
+__global__ void __launch_bounds__(256) k_init(const uint8_t *roots, int64_t n, int64_t rpitch, int rshift, uint8_t *beam, int64_t pitch,
+                                              int shift, int width, uint8_t *last, int32_t *live, uint8_t *active, int32_t *length,
+                                              int32_t *solution) {
+    const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (p >= n) return;
+    const int64_t b = p * width;
+    const uint8_t *src = roots + (rshift >= 63 ? p : tiled(p, rpitch, rshift, T::S));
+    uint8_t *dst = beam + tiled(b, pitch, shift, T::S);
+    bool solved = true;
+    uint8_t first = 0;
+    for (int i = 0; i < T::S; ++i) {
+        const uint8_t v = src[(int64_t)i * rpitch];
+        dst[(int64_t)i * pitch] = v;
+        if (i % T::FACE == 0) first = v;
+        else solved = solved && v == first;                    // py333.py:229-233: every face equals its first sticker
+    }
+    last[b] = (uint8_t)T::A;
+    live[p] = solved ? 0 : 1;
+    active[p] = solved ? 0 : 1;
+    length[p] = solved ? 0 : -1;
+    solution[p] = -1;
+}
+
+// ------------------------------------------------------------------------------------------------ expand
+struct ExpandArgs {
+    const uint8_t *beam, *last_action;
+    const int32_t *live;
+    const uint8_t *active;
+    uint8_t *code, *flags;
+    uint64_t *keys;
+    int64_t nb, nbp, pitch;       // nb = P * W slots, nbp = tiles * pitch
+    int width, shift;
+};
+
+// One lane = 4 consecutive beam slots (one dword per sticker row), all A children in registers: a child is a renaming of the
+// parent's registers (fixed_move).  Its codes come from its own look-ups (encode): the parent's shared family look-ups
+// (family_codes) would stay live across all A children and spill.
+template <class T>
+__global__ void __launch_bounds__(kWave) k_expand(ExpandArgs a) {
+    using K = Key<T>;
+    const int64_t g0 = (int64_t)blockIdx.x * kSpan;            // a wave never straddles a tile (pitch >= 512)
+    const uint32_t lo = threadIdx.x * 4;
+    const int64_t col = g0 & (a.pitch - 1), tile = g0 >> a.shift;
+    const uint32_t rs = (uint32_t)a.pitch;
+    Pk<1> s[T::S];
+    {
+        const __amdgpu_buffer_rsrc_t r = make_srd(a.beam + tile * T::S * a.pitch + col);
+#pragma unroll
+        for (int i = 0; i < T::S; ++i) s[i] = bld<1, kAuxCached>(r, lo, i * rs);
+    }
+    uint32_t live = 0;                                         // 0x01 in byte q: slot g0 + lo + q is live
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int64_t b = g0 + lo + q;
+        if (b < a.nb) {
+            const int64_t p = b / a.width, w = b - p * a.width;
+            if (a.active[p] && w < a.live[p]) live |= 1u << (8 * q);
+        }
+    }
+    const uint32_t last = *reinterpret_cast<const uint32_t *>(a.last_action + g0 + lo);
+    sfor<T::A>([&](auto ac) {
+        constexpr int A_ = decltype(ac)::value;
+        Pk<1> c[T::S];
+        fixed_move<T, 1, A_>(s, c);
+        const uint32_t solved = done_bytes(unsolved<T, 1>(c)).d[0];
+        Pk<1> x;
+        x.d[0] = last ^ ((uint32_t)(A_ ^ 1) * 0x01010101u);
+        const uint32_t undo = done_bytes(x).d[0];              // 0x01 where the slot was made by the inverse of A_
+        const int64_t j0 = (int64_t)A_ * a.nbp + g0;
+        *reinterpret_cast<uint32_t *>(a.flags + j0 + lo) = (live & ~undo) | (solved << 1);
+        Pk<1> cc[T::SLOTS];
+        encode<T, 1>(c, cc);                                   // the child's own look-ups: exact for any colouring
+        const __amdgpu_buffer_rsrc_t r = make_srd(a.code + ((int64_t)A_ * a.nbp + tile * a.pitch) * T::SLOTS + col);
+#pragma unroll
+        for (int p = 0; p < T::SLOTS; ++p) bst<1, kAuxCached>(r, lo, p * rs, cc[p]);
+        uint64_t *kp = a.keys + j0 + lo;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            uint64_t w[K::KW] = {};
+            sfor<K::N>([&](auto kc) {
+                constexpr int k = decltype(kc)::value;
+                w[k / 16] |= (uint64_t)((c[K::sticker(k)].d[0] >> (8 * q)) & 7u) << (3 * (k % 16));
+            });
+#pragma unroll
+            for (int k = 0; k < K::KW; ++k) kp[(int64_t)k * T::A * a.nbp + q] = w[k];
+        }
+    });
+}
+
+// ------------------------------------------------------------------------------------------ dedup + select
+struct SelectArgs {
+    uint8_t *flags;
+    const uint64_t *keys;
+    const float *scores;
+    const int32_t *live;
+    uint8_t *active;
+    int32_t *length, *solution;
+    const int32_t *depth;
+    uint16_t *sel_parent;
+    uint8_t *sel_action;
+    int32_t *sel_count;
+    unsigned long long *table;
+    uint64_t tmask;
+    int64_t nbp;
+    int width;
+};
+
+__device__ __forceinline__ uint64_t mix64(uint64_t z) {
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+
+template <class T>
+__device__ __forceinline__ int64_t cand_j(const SelectArgs &a, int64_t p, uint32_t c) {
+    return (int64_t)(c % T::A) * a.nbp + p * a.width + c / T::A;
+}
+
+template <class T>
+__device__ __forceinline__ void load_key(const SelectArgs &a, int64_t j, uint64_t (&k)[Key<T>::KW]) {
+#pragma unroll
+    for (int x = 0; x < Key<T>::KW; ++x) k[x] = a.keys[(int64_t)x * T::A * a.nbp + j];
+}
+
+template <class T>
+__device__ __forceinline__ uint64_t slot_of(const uint64_t (&k)[Key<T>::KW], int64_t p, uint64_t tmask) {
+    uint64_t h = mix64((uint64_t)p + 0x9E3779B97F4A7C15ull);
+#pragma unroll
+    for (int x = 0; x < Key<T>::KW; ++x) h = mix64(h ^ k[x]);
+    return h & tmask;
+}
+
+// the candidate `id` = (p << 32) | c holds the same key as (k, p)
+template <class T>
+__device__ __forceinline__ bool same_key(const SelectArgs &a, uint64_t id, const uint64_t (&k)[Key<T>::KW], int64_t p) {
+    if ((int64_t)(id >> 32) != p) return false;
+    uint64_t o[Key<T>::KW];
+    load_key<T>(a, cand_j<T>(a, p, (uint32_t)id), o);
+    bool eq = true;
+#pragma unroll
+    for (int x = 0; x < Key<T>::KW; ++x) eq = eq && o[x] == k[x];
+    return eq;
+}
+
+template <class T>
+__global__ void __launch_bounds__(256) k_insert(SelectArgs a) {
+    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (j >= T::A * a.nbp || !(a.flags[j] & RC_SEARCH_VALID)) return;        // valid implies a slot of a real problem
+    const int64_t ac = j / a.nbp, b = j - ac * a.nbp, p = b / a.width, w = b - p * a.width;
+    const unsigned long long id = ((uint64_t)p << 32) | (uint64_t)(w * T::A + ac);
+    uint64_t k[Key<T>::KW];
+    load_key<T>(a, j, k);
+    uint64_t h = slot_of<T>(k, p, a.tmask);
+    while (true) {                                             // the table has >= 2 slots per candidate: an empty one is reached
+        const unsigned long long old = atomicCAS(&a.table[h], (unsigned long long)kEmpty, id);
+        if (old == kEmpty) return;
+        if (same_key<T>(a, old, k, p)) {                       // a slot's key never changes once set: only equal ids compete
+            atomicMin(&a.table[h], id);
+            return;
+        }
+        h = (h + 1) & a.tmask;
+    }
+}
+
+// rank of a candidate: larger is better.  Score order with NaN lowest and -0 == +0 in the high word, then the lower c.
+__device__ __forceinline__ uint64_t rank_of(float v, uint32_t c) {
+    uint32_t u = __float_as_uint(v);
+    uint32_t o;
+    if (v != v) o = 0u;
+    else {
+        if (u == 0x80000000u) u = 0u;
+        o = (u & 0x80000000u) ? ~u : (u | 0x80000000u);      // never 0: ~u == 0 only for a NaN pattern
+    }
+    return ((uint64_t)o << 32) | (0xFFFFFFFFu - c);
+}
+
+__device__ __forceinline__ uint32_t block_min(uint32_t v, uint32_t *red) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = min(v, (uint32_t)__shfl_xor((int)v, o));
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    const uint32_t r = min(min(red[0], red[1]), min(red[2], red[3]));
+    __syncthreads();
+    return r;
+}
+__device__ __forceinline__ uint32_t block_sum(uint32_t v, uint32_t *red) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    const uint32_t r = red[0] + red[1] + red[2] + red[3];
+    __syncthreads();
+    return r;
+}
+
+// One workgroup per problem.  Every phase walks the candidates in c order with c = tid + 256 k, so a thread only ever re-reads
+// the survivor flags it wrote itself.
+template <class T>
+__global__ void __launch_bounds__(kSelThreads) k_select(SelectArgs a) {
+    __shared__ uint32_t red[4];
+    __shared__ uint32_t hist[256];
+    __shared__ uint64_t s_prefix, s_mask;
+    __shared__ uint32_t s_need, s_done;
+    const int64_t p = blockIdx.x;
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    if (!a.active[p]) {
+        if (tid == 0) a.sel_count[p] = 0;
+        return;
+    }
+    const uint32_t W = (uint32_t)a.width;
+    const uint32_t M = (uint32_t)min(max(a.live[p], 0), a.width) * T::A;
+    // 1. solved check: the lowest valid solved candidate
+    uint32_t best = ~0u;
+    for (uint32_t c = tid; c < M; c += kSelThreads) {
+        const uint8_t f = a.flags[cand_j<T>(a, p, c)];
+        if ((f & RC_SEARCH_VALID) && (f & RC_SEARCH_SOLVED)) { best = c; break; }   // c grows: the thread's first is its lowest
+    }
+    best = block_min(best, red);
+    if (best != ~0u) {
+        if (tid == 0) {
+            a.length[p] = *a.depth;
+            a.solution[p] = (int32_t)best;
+            a.active[p] = 0;
+            a.sel_count[p] = 0;
+        }
+        return;
+    }
+    // 2. survivors: the candidate that owns its key's table slot
+    uint32_t cnt = 0;
+    for (uint32_t c = tid; c < M; c += kSelThreads) {
+        const int64_t j = cand_j<T>(a, p, c);
+        const uint8_t f = a.flags[j];
+        if (!(f & RC_SEARCH_VALID)) continue;
+        uint64_t k[Key<T>::KW];
+        load_key<T>(a, j, k);
+        const uint64_t id = ((uint64_t)p << 32) | c;
+        uint64_t h = slot_of<T>(k, p, a.tmask);
+        while (true) {
+            const uint64_t v = a.table[h];
+            if (v == kEmpty) break;                            // cannot happen: every valid candidate was inserted
+            if (same_key<T>(a, v, k, p)) {
+                if (v == id) {
+                    a.flags[j] = f | RC_SEARCH_SURVIVOR;
+                    ++cnt;
+                }
+                break;
+            }
+            h = (h + 1) & a.tmask;
+        }
+    }
+    const uint32_t nsurv = block_sum(cnt, red);
+    // 3. the W-th best rank among the survivors (MSB-first radix select, 8 bits per pass; ranks are distinct)
+    uint64_t thr = 0;
+    if (nsurv > W) {
+        if (tid == 0) { s_prefix = 0; s_mask = 0; s_need = W; s_done = 0; }
+        for (int shift = 56; shift >= 0; shift -= 8) {
+            hist[tid] = 0;
+            __syncthreads();
+            const uint64_t prefix = s_prefix, mask = s_mask;
+            for (uint32_t c = tid; c < M; c += kSelThreads) {
+                const int64_t j = cand_j<T>(a, p, c);
+                if (!(a.flags[j] & RC_SEARCH_SURVIVOR)) continue;
+                const uint64_t r = rank_of(a.scores[j], c);
+                if ((r & mask) == prefix) atomicAdd(&hist[(r >> shift) & 255u], 1u);
+            }
+            __syncthreads();
+            if (tid == 0) {
+                const uint32_t need = s_need;
+                uint32_t cum = 0;
+                int bin = 255;
+                for (; bin > 0 && cum + hist[bin] < need; --bin) cum += hist[bin];
+                s_prefix = prefix | ((uint64_t)bin << shift);
+                s_mask = mask | (255ull << shift);
+                s_need = need - cum;
+                s_done = hist[bin] == need - cum;              // the whole bin is kept: ranks >= the prefix are exactly the W best
+            }
+            __syncthreads();
+            if (s_done) break;
+        }
+        thr = s_prefix;
+    }
+    // 4. the kept candidates in ascending c
+    uint32_t base = 0;
+    for (uint32_t c0 = 0; c0 < M; c0 += kSelThreads) {
+        const uint32_t c = c0 + tid;
+        bool keep = false;
+        if (c < M) {
+            const int64_t j = cand_j<T>(a, p, c);
+            keep = (a.flags[j] & RC_SEARCH_SURVIVOR) && (nsurv <= W || rank_of(a.scores[j], c) >= thr);
+        }
+        const unsigned long long bal = __ballot(keep);
+        if (lane == 0) red[wv] = (uint32_t)__popcll(bal);
+        __syncthreads();
+        uint32_t off = base;
+        for (int q = 0; q < wv; ++q) off += red[q];
+        const uint32_t tot = red[0] + red[1] + red[2] + red[3];
+        if (keep) {
+            const uint32_t slot = off + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
+            if (slot < W) {
+                a.sel_parent[p * a.width + slot] = (uint16_t)(c / T::A);
+                a.sel_action[p * a.width + slot] = (uint8_t)(c % T::A);
+            }
+        }
+        base += tot;
+        __syncthreads();
+    }
+    if (tid == 0) a.sel_count[p] = (int32_t)min(base, W);
+}
+
+// ----------------------------------------------------------------------------------------------- advance
+struct AdvanceArgs {
+    const uint8_t *in;
+    uint8_t *out;
+    const uint16_t *sel_parent;
+    const uint8_t *sel_action;
+    const int32_t *sel_count;
+    int32_t *live;
+    uint8_t *last_action;
+    uint16_t *hist_parent;
+    uint8_t *hist_action;
+    const int32_t *depth;
+    int64_t nb, nbp, pitch;
+    int width, shift, max_depth;
+};
+
+// One lane = 4 consecutive new slots: their parents' stickers gathered byte by byte, then ONE packed move with per-byte actions.
+template <class T>
+__global__ void __launch_bounds__(kWave) k_advance(AdvanceArgs a) {
+    const int64_t g0 = (int64_t)blockIdx.x * kSpan;
+    const uint32_t lo = threadIdx.x * 4;
+    const int t = *a.depth;
+    const bool record = t >= 1 && t <= a.max_depth;
+    uint32_t act = 0;
+    int64_t src[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int64_t n = g0 + lo + q;
+        uint32_t aq = T::A, wq = 0;
+        src[q] = n;                                            // dead slots copy themselves under the no-op
+        if (n < a.nb) {
+            const int64_t p = n / a.width, i = n - p * a.width;
+            const int32_t cnt = a.sel_count[p];
+            if (i < cnt) {
+                wq = min((uint32_t)a.sel_parent[n], (uint32_t)a.width - 1u);
+                aq = min((uint32_t)a.sel_action[n], (uint32_t)T::A);
+                src[q] = p * a.width + wq;
+            }
+            if (i == 0) a.live[p] = cnt;
+        }
+        act |= aq << (8 * q);
+        a.last_action[n] = (uint8_t)aq;
+        if (record) {
+            a.hist_parent[(int64_t)(t - 1) * a.nbp + n] = (uint16_t)wq;
+            a.hist_action[(int64_t)(t - 1) * a.nbp + n] = (uint8_t)aq;
+        }
+    }
+    Pk<1> s[T::S];
+#pragma unroll
+    for (int i = 0; i < T::S; ++i) {
+        uint32_t v = 0;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) v |= (uint32_t)a.in[tiled(src[q], a.pitch, a.shift, T::S) + (int64_t)i * a.pitch] << (8 * q);
+        s[i].d[0] = v;
+    }
+    Pk<1> m[T::A];
+    Pk<1> ap;
+    ap.d[0] = act;
+    (void)action_masks<T, 1>(ap, m);                           // actions are 0..A by construction
+    Pk<1> o[T::S];
+    apply_move<T, 1>(s, m, o);
+    const __amdgpu_buffer_rsrc_t r = make_srd(a.out + tiled(g0, a.pitch, a.shift, T::S));
+#pragma unroll
+    for (int i = 0; i < T::S; ++i) bst<1, kAuxCached>(r, lo, i * (uint32_t)a.pitch, o[i]);
+}
+
+// --------------------------------------------------------------------------------------------- backtrack
+__global__ void __launch_bounds__(256) k_backtrack(const uint16_t *hp, const uint8_t *ha, int64_t n, int width, int64_t nbp, int A,
+                                                   int D, const int32_t *length, const int32_t *solution, uint8_t *actions) {
+    const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (p >= n) return;
+    for (int d = 0; d < D; ++d) actions[(int64_t)d * n + p] = (uint8_t)A;
+    const int L = length[p];
+    const int32_t c = solution[p];
+    if (L < 1 || L > D || c < 0 || c >= width * A) return;
+    int64_t w = c / A;
+    actions[(int64_t)(L - 1) * n + p] = (uint8_t)(c % A);
+    for (int t = L - 1; t >= 1; --t) {                         // slot w of the beam after depth t came from history row t - 1
+        const int64_t idx = (int64_t)(t - 1) * nbp + p * width + w;
+        actions[(int64_t)(t - 1) * n + p] = ha[idx];
+        w = hp[idx];
+        if (w >= width) return;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------- host side
+thread_local char t_err[256] = "";
+
+int fail(const char *msg) {
+    snprintf(t_err, sizeof t_err, "%s", msg);
+    return -1;
+}
+#define RCS_HIP(call)                                                                               \
+    do {                                                                                            \
+        const hipError_t e_ = (call);                                                               \
+        if (e_ != hipSuccess) {                                                                     \
+            snprintf(t_err, sizeof t_err, "%s: %s", #call, hipGetErrorString(e_));                   \
+            return -2;                                                                              \
+        }                                                                                           \
+    } while (0)
+
+inline hipStream_t S(void *s) { return static_cast<hipStream_t>(s); }
+inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+inline int log2_exact(int64_t v) {
+    int s = 0;
+    while (((int64_t)1 << s) < v) ++s;
+    return s;
+}
+
+template <class F>
+int by_size(int cube_size, F &&f) {
+    if (cube_size == 3) return f(Cube3{});
+    if (cube_size == 2) return f(Cube2{});
+    return fail("cube_size must be 2 or 3");
+}
+
+struct Geo {
+    int64_t nb, nbp;
+    int shift;
+};
+// beam tiling of P problems x W slots at `pitch` (include/rubiksearch.h "Conventions")
+template <class T>
+int geometry(int64_t n_problems, int width, int64_t pitch, Geo &g) {
+    if (n_problems < 1 || width < 1 || width > 65536) return fail("need n_problems >= 1 and 1 <= width <= 65536");
+    if (pitch < 512 || (pitch & (pitch - 1)) != 0 || pitch * T::S >= ((int64_t)1 << 32)) return fail("pitch must be a power of two >= 512 with S * pitch < 2^32");
+    g.nb = n_problems * width;
+    g.nbp = (g.nb + pitch - 1) / pitch * pitch;
+    g.shift = log2_exact(pitch);
+    if ((int64_t)T::A * g.nbp / 256 > 0x7fffffff) return fail("too many candidates for one launch");
+    return 0;
+}
+
+int64_t table_slots(int A, int64_t n_problems, int width) {
+    const int64_t need = 2 * (int64_t)A * n_problems * width;
+    int64_t s = 1024;
+    while (s < need) s <<= 1;
+    return s;
+}
+
+}  // namespace
+
+// the hash of the sources this binary was compiled from (__graft_entry__.build passes -DRC_SRC_HASH=<16 hex digits>)
+#ifndef RC_SRC_HASH
+#define RC_SRC_HASH unhashed
+#endif
+#define RCS_STR2(x) #x
+#define RCS_STR(x) RCS_STR2(x)
+static const char k_build_id[] = "rc-build-id:" RCS_STR(RC_SRC_HASH);
+const char *rc_search_build_id(void) { return k_build_id + 12; }
+
+const char *rc_search_last_error(void) { return t_err; }
+
+int64_t rc_search_workspace_bytes(int cube_size, int64_t n_problems, int width) {
+    if ((cube_size != 2 && cube_size != 3) || n_problems < 1 || width < 1 || width > 65536) return -1;
+    return table_slots(cube_size == 3 ? 12 : 6, n_problems, width) * 8;
+}
+
+int rc_search_init(const uint8_t *roots, int64_t n, int64_t root_pitch, int cube_size, int width, uint8_t *beam, int64_t pitch,
+                   uint8_t *last_action, int32_t *live, uint8_t *active, int32_t *length, int32_t *solution, void *stream) {
+    return by_size(cube_size, [&](auto t) {
+        using T = decltype(t);
+        Geo g;
+        if (int rc = geometry<T>(n, width, pitch, g)) return rc;
+        if (!roots || !beam || !last_action || !live || !active || !length || !solution) return fail("rc_search_init: null buffer");
+        int rshift = 63;                                       // roots: one tile (pitch >= n, pitch % 16 == 0) or power-of-two tiles
+        if (root_pitch <= 0 || (root_pitch & 15) != 0 || root_pitch * T::S >= ((int64_t)1 << 32)) return fail("rc_search_init: bad root_pitch");
+        if (n > root_pitch) {
+            if (root_pitch < 512 || (root_pitch & (root_pitch - 1)) != 0) return fail("rc_search_init: several root tiles need a power-of-two pitch >= 512");
+            rshift = log2_exact(root_pitch);
+        }
+        hipLaunchKernelGGL((k_init<T>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, S(stream), roots, n, root_pitch, rshift, beam, pitch,
+                           g.shift, width, last_action, live, active, length, solution);
+        RCS_HIP(hipGetLastError());
+        return 0;
+    });
+}
+
+int rc_search_expand(const uint8_t *beam, int64_t n, int width, int64_t pitch, int cube_size, const uint8_t *last_action,
+                     const int32_t *live, const uint8_t *active, uint8_t *code, uint8_t *flags, uint64_t *keys, void *stream) {
+    return by_size(cube_size, [&](auto t) {
+        using T = decltype(t);
+        Geo g;
+        if (int rc = geometry<T>(n, width, pitch, g)) return rc;
+        if (!beam || !last_action || !live || !active || !code || !flags || !keys) return fail("rc_search_expand: null buffer");
+        if (!aligned16(beam) || !aligned16(last_action) || !aligned16(code) || !aligned16(flags) || !aligned16(keys))
+            return fail("rc_search_expand: buffers must be 16-byte aligned");
+        const ExpandArgs a{beam, last_action, live, active, code, flags, keys, g.nb, g.nbp, pitch, width, g.shift};
+        hipLaunchKernelGGL((k_expand<T>), dim3((unsigned)(g.nbp / kSpan)), dim3(kWave), 0, S(stream), a);
+        RCS_HIP(hipGetLastError());
+        return 0;
+    });
+}
+
+int rc_search_select(uint8_t *flags, const uint64_t *keys, const float *scores, int64_t n, int width, int64_t pitch, int cube_size,
+                     const int32_t *live, uint8_t *active, int32_t *length, int32_t *solution, const int32_t *depth, uint16_t *sel_parent,
+                     uint8_t *sel_action, int32_t *sel_count, void *workspace, int64_t workspace_bytes, void *stream) {
+    return by_size(cube_size, [&](auto t) {
+        using T = decltype(t);
+        Geo g;
+        if (int rc = geometry<T>(n, width, pitch, g)) return rc;
+        if (!flags || !keys || !scores || !live || !active || !length || !solution || !depth || !sel_parent || !sel_action || !sel_count || !workspace)
+            return fail("rc_search_select: null buffer");
+        if (!aligned16(workspace)) return fail("rc_search_select: workspace must be 16-byte aligned");
+        const int64_t slots = table_slots(T::A, n, width);
+        if (workspace_bytes < slots * 8) return fail("rc_search_select: workspace smaller than rc_search_workspace_bytes()");
+        if (n > 0x7fffffff) return fail("rc_search_select: too many problems for one launch");
+        const SelectArgs a{flags, keys, scores, live, active, length, solution, depth, sel_parent, sel_action, sel_count,
+                           static_cast<unsigned long long *>(workspace), (uint64_t)(slots - 1), g.nbp, width};
+        RCS_HIP(hipMemsetAsync(workspace, 0xFF, (size_t)slots * 8, S(stream)));       // every slot kEmpty
+        hipLaunchKernelGGL((k_insert<T>), dim3((unsigned)((T::A * g.nbp + 255) / 256)), dim3(256), 0, S(stream), a);
+        RCS_HIP(hipGetLastError());
+        hipLaunchKernelGGL((k_select<T>), dim3((unsigned)n), dim3(kSelThreads), 0, S(stream), a);
+        RCS_HIP(hipGetLastError());
+        return 0;
+    });
+}
+
+int rc_search_advance(const uint8_t *beam_in, uint8_t *beam_out, int64_t n, int width, int64_t pitch, int cube_size, const uint16_t *sel_parent,
+                      const uint8_t *sel_action, const int32_t *sel_count, int32_t *live, uint8_t *last_action, uint16_t *hist_parent,
+                      uint8_t *hist_action, const int32_t *depth, int max_depth, void *stream) {
+    return by_size(cube_size, [&](auto t) {
+        using T = decltype(t);
+        Geo g;
+        if (int rc = geometry<T>(n, width, pitch, g)) return rc;
+        if (!beam_in || !beam_out || !sel_parent || !sel_action || !sel_count || !live || !last_action || !hist_parent || !hist_action || !depth)
+            return fail("rc_search_advance: null buffer");
+        if (max_depth < 1) return fail("rc_search_advance: max_depth must be >= 1");
+        if (!aligned16(beam_out)) return fail("rc_search_advance: beam_out must be 16-byte aligned");
+        const int64_t bytes = g.nbp * T::S;
+        if (beam_in < beam_out + bytes && beam_out < beam_in + bytes) return fail("rc_search_advance: beam_in and beam_out overlap");
+        const AdvanceArgs a{beam_in, beam_out, sel_parent, sel_action, sel_count, live, last_action, hist_parent, hist_action, depth,
+                            g.nb, g.nbp, pitch, width, g.shift, max_depth};
+        hipLaunchKernelGGL((k_advance<T>), dim3((unsigned)(g.nbp / kSpan)), dim3(kWave), 0, S(stream), a);
+        RCS_HIP(hipGetLastError());
+        return 0;
+    });
+}
+
+int rc_search_backtrack(const uint16_t *hist_parent, const uint8_t *hist_action, int64_t n, int width, int64_t pitch, int cube_size,
+                        int max_depth, const int32_t *length, const int32_t *solution, uint8_t *actions, void *stream) {
+    return by_size(cube_size, [&](auto t) {
+        using T = decltype(t);
+        Geo g;
+        if (int rc = geometry<T>(n, width, pitch, g)) return rc;
+        if (!hist_parent || !hist_action || !length || !solution || !actions) return fail("rc_search_backtrack: null buffer");
+        if (max_depth < 1) return fail("rc_search_backtrack: max_depth must be >= 1");
+        hipLaunchKernelGGL(k_backtrack, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, S(stream), hist_parent, hist_action, n, width, g.nbp,
+                           T::A, max_depth, length, solution, actions);
+        RCS_HIP(hipGetLastError());
+        return 0;
+    });
+}

@@ -1,0 +1,174 @@
+"""Batched beam search guided by the value head (DeepCubeA-style; DESIGN.md "Beam search"): the solver behind the solve rates
+test.py and train.py:167-198 report, for thousands of cubes at once.
+
+One depth step, all on the device and without a host synchronisation:
+  rc_search_expand     all A children of every beam slot: compact codes, valid / solved flags, exact sticker keys
+  rc_onehot_from_code  + ONE forward of the caller's net per chunk of candidates (dense_budget_bytes), scores = model(x)[0][:, 0]
+  rc_search_select     solved check, exact removal of duplicate states, the W best per cube (score desc, candidate index asc)
+  rc_search_advance    the kept children become the next beam (ping-pong buffers) + one history row
+The solutions are read back from the history by rc_search_backtrack at the end.
+"""
+from __future__ import annotations
+
+import torch
+
+from . import _lib, _search_lib, ops
+from ._lib import ptr, stream_ptr
+from ._search_lib import check
+from .tables import get_env_config
+
+MAX_WIDTH = 65536
+KEY_WORDS = {3: 3, 2: 2}
+
+
+def beam_pitch(n_slots):
+    """Tile pitch of the beam and candidate buffers: a power of two >= 512 (the A candidate blocks then form ONE tiled code buffer)
+    and at most ops.DEFAULT_TILE."""
+    p = ops.MIN_TILE
+    while p < n_slots and p < ops.DEFAULT_TILE:
+        p *= 2
+    return p
+
+
+class BeamPlan:
+    """Device buffers of one search shape (P problems, width W, max_depth D) and the launches of one depth step.
+    Layouts: include/rubiksearch.h.  The methods wrap one entry point each; tests drive them one by one."""
+
+    def __init__(self, n_problems, cube_size, width, max_depth, device, dtype=torch.float32, dense_budget_bytes=1 << 30):
+        if not 1 <= int(width) <= MAX_WIDTH:
+            raise ValueError(f"width must be in 1..{MAX_WIDTH}")
+        if int(max_depth) < 0 or int(n_problems) < 1:
+            raise ValueError("need n_problems >= 1 and max_depth >= 0")
+        self.P, self.W, self.D, self.cs = int(n_problems), int(width), int(max_depth), int(cube_size)
+        S, A, SL = ops._size(cube_size)
+        self.S, self.A, self.SL = S, A, SL
+        self.dev = dev = torch.device(device)
+        (self.R, self.C), _ = get_env_config(cube_size)
+        self.pitch = beam_pitch(self.P * self.W)
+        self.tiles = -(-self.P * self.W // self.pitch)
+        self.nbp = nbp = self.tiles * self.pitch
+        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)
+        self.beams = [z((self.tiles, S, self.pitch), torch.uint8) for _ in range(2)]
+        self.last_action = z(nbp, torch.uint8)
+        self.live, self.active = z(self.P, torch.int32), z(self.P, torch.uint8)
+        self.length, self.solution = z(self.P, torch.int32), z(self.P, torch.int32)
+        self.code = z((A * self.tiles, SL, self.pitch), torch.uint8)
+        self.flags = z((A, nbp), torch.uint8)
+        self.keys = z((KEY_WORDS[cube_size], A, nbp), torch.int64)           # uint64 words
+        self.scores = z((A, nbp), torch.float32)
+        self.sel_parent, self.sel_action = z(nbp, torch.int16), z(nbp, torch.uint8)   # uint16 slots
+        self.sel_count = z(self.P, torch.int32)
+        self.hist_parent, self.hist_action = z((max(self.D, 1), nbp), torch.int16), z((max(self.D, 1), nbp), torch.uint8)
+        self.actions = z((max(self.D, 1), self.P), torch.uint8)
+        self.depth = z(1, torch.int32)
+        L = _search_lib.search_lib()
+        self.workspace = torch.empty(int(L.rc_search_workspace_bytes(self.cs, self.P, self.W)), dtype=torch.uint8, device=dev)
+        self.dtype = dtype
+        row_bytes = self.R * self.C * torch.empty((), dtype=dtype).element_size()
+        total = A * nbp
+        self.chunk = min(total, max(self.pitch, int(dense_budget_bytes) // row_bytes // self.pitch * self.pitch))
+        self.dense = torch.empty((self.chunk, self.R, self.C), dtype=dtype, device=dev)
+
+    # ------------------------------------------------------------------ one entry point each
+    def init(self, roots, root_pitch):
+        _lib.init(self.dev)
+        check(_search_lib.search_lib().rc_search_init(ptr(roots), self.P, root_pitch, self.cs, self.W, ptr(self.beams[0]), self.pitch,
+                                                      ptr(self.last_action), ptr(self.live), ptr(self.active), ptr(self.length),
+                                                      ptr(self.solution), stream_ptr(self.dev)))
+        self.depth.fill_(1)
+
+    def expand(self, parity):
+        check(_search_lib.search_lib().rc_search_expand(ptr(self.beams[parity]), self.P, self.W, self.pitch, self.cs, ptr(self.last_action),
+                                                        ptr(self.live), ptr(self.active), ptr(self.code), ptr(self.flags), ptr(self.keys),
+                                                        stream_ptr(self.dev)))
+
+    def score(self, model):
+        """scores = model(dense one-hot)[0][:, 0] for every candidate, one forward per chunk (chunks start on tile boundaries)."""
+        total, flat = self.A * self.nbp, self.scores.view(-1)
+        for j0 in range(0, total, self.chunk):
+            m = min(self.chunk, total - j0)
+            t0 = j0 // self.pitch
+            ops.onehot_from_code(self.code[t0:t0 + m // self.pitch], m, self.cs, self.dense[:m])
+            flat[j0:j0 + m].copy_(model(self.dense[:m])[0][:, 0])
+
+    def select(self):
+        check(_search_lib.search_lib().rc_search_select(ptr(self.flags), ptr(self.keys), ptr(self.scores), self.P, self.W, self.pitch, self.cs,
+                                                        ptr(self.live), ptr(self.active), ptr(self.length), ptr(self.solution), ptr(self.depth),
+                                                        ptr(self.sel_parent), ptr(self.sel_action), ptr(self.sel_count), ptr(self.workspace),
+                                                        self.workspace.numel(), stream_ptr(self.dev)))
+
+    def advance(self, parity):
+        check(_search_lib.search_lib().rc_search_advance(ptr(self.beams[parity]), ptr(self.beams[1 - parity]), self.P, self.W, self.pitch,
+                                                         self.cs, ptr(self.sel_parent), ptr(self.sel_action), ptr(self.sel_count), ptr(self.live),
+                                                         ptr(self.last_action), ptr(self.hist_parent), ptr(self.hist_action), ptr(self.depth),
+                                                         max(self.D, 1), stream_ptr(self.dev)))
+
+    def backtrack(self):
+        check(_search_lib.search_lib().rc_search_backtrack(ptr(self.hist_parent), ptr(self.hist_action), self.P, self.W, self.pitch, self.cs,
+                                                           max(self.D, 1), ptr(self.length), ptr(self.solution), ptr(self.actions),
+                                                           stream_ptr(self.dev)))
+
+    def step(self, model, parity):
+        """One depth: beam `parity` -> beam 1 - parity.  Stream-ordered, no host synchronisation (capturable as a linear hipGraph)."""
+        self.expand(parity)
+        self.score(model)
+        self.select()
+        self.advance(parity)
+        self.depth.add_(1)
+
+
+@torch.no_grad()
+def beam_search(model, env, width, max_depth, *, dense_budget_bytes=1 << 30, sync_every=4, graph=False):
+    """Beam search from every cube of `env` (a VecCubeEnv, any observation mode; its state is left unchanged).
+
+    Each depth expands the beam, scores the children with the value head model(onehot)[0][:, 0] in the model's dtype, and keeps the
+    `width` best distinct children per cube (ties: the lower candidate index c = slot * A + action); a cube is solved at the first
+    depth where a child is solved.  "All cubes done" is checked on the host every `sync_every` depths.  graph=True replays one
+    depth step as a hipGraph (two captures: the two directions of the beam ping-pong); the results equal the eager run's.
+
+    Returns dict(solved bool [P], length int32 [P] (0: the root was solved, -1: not solved within max_depth), actions uint8
+    [max_depth, P]: the solution's moves, then the no-op action_dim)."""
+    from .adi import _module_dtype
+    P, cs = env.num_envs, env.cube_size
+    dtype = _module_dtype(model)
+    plan = BeamPlan(P, cs, width, max_depth, env.device, dtype, dense_budget_bytes)
+    plan.init(env.stickers, env.stickers.shape[-1])
+    graphs = {}
+    for t in range(1, plan.D + 1):
+        parity = (t - 1) & 1
+        if not graph:
+            plan.step(model, parity)
+        elif t == 1:                                           # warm-up outside capture (libraries pick their kernels here)
+            s = torch.cuda.Stream(plan.dev)
+            s.wait_stream(torch.cuda.current_stream(plan.dev))
+            with torch.cuda.stream(s):
+                plan.step(model, parity)
+            torch.cuda.current_stream(plan.dev).wait_stream(s)
+        else:
+            if parity not in graphs:
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g):                      # capture does not execute
+                    plan.step(model, parity)
+                graphs[parity] = g
+            graphs[parity].replay()
+        if t % sync_every == 0 and not bool(plan.active.any()):
+            break
+    if plan.D:
+        plan.backtrack()
+    actions = plan.actions[:plan.D]
+    return {"solved": plan.length >= 0, "length": plan.length, "actions": actions}
+
+
+@torch.no_grad()
+def beam_solve_percentage(model, cube_size, sample_scramble_count, sample_cube_count, width, max_depth, device="cuda", seeds=None,
+                          graph=False):
+    """rollout.solve_percentage with the beam search as the solver: for scramble_count = 1..sample_scramble_count, the percentage
+    of the sample_cube_count cubes (seeds i * 10, train.py:180) solved within max_depth.  All (k, seed) pairs run as ONE batch."""
+    from .vec_env import VecCubeEnv
+    seeds = list(seeds) if seeds is not None else [i * 10 for i in range(sample_cube_count)]
+    ks = [k for k in range(1, sample_scramble_count + 1) for _ in seeds]
+    env = VecCubeEnv(len(ks), device, cube_size, obs=None)
+    env.reset(seeds=seeds * sample_scramble_count, scramble_count=ks)
+    res = beam_search(model, env, width, max_depth, graph=graph)
+    solved = res["solved"].view(sample_scramble_count, len(seeds)).float().mean(1) * 100.0
+    return [float(x) for x in solved.cpu()]

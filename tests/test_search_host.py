@@ -1,0 +1,97 @@
+"""The beam search without a GPU: librubiksearch.so's ABI and build id, and the numpy restatement (tests/beam_ref.py) against a BFS
+and against the shipped 2x2x2 checkpoint's value head."""
+import os
+import re
+import subprocess
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import beam_ref  # noqa: E402
+
+
+def test_search_abi_exports_every_declared_symbol():
+    from rubiks_cube_solver_amd import _build, _search_lib
+    L = _search_lib.search_lib()                                      # loads without a GPU
+    header = open(os.path.join(ROOT, "include", "rubiksearch.h")).read()
+    declared = set(re.findall(r"^(?:int|int64_t|const char \*)\s*(rc_search_\w+)\(", header, re.M))
+    assert declared == {"rc_search_build_id", "rc_search_last_error", "rc_search_workspace_bytes", "rc_search_init", "rc_search_expand",
+                        "rc_search_select", "rc_search_advance", "rc_search_backtrack"}
+    nm = subprocess.run(["nm", "-D", "--defined-only", _search_lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
+    exported = {l.split()[-1] for l in nm.splitlines() if " T " in l}
+    assert {e for e in exported if e.startswith("rc_")} == declared, exported ^ declared
+    assert _search_lib.build_id() == _build.source_hash(_build.SEARCH_SOURCES) == _build.embedded_id(_search_lib.LIB_PATH)
+    # the workspace query is host only: a power of two of 8-byte slots, at least 2 * A * P * W of them
+    assert L.rc_search_workspace_bytes(3, 1000, 1024) == 8 * (1 << 25) and L.rc_search_workspace_bytes(2, 10, 16) == 8 * 2048
+    assert L.rc_search_workspace_bytes(4, 10, 16) == -1 and L.rc_search_workspace_bytes(3, 10, 65537) == -1
+
+
+def test_stale_search_library_is_refused(tmp_path):
+    from rubiks_cube_solver_amd import _build, _search_lib
+    fake = str(tmp_path / "librubiksearch.so")
+    data = bytearray(open(_search_lib.LIB_PATH, "rb").read())
+    i = data.find(_build.MARKER) + len(_build.MARKER)
+    data[i] = ord("0") if data[i] != ord("0") else ord("1")
+    open(fake, "wb").write(bytes(data))
+    code = "from rubiks_cube_solver_amd import _search_lib; _search_lib.search_lib(); print('loaded')"
+    env = dict(os.environ, RUBIKSEARCH_LIB=fake)
+    env.pop("RC_ALLOW_STALE", None)
+    out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300, cwd=ROOT, env=env)
+    assert out.returncode != 0 and "is stale" in out.stderr and "loaded" not in out.stdout, out.stderr[-2000:]
+    out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300, cwd=ROOT,
+                         env=dict(env, RUBIKSEARCH_LIB=str(tmp_path / "missing.so")))
+    assert out.returncode != 0 and "not found" in out.stderr
+
+
+def test_restated_moves_match_the_oracle(oracle):
+    """beam_ref's vectorised moves / codes / one-hots are the oracle's."""
+    rng = np.random.default_rng(1)
+    for cs in (3, 2):
+        cube = beam_ref.Cube(cs)
+        st = cube.scramble(rng.integers(0, cube.A, (50, 12)))
+        a = rng.integers(0, cube.A, 50)
+        e_st, e_code, e_done, _ = oracle.step(cs, st, a.astype(np.uint8))
+        ch = cube.move(st, a)
+        assert (ch == e_st).all() and (cube.codes(ch) == e_code).all() and (cube.is_solved(ch) == e_done.astype(bool)).all()
+        assert (cube.onehot(ch).astype(np.uint8) == oracle.encode(cs, ch)[1]).all()
+
+
+def test_bfs_counts_and_exhaustive_width_is_optimal():
+    """Published quarter-turn counts per distance, and with W above every candidate set the restatement's length IS the distance."""
+    for cs, depth, counts, kmax, width in ((3, 4, [1, 12, 114, 1068, 10011], 4, 16384), (2, 6, [1, 6, 27, 120, 534, 2256, 8969], 5, 4096)):
+        cube = beam_ref.Cube(cs)
+        dist, got = beam_ref.bfs_distances(cube, depth)
+        assert got == counts
+        rng = np.random.default_rng(cs)
+        scr = np.concatenate([cube.scramble(rng.integers(0, cube.A, (4, k))) for k in range(1, kmax + 1)])
+        w = beam_ref.stub_weights(cs)
+        res = beam_ref.beam_search(cube, scr, width, kmax + 1, lambda x: x.reshape(len(x), -1) @ w)
+        want = np.array([dist[s.tobytes()] for s in scr])
+        assert (res["length"] == want).all(), (res["length"], want)
+        assert replay_solves(cube, scr, res["actions"], res["length"])
+
+
+def replay_solves(cube, roots, actions, length):
+    st = roots.copy()
+    for d in range(actions.shape[0]):
+        a = actions[d].astype(np.intp)
+        live = a < cube.A
+        st[live] = cube.move(st[live], a[live])
+    ok = cube.is_solved(st)
+    return bool(ok[length >= 0].all()) and bool((actions[:, length < 0] == cube.A).all())
+
+
+def test_restated_search_with_the_checkpoint_solves_every_fixture_scramble():
+    """The shipped 2x2x2 checkpoint's value head at W = 16 solves all 160 fixture scrambles of depths 8, 10, 12, 14 (greedy: 60 % at 14)."""
+    g = np.load(os.path.join(ROOT, "tests", "golden", "crosscheck_222.npz"))
+    with np.load(os.path.join(ROOT, "tests", "golden", "crosscheck_222_weights.npz")) as z:
+        sd = {k: z[k] for k in z.files}
+    pick = np.isin(g["ks"], (8, 10, 12, 14))
+    assert pick.sum() == 160
+    cube = beam_ref.Cube(2)
+    roots = cube.scramble(g["scramble"][pick])
+    res = beam_ref.beam_search(cube, roots, 16, 30, lambda x: beam_ref.value_head(sd, x))
+    assert res["solved"].all() and (res["length"] <= g["ks"][pick]).all()
+    assert replay_solves(cube, roots, res["actions"], res["length"])
