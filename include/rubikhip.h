@@ -287,6 +287,12 @@ int rc_onehot_from_family(const uint8_t *family, int64_t n_cubes, int64_t pitch,
 int rc_onehot_from_family_depths(const uint8_t *family, int64_t n_cubes, int64_t pitch, int cube_size, void *onehot,
                                  int fmt, int64_t block_stride, int n_depths, void *stream);
 
+/* ADI targets of one depth (cube_env.py:229-232,239-251).  child_value / child_solved [A][pitch], walk w < n:
+ *   a solved child exists  target_value = 1.0f, target_policy = the lowest solved index (whatever the values are, NaN included);
+ *   otherwise              torch.max(child_value + (-1.0f)) over the A children, with torch.max's order: the FIRST maximal index
+ *                          (-0 == +0, so a tie of zeros keeps the lower index; the first +inf wins), and NaN propagates -- if any
+ *                          child value is NaN the target is NaN and target_policy is the index of the FIRST NaN;
+ *   error (optional)       fabs((double)parent_value[w] - (double)target_value) * weight[w], NaN when either side is. */
 int rc_adi_targets(const float *child_value, const uint8_t *child_solved, const float *parent_value,
                    const double *weight, int64_t n, int64_t pitch, int cube_size,
                    float *target_value, int32_t *target_policy, double *error, void *stream);

@@ -977,7 +977,7 @@ __global__ void __launch_bounds__(256) k_adi_targets(TargetArgs t) {
     for (int k = 0; k < A_; ++k) {
         const float v = cv[k * t.cv_child] + (-1.0f);                    // cube_env.py:244  value + reward
         if (cs[k * t.cs_child] && solved_at < 0) solved_at = k;          // cube_env.py:229-232  first solved child wins
-        if (arg < 0 || v > best) { best = v; arg = k; }                  // torch.max: first maximal index
+        if (arg < 0 || (v != v ? best == best : v > best)) { best = v; arg = k; }   // torch.max: first maximal index; the first NaN wins and stays
     }
     const float tv = solved_at >= 0 ? 1.0f : best;
     const int64_t o = i * t.out_stride + g;

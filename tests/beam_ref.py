@@ -101,45 +101,123 @@ def select_problem(valid, solved, keys, scores, width):
     return "kept", kept, surv
 
 
-def beam_search(cube, roots, width, max_depth, score_fn):
-    """roots [P, S] -> dict(solved [P], length [P], actions [max_depth, P]).  score_fn(onehot float32 [m, R, C]) -> float32 [m]."""
-    P, A = len(roots), cube.A
-    length = np.where(cube.is_solved(roots), 0, -1).astype(np.int32)
-    actions = np.full((max(max_depth, 0), P), A, np.uint8)
-    beams = [roots[p:p + 1].copy() for p in range(P)]
-    last = [np.array([A]) for _ in range(P)]
-    paths = [[[]] for _ in range(P)]
-    active = length < 0
-    for t in range(1, max_depth + 1):
-        pending = []
-        for p in np.flatnonzero(active):
-            live = len(beams[p])
+class Stepper:
+    """The restated search one stage at a time, the four stages of the device (include/rubiksearch.h): expand -> (scores from the
+    caller) -> select -> advance.  Per problem it holds the live beam, the last actions and the history; a GPU test drives a
+    BeamPlan next to it and compares the buffers after every stage."""
+
+    def __init__(self, cube, roots, width, max_depth):
+        self.cube, self.W, self.D, self.P = cube, int(width), int(max_depth), len(roots)
+        self.length = np.where(cube.is_solved(roots), 0, -1).astype(np.int32)
+        self.solution = np.full(self.P, -1, np.int32)
+        self.active = self.length < 0
+        self.live = self.active.astype(np.int32)
+        self.beams = [roots[p:p + 1][:self.live[p]].copy() for p in range(self.P)]
+        self.last = [np.full(self.live[p], cube.A, np.int64) for p in range(self.P)]
+        self.hist = []            # row t - 1: per problem (parent slot [live], action [live]) of the beam after depth t
+        self.depth = 1            # the 1-based depth the next expand searches
+        self.cand, self.sel = {}, {}
+
+    def expand(self):
+        """cand[p] of every active problem, arrays over c = w * A + a ascending: w, a, children, valid, solved, keys; and what
+        follows from them alone: hit (the lowest valid solved c, or -1) and surv (the survivor mask; None when hit >= 0)."""
+        cube, A = self.cube, self.cube.A
+        self.cand, self.sel = {}, {}
+        for p in np.flatnonzero(self.active):
+            live = len(self.beams[p])
             w = np.repeat(np.arange(live), A)
-            a = np.tile(np.arange(A), live)                                # c = w * A + a, ascending
-            children = cube.move(beams[p][w], a)
-            valid = a != (last[p][w] ^ 1)
-            kind, res, surv = select_problem(valid, cube.is_solved(children), cube.keys(children), np.zeros(len(a), np.float32), 1)
-            if kind == "solved":
-                path = paths[p][w[res]] + [int(a[res])]
-                length[p], active[p] = t, False
-                actions[:t, p] = path
+            a = np.tile(np.arange(A), live)
+            children = cube.move(self.beams[p][w], a)
+            valid = a != (self.last[p][w] ^ 1)
+            solved, keys = cube.is_solved(children), cube.keys(children)
+            kind, res, surv = select_problem(valid, solved, keys, np.zeros(len(a), np.float32), 1)
+            self.cand[int(p)] = dict(w=w, a=a, children=children, valid=valid, solved=solved, keys=keys,
+                                     hit=res if kind == "solved" else -1, surv=surv)
+
+    def select(self, scores):
+        """scores[p]: float32 over c for every problem of cand without a hit.  sel[p] = ("solved", c) | ("kept", ascending c)."""
+        for p, cd in self.cand.items():
+            if cd["hit"] >= 0:
+                self.sel[p] = ("solved", cd["hit"])
+                self.length[p], self.solution[p], self.active[p] = self.depth, cd["hit"], False
                 continue
-            pending.append((p, w, a, children, valid, surv))
-        if not pending:
-            break
-        allc = np.concatenate([ch[s] for (_, _, _, ch, _, s) in pending])
-        sc = np.asarray(score_fn(cube.onehot(allc)), np.float32).reshape(-1)
-        at = 0
-        for p, w, a, children, valid, surv in pending:
-            scores = np.full(len(a), np.nan, np.float32)
-            k = int(surv.sum())
-            scores[surv] = sc[at:at + k]
-            at += k
-            cand = np.flatnonzero(surv)
-            kept = np.sort(cand[rank_order(scores[cand], cand)[:width]])
-            beams[p], last[p] = children[kept], a[kept]
-            paths[p] = [paths[p][w[c]] + [int(a[c])] for c in kept]
-    return {"solved": length >= 0, "length": length, "actions": actions}
+            cnd = np.flatnonzero(cd["surv"])
+            sc = np.asarray(scores[p], np.float32)
+            self.sel[p] = ("kept", np.sort(cnd[rank_order(sc[cnd], cnd)[:self.W]]))
+
+    def sel_count(self):
+        return np.array([len(self.sel[p][1]) if p in self.sel and self.sel[p][0] == "kept" else 0 for p in range(self.P)], np.int32)
+
+    def advance(self):
+        row = []
+        for p in range(self.P):
+            kind, kept = self.sel.get(p, ("none", None))
+            if kind == "kept":
+                cd = self.cand[p]
+                self.beams[p], self.last[p] = cd["children"][kept], cd["a"][kept]
+                row.append((cd["w"][kept], cd["a"][kept]))
+            else:
+                self.beams[p], self.last[p] = self.beams[p][:0], self.last[p][:0]
+                row.append((np.zeros(0, np.int64), np.zeros(0, np.int64)))
+        self.live = np.array([len(b) for b in self.beams], np.int32)
+        self.hist.append(row)
+        self.depth += 1
+
+    def backtrack(self):
+        """actions [max_depth, P]: the solution's moves read back through the history, then the no-op."""
+        A = self.cube.A
+        actions = np.full((max(self.D, 0), self.P), A, np.uint8)
+        for p in np.flatnonzero(self.length >= 1):
+            L, c = int(self.length[p]), int(self.solution[p])
+            w, actions[L - 1, p] = c // A, c % A
+            for t in range(L - 1, 0, -1):
+                par, act = self.hist[t - 1][p]
+                actions[t - 1, p], w = act[w], int(par[w])
+        return actions
+
+
+def beam_search(cube, roots, width, max_depth, score_fn):
+    """roots [P, S] -> dict(solved [P], length [P], actions [max_depth, P]).  score_fn(onehot float32 [m, R, C]) -> float32 [m].
+    Only the survivors are scored, all problems of a depth in one call."""
+    st = Stepper(cube, roots, width, max_depth)
+    while st.depth <= max_depth and st.active.any():
+        st.expand()
+        pending = [p for p, cd in st.cand.items() if cd["hit"] < 0]
+        scores = {}
+        if pending:
+            allc = np.concatenate([st.cand[p]["children"][st.cand[p]["surv"]] for p in pending])
+            sc = np.asarray(score_fn(cube.onehot(allc)), np.float32).reshape(-1)
+            at = 0
+            for p in pending:
+                surv = st.cand[p]["surv"]
+                scores[p] = np.full(len(surv), np.nan, np.float32)
+                k = int(surv.sum())
+                scores[p][surv] = sc[at:at + k]
+                at += k
+        st.select(scores)
+        st.advance()
+    return {"solved": st.length >= 0, "length": st.length.copy(), "actions": st.backtrack()}
+
+
+def hard_scores(rng, n, width, mode):
+    """n float32 scores that make the low bytes of a rank decide (tests of the select kernel and of rank_order itself).
+    mode 0  uniformly random 32-bit patterns: NaN payloads, denormals, both zeros, +-inf
+    mode 1  a positive base + 0..300 ulps built through the integer view: neighbours differ in the lowest mantissa byte or the
+            second lowest only;  mode 2: the same below a negative base
+    mode 3  +0, -0 and -2 only: the zeros are ONE block of equal scores (-0 == +0) of two thirds of the candidates, c decides
+    mode 4  every candidate draws one of the sources above, or one of +-FLT_MAX, +-the smallest denormal, +-0, +-inf, NaN"""
+    bits = rng.integers(0, 1 << 32, n, dtype=np.uint64).astype(np.uint32)
+    ulps = rng.integers(0, 301, n).astype(np.uint32)
+    pos = (np.array([1.5e30], np.float32).view(np.uint32)[0] + ulps).astype(np.uint32)
+    neg = (np.array([-3.0], np.float32).view(np.uint32)[0] + ulps).astype(np.uint32)
+    blocks = np.array([0.0, -0.0, -2.0], np.float32).view(np.uint32)[rng.integers(0, 3, n)]
+    ext = np.array([0x7F7FFFFF, 0xFF7FFFFF, 0x00000001, 0x80000001, 0, 0x80000000, 0x7F800000, 0xFF800000, 0x7FC00000, 0xFFC00001],
+                   np.uint32)[rng.integers(0, 10, n)]
+    src = [bits, pos, neg, blocks, ext]
+    if mode < 4:
+        return src[mode].view(np.float32).copy()
+    pick = rng.integers(0, 5, n)
+    return np.choose(pick, src).astype(np.uint32).view(np.float32).copy()
 
 
 def bfs_distances(cube, depth):

@@ -176,6 +176,42 @@ def test_family_and_targets_depth_groups_match_single_depth_launches(ops, L, ora
         ops.adi_targets_depths(v[:10], 13 * bs, bs, bufs["child_solved"], v[12 * bs:], 13 * bs, wgt, n, D, 3, tv[3:, 1:], tp[3:, 1:], er[3:, 1:])
 
 
+@pytest.mark.parametrize("cs", [3, 2])
+def test_targets_depth_groups_with_nonfinite_values(ops, cs):
+    """rc_adi_targets_depths on the net-output layout [D][A + 1][bs] with the non-finite columns of tests/adi_cases.py, a different
+    permutation of them at every depth, against torch.max on CPU float32 tensors (NaN propagates, index of the first NaN)."""
+    import os
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import adi_cases
+    adi_cases.check_oracle()
+    A = 12 if cs == 3 else 6
+    cv, solved, pv = adi_cases.edge_columns(A, seed=10 + cs)
+    n, D = cv.shape[1], 4
+    bs, wp = -(-n // 8) * 8 + 8, -(-n // 256) * 256
+    g = torch.Generator().manual_seed(cs)
+    perms = [torch.randperm(n, generator=g) for _ in range(D)]
+    v = torch.zeros((D, A + 1, bs))
+    sol = torch.zeros((D, A, wp), dtype=torch.uint8)
+    for d in range(D):
+        v[d, :A, :n], v[d, A, :n], sol[d, :, :n] = cv[:, perms[d]], pv[perms[d]], solved[:, perms[d]]
+    wgt = np.array([float(d + 1) ** -0.5 for d in range(D)])
+    vd = v.reshape(-1).cuda()
+    tv = torch.zeros((n + 3, D + 2), dtype=torch.float32, device="cuda")
+    tp = torch.full((n + 3, D + 2), -7, dtype=torch.int32, device="cuda")
+    er = torch.zeros((n + 3, D + 2), dtype=torch.float64, device="cuda")
+    ops.adi_targets_depths(vd, (A + 1) * bs, bs, sol.cuda(), vd[A * bs:], (A + 1) * bs, torch.tensor(wgt, dtype=torch.float64).cuda(), n, D, cs,
+                           tv[3:, 1:], tp[3:, 1:], er[3:, 1:])
+    for d in range(D):
+        e_tv, e_tp, e_err = adi_cases.expected(cv[:, perms[d]].contiguous(), solved[:, perms[d]].contiguous(), pv[perms[d]], np.full(n, wgt[d]))
+        assert np.isnan(e_tv).sum() > 100
+        adi_cases.assert_same(tp[3:3 + n, 1 + d].cpu().numpy(), e_tp, ("target_policy", d))
+        adi_cases.assert_same(tv[3:3 + n, 1 + d].cpu().numpy(), e_tv, ("target_value", d))
+        adi_cases.assert_same(er[3:3 + n, 1 + d].cpu().numpy(), e_err, ("error", d))
+    assert float(tv[:3].abs().sum()) == 0 and float(tv[:, 0].abs().sum()) == 0 and float(tv[:, D + 1].abs().sum()) == 0   # nothing outside the view
+    assert bool((tp[:3] == -7).all()) and bool((tp[:, 0] == -7).all()) and bool((tp[:, D + 1] == -7).all())
+
+
 @pytest.mark.parametrize("cs", [2, 3])
 def test_onehot_from_code_blocks_packs_equally_tiled_buffers(ops, L, oracle, cs):
     """rc_onehot_from_code_blocks (round 6): the A child-code buffers of several depths of ONE rc_adi_generate call, each [tile][SLOTS][pitch],

@@ -406,6 +406,35 @@ def test_adi_targets(ops, cs):
     assert (err.cpu().numpy() == exp_err).all()
 
 
+@pytest.mark.parametrize("cs", CS)
+def test_adi_targets_nonfinite(ops, cs):
+    """Non-finite child values (tests/adi_cases.py: NaN at every index, at several, everywhere; +-inf; -0 / +0 ties; solved children
+    next to NaN; NaN parent values) against the reference's own operator, torch.max on CPU float32 tensors: NaN propagates with the
+    index of the first NaN, otherwise the first maximal index; a solved child wins over both."""
+    import os
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import adi_cases
+    adi_cases.check_oracle()
+    A = A_OF[cs]
+    cv, solved, pv = adi_cases.edge_columns(A, seed=cs)
+    n = cv.shape[1]
+    p = -(-n // 256) * 256
+    cvp, sp = torch.zeros((A, p)), torch.zeros((A, p), dtype=torch.uint8)
+    cvp[:, :n], sp[:, :n] = cv, solved
+    w = np.array([float(1 + i % 30) ** -0.3 for i in range(n)])
+    tv, tp, err = ops.adi_targets(cvp.cuda(), sp.cuda(), n, cs, pv.cuda(), torch.tensor(w, dtype=torch.float64).cuda())
+    e_tv, e_tp, e_err = adi_cases.expected(cv, solved, pv, w)
+    assert np.isnan(e_tv).sum() > 100 and np.isinf(e_tv).sum() > 50 and (e_tv == 1.0).sum() > 20      # the cases are there
+    adi_cases.assert_same(tp.cpu().numpy(), e_tp, "target_policy")
+    adi_cases.assert_same(tv.cpu().numpy(), e_tv, "target_value")
+    adi_cases.assert_same(err.cpu().numpy(), e_err, "error")
+    tv2, tp2, none = ops.adi_targets(cvp.cuda(), sp.cuda(), n, cs)                                    # without the error output
+    assert none is None
+    adi_cases.assert_same(tv2.cpu().numpy(), e_tv, "target_value")
+    adi_cases.assert_same(tp2.cpu().numpy(), e_tp, "target_policy")
+
+
 def test_full_size_properties(ops, L):
     """BASELINE sizes (4M cubes): order-4 and inverse identities, checksum of checksums."""
     n = 1 << 22

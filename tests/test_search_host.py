@@ -95,3 +95,34 @@ def test_restated_search_with_the_checkpoint_solves_every_fixture_scramble():
     res = beam_ref.beam_search(cube, roots, 16, 30, lambda x: beam_ref.value_head(sd, x))
     assert res["solved"].all() and (res["length"] <= g["ks"][pick]).all()
     assert replay_solves(cube, roots, res["actions"], res["length"])
+
+
+def test_rank_order_equals_a_plain_sort_with_an_explicit_key():
+    """beam_ref.rank_order (the reference of the select kernel's order) against Python's sorted with the order spelt out: NaN
+    below everything, then the score descending with -0 == +0, then c ascending -- on the generator the GPU select tests use
+    (random bit patterns, neighbours a few ulps apart, blocks of equal scores, +-FLT_MAX, denormals, +-inf, NaN payloads)."""
+    import math
+
+    for mode in range(5):
+        for n in (1, 2, 700, 5000):
+            rng = np.random.default_rng(100 * mode + n)
+            s = beam_ref.hard_scores(rng, n, 7, mode)
+            c = rng.permutation(4 * n)[:n]
+            assert s.dtype == np.float32 and len(s) == n
+
+            def key(i):
+                if math.isnan(s[i]):
+                    return (1, 0.0, int(c[i]))
+                return (0, -(0.0 if s[i] == 0 else float(s[i])), int(c[i]))
+
+            assert sorted(range(n), key=key) == beam_ref.rank_order(s, c).tolist(), (mode, n)
+    # the generator reaches what it promises
+    s = np.concatenate([beam_ref.hard_scores(np.random.default_rng(m), 20000, 7, m) for m in (0, 4)])
+    u = s.view(np.uint32)
+    assert np.isnan(s).any() and np.isinf(s).any() and (u == 0x80000000).any() and (u == 0).any()
+    assert (u == 0x7F7FFFFF).any() and (u == 0xFF7FFFFF).any() and (u == 1).any() and (u == 0x80000001).any()
+    assert ((u & 0x7F800000) == 0).sum() > 50                                 # denormals
+    for m in (1, 2):                                                          # 301 neighbours: only the two low bytes differ
+        u = beam_ref.hard_scores(np.random.default_rng(m), 20000, 7, m).view(np.uint32)
+        assert len(np.unique(u)) == 301 and len(np.unique(u >> 16)) == 1 and len(np.unique(u >> 8)) == 2
+    assert set(beam_ref.hard_scores(np.random.default_rng(3), 1000, 7, 3).view(np.uint32).tolist()) == {0, 0x80000000, 0xC0000000}
