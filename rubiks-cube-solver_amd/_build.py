@@ -1,5 +1,5 @@
 """Build identity of the native libraries: a hash of the sources a library is compiled from, embedded at build time
-(-DRC_SRC_HASH=..., returned by rc_build_id() / rc_tree_build_id()) and recomputed from the tree at load time.
+(-DRC_SRC_HASH=..., returned by rc_build_id() / rc_tree_build_id() / rc_search_build_id() / rc_net_build_id()) and recomputed from the tree at load time.
 
 A library whose embedded id differs from the tree's sources is STALE: __graft_entry__.build() recompiles it (it compares ids, not
 mtimes -- touching the .so hides nothing) and _lib.lib() / _tree.tree_lib() refuse to load it.  No torch import here: build() runs
@@ -18,6 +18,7 @@ HIP_SOURCES = (os.path.join(_HERE, "csrc", "rubikhip.hip"), os.path.join(_HERE, 
 TREE_SOURCES = (os.path.join(_HERE, "csrc", "rc_tree.cpp"), os.path.join(_ROOT, "include", "rubiktree.h"))
 SEARCH_SOURCES = (os.path.join(_HERE, "csrc", "rc_search.hip"), os.path.join(_HERE, "csrc", "rc_device.h"),
                   os.path.join(_HERE, "csrc", "rc_tables.h"), os.path.join(_ROOT, "include", "rubiksearch.h"))
+NET_SOURCES = (os.path.join(_HERE, "csrc", "rc_net.hip"), os.path.join(_ROOT, "include", "rubiknet.h"))
 
 
 def source_hash(paths) -> str | None:

@@ -7,6 +7,9 @@ One depth step, all on the device and without a host synchronisation:
   rc_search_select     solved check, exact removal of duplicate states, the W best per cube (score desc, candidate index asc)
   rc_search_advance    the kept children become the next beam (ping-pong buffers) + one history row
 The solutions are read back from the history by rc_search_backtrack at the end.
+
+front="codes" (opt-in; DESIGN.md "Net front") replaces the second line: rc_net_first_layer sums the first layer's rows straight from
+the candidate codes into a [chunk, H1] buffer, and the rest of the encoder and the value head run on that; no dense one-hot exists.
 """
 from __future__ import annotations
 
@@ -34,7 +37,16 @@ class BeamPlan:
     """Device buffers of one search shape (P problems, width W, max_depth D) and the launches of one depth step.
     Layouts: include/rubiksearch.h.  The methods wrap one entry point each; tests drive them one by one."""
 
-    def __init__(self, n_problems, cube_size, width, max_depth, device, dtype=torch.float32, dense_budget_bytes=1 << 30):
+    def __init__(self, n_problems, cube_size, width, max_depth, device, dtype=torch.float32, dense_budget_bytes=1 << 30, front="dense",
+                 hidden=None):
+        """front="codes": `hidden` = H1, the width of the net's first layer; the plan then holds a [chunk, H1] buffer of `dtype` instead of
+        the dense one-hot, sized by the same dense_budget_bytes rule."""
+        if front not in ("dense", "codes"):
+            raise ValueError(f"front must be 'dense' or 'codes', got {front!r}")
+        if front == "codes" and (hidden is None or dtype not in (torch.float32, torch.bfloat16)):
+            raise ValueError("front='codes' needs hidden = the first layer's width and a float32 or bfloat16 model "
+                             f"(the kernel takes no other format), got hidden = {hidden}, dtype = {dtype}")
+        self.front = front
         if not 1 <= int(width) <= MAX_WIDTH:
             raise ValueError(f"width must be in 1..{MAX_WIDTH}")
         if int(max_depth) < 0 or int(n_problems) < 1:
@@ -64,10 +76,14 @@ class BeamPlan:
         L = _search_lib.search_lib()
         self.workspace = torch.empty(int(L.rc_search_workspace_bytes(self.cs, self.P, self.W)), dtype=torch.uint8, device=dev)
         self.dtype = dtype
-        row_bytes = self.R * self.C * torch.empty((), dtype=dtype).element_size()
+        row_bytes = (self.R * self.C if front == "dense" else int(hidden)) * torch.empty((), dtype=dtype).element_size()
         total = A * nbp
         self.chunk = min(total, max(self.pitch, int(dense_budget_bytes) // row_bytes // self.pitch * self.pitch))
-        self.dense = torch.empty((self.chunk, self.R, self.C), dtype=dtype, device=dev)
+        if front == "dense":
+            self.dense = torch.empty((self.chunk, self.R, self.C), dtype=dtype, device=dev)
+        else:
+            self.hidden = torch.empty((self.chunk, int(hidden)), dtype=dtype, device=dev)
+            self._net = None
 
     # ------------------------------------------------------------------ one entry point each
     def init(self, roots, root_pitch):
@@ -84,12 +100,40 @@ class BeamPlan:
 
     def score(self, model):
         """scores = model(dense one-hot)[0][:, 0] for every candidate, one forward per chunk (chunks start on tile boundaries)."""
+        if self.front == "codes":
+            return self.score_codes(model)
         total, flat = self.A * self.nbp, self.scores.view(-1)
         for j0 in range(0, total, self.chunk):
             m = min(self.chunk, total - j0)
             t0 = j0 // self.pitch
             ops.onehot_from_code(self.code[t0:t0 + m // self.pitch], m, self.cs, self.dense[:m])
             flat[j0:j0 + m].copy_(model(self.dense[:m])[0][:, 0])
+
+    def code_net(self, model):
+        """The CodeNet of `model` (a CodeNet passes through), checked against the plan: cube size, H1, dtype, device."""
+        from .codenet import CodeNet
+        if isinstance(model, CodeNet):
+            net = model
+        else:
+            if self._net is None or self._net.model is not model:
+                self._net = CodeNet(model, self.cs)
+            net = self._net
+        if net.cube_size != self.cs or net.hidden != self.hidden.shape[1]:
+            raise ValueError(f"front='codes': the plan was built for a {self.cs}x{self.cs}x{self.cs} net with H1 = {self.hidden.shape[1]}, "
+                             f"the model is {net.cube_size}x{net.cube_size}x{net.cube_size} with H1 = {net.hidden}")
+        if net.dtype != self.dtype or net.device != self.code.device:
+            raise ValueError(f"front='codes': the model is {net.dtype} on {net.device}, the plan {self.dtype} on {self.code.device}")
+        return net
+
+    def score_codes(self, model):
+        """scores = value head from the candidate CODES, per chunk: rc_net_first_layer -> hidden, then the rest of the encoder and
+        value_net (codenet.CodeNet.value_codes).  The policy head is not run."""
+        net = self.code_net(model)
+        total, flat = self.A * self.nbp, self.scores.view(-1)
+        for j0 in range(0, total, self.chunk):
+            m = min(self.chunk, total - j0)
+            t0 = j0 // self.pitch
+            flat[j0:j0 + m].copy_(net.value_codes(self.code[t0:t0 + m // self.pitch], m, out=self.hidden)[:, 0])
 
     def select(self):
         check(_search_lib.search_lib().rc_search_select(ptr(self.flags), ptr(self.keys), ptr(self.scores), self.P, self.W, self.pitch, self.cs,
@@ -118,20 +162,32 @@ class BeamPlan:
 
 
 @torch.no_grad()
-def beam_search(model, env, width, max_depth, *, dense_budget_bytes=1 << 30, sync_every=4, graph=False):
+def beam_search(model, env, width, max_depth, *, dense_budget_bytes=1 << 30, sync_every=4, graph=False, front="dense"):
     """Beam search from every cube of `env` (a VecCubeEnv, any observation mode; its state is left unchanged).
 
     Each depth expands the beam, scores the children with the value head model(onehot)[0][:, 0] in the model's dtype, and keeps the
     `width` best distinct children per cube (ties: the lower candidate index c = slot * A + action); a cube is solved at the first
     depth where a child is solved.  "All cubes done" is checked on the host every `sync_every` depths.  graph=True replays one
     depth step as a hipGraph (two captures: the two directions of the beam ping-pong); the results equal the eager run's.
+    front="codes": the net's first layer is summed from the candidate codes by rc_net_first_layer (codenet.CodeNet; the model must have
+    the reference's layout, be float32 or bfloat16 and live on the cubes' device); the default "dense" feeds model() dense one-hots.
 
     Returns dict(solved bool [P], length int32 [P] (0: the root was solved, -1: not solved within max_depth), actions uint8
     [max_depth, P]: the solution's moves, then the no-op action_dim)."""
     from .adi import _module_dtype
     P, cs = env.num_envs, env.cube_size
     dtype = _module_dtype(model)
-    plan = BeamPlan(P, cs, width, max_depth, env.device, dtype, dense_budget_bytes)
+    if front == "codes":
+        from .codenet import CodeNet
+        model = model if isinstance(model, CodeNet) else CodeNet(model, cs)      # ValueError for a float16 model
+        dtype = model.dtype
+        if model.device != env.stickers.device:
+            raise ValueError(f"front='codes': the model is on {model.device}, the cubes on {env.stickers.device}")
+        plan = BeamPlan(P, cs, width, max_depth, env.device, dtype, dense_budget_bytes, front="codes", hidden=model.hidden)
+    else:
+        if front != "dense":
+            raise ValueError(f"front must be 'dense' or 'codes', got {front!r}")
+        plan = BeamPlan(P, cs, width, max_depth, env.device, dtype, dense_budget_bytes)
     plan.init(env.stickers, env.stickers.shape[-1])
     graphs = {}
     for t in range(1, plan.D + 1):
@@ -161,7 +217,7 @@ def beam_search(model, env, width, max_depth, *, dense_budget_bytes=1 << 30, syn
 
 @torch.no_grad()
 def beam_solve_percentage(model, cube_size, sample_scramble_count, sample_cube_count, width, max_depth, device="cuda", seeds=None,
-                          graph=False):
+                          graph=False, front="dense"):
     """rollout.solve_percentage with the beam search as the solver: for scramble_count = 1..sample_scramble_count, the percentage
     of the sample_cube_count cubes (seeds i * 10, train.py:180) solved within max_depth.  All (k, seed) pairs run as ONE batch."""
     from .vec_env import VecCubeEnv
@@ -169,6 +225,6 @@ def beam_solve_percentage(model, cube_size, sample_scramble_count, sample_cube_c
     ks = [k for k in range(1, sample_scramble_count + 1) for _ in seeds]
     env = VecCubeEnv(len(ks), device, cube_size, obs=None)
     env.reset(seeds=seeds * sample_scramble_count, scramble_count=ks)
-    res = beam_search(model, env, width, max_depth, graph=graph)
+    res = beam_search(model, env, width, max_depth, graph=graph, front=front)
     solved = res["solved"].view(sample_scramble_count, len(seeds)).float().mean(1) * 100.0
     return [float(x) for x in solved.cpu()]

@@ -1,0 +1,165 @@
+"""The net front without a GPU: librubiknet.so's ABI and build id, the code -> one-hot index table, what CodeNet refuses, and the
+restatement (tests/net_ref.py) against the dense first layer."""
+import os
+import re
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import beam_ref  # noqa: E402
+import net_ref  # noqa: E402
+
+
+def test_net_abi_exports_every_declared_symbol():
+    from rubiks_cube_solver_amd import _build, _net_lib
+    L = _net_lib.net_lib()                                            # loads without a GPU
+    header = open(os.path.join(ROOT, "include", "rubiknet.h")).read()
+    declared = set(re.findall(r"^(?:int|int64_t|const char \*)\s*(rc_net_\w+)\(", header, re.M))
+    assert declared == {"rc_net_build_id", "rc_net_last_error", "rc_net_first_layer"}
+    assert os.path.exists(os.path.join(ROOT, "rubiks-cube-solver_amd", "librubiknet.so"))
+    nm = subprocess.run(["nm", "-D", "--defined-only", _net_lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
+    exported = {l.split()[-1] for l in nm.splitlines() if " T " in l}
+    assert {e for e in exported if e.startswith("rc_")} == declared, exported ^ declared
+    assert _net_lib.build_id() == _build.source_hash(_build.NET_SOURCES) == _build.embedded_id(_net_lib.LIB_PATH)
+    assert L.rc_net_last_error() == b""
+    # the header restates the two formats of include/rubikhip.h: same values
+    fmt = lambda text: {k: int(v) for k, v in re.findall(r"#define (RC_FMT_F32|RC_FMT_BF16) (\d+)", text)}
+    assert fmt(header) == fmt(open(os.path.join(ROOT, "include", "rubikhip.h")).read()) == {"RC_FMT_F32": 4, "RC_FMT_BF16": 5}
+    # a library of its own: the other libraries' sources do not include it
+    assert not set(_build.NET_SOURCES) & (set(_build.HIP_SOURCES) | set(_build.SEARCH_SOURCES) | set(_build.TREE_SOURCES))
+
+
+def test_stale_net_library_is_refused(tmp_path):
+    from rubiks_cube_solver_amd import _build, _net_lib
+    fake = str(tmp_path / "librubiknet.so")
+    data = bytearray(open(_net_lib.LIB_PATH, "rb").read())
+    i = data.find(_build.MARKER) + len(_build.MARKER)
+    data[i] = ord("0") if data[i] != ord("0") else ord("1")
+    open(fake, "wb").write(bytes(data))
+    code = "from rubiks_cube_solver_amd import _net_lib; _net_lib.net_lib(); print('loaded')"
+    env = dict(os.environ, RUBIKNET_LIB=fake)
+    env.pop("RC_ALLOW_STALE", None)
+    out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300, cwd=ROOT, env=env)
+    assert out.returncode != 0 and "is stale" in out.stderr and "loaded" not in out.stdout, out.stderr[-2000:]
+    out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300, cwd=ROOT,
+                         env=dict(env, RUBIKNET_LIB=str(tmp_path / "missing.so")))
+    assert out.returncode != 0 and "not found" in out.stderr
+
+
+@pytest.mark.parametrize("cs", [3, 2])
+def test_onehot_index_is_where_the_dense_one_hot_has_its_ones(cs):
+    """codenet.onehot_index(cs)[s, code_s] = the argmax positions of beam_ref.Cube(cs).onehot, on 1000 random scrambles; the table is
+    a bijection onto the R * C inputs where the code ranges allow (3x3x3) and injective per slot; net_ref.row_index agrees."""
+    from rubiks_cube_solver_amd import codenet
+    cube = beam_ref.Cube(cs)
+    tab = codenet.onehot_index(cs)
+    assert tab.shape == (cube.slots, net_ref.N_CODES[cs]) and tab.dtype.kind == "i"
+    assert tab.min() == 0 and tab.max() == cube.R * cube.C - 1
+    rng = np.random.default_rng(cs)
+    st = net_ref.random_states(cube, 1000, rng)
+    codes = cube.codes(st)
+    flat = cube.onehot(st).reshape(len(st), -1)
+    assert (flat.sum(1) == cube.slots).all()
+    got = tab[np.arange(cube.slots)[None, :], codes]                                  # [n, SLOTS]
+    assert (np.sort(got, 1) == np.stack([np.flatnonzero(r) for r in flat])).all()       # the same set of ones per state
+    assert (flat[np.arange(len(st))[:, None], got] == 1).all()
+    assert (got == net_ref.row_index(cs, codes)).all()
+    if cs == 3:
+        assert sorted(tab.reshape(-1)) == list(range(480))
+    else:                                                                               # every slot's codes hit distinct inputs
+        assert all(len(set(row)) == 21 for row in tab)
+
+
+def _deepcube(in_features=480, alpha=1.0, hidden=(32, 16, 8)):
+    import torch
+    nn = torch.nn
+
+    class M(nn.Module):
+        def __init__(self):
+            super().__init__()
+            self.encoder_net = nn.Sequential(nn.Flatten(), nn.Linear(in_features, hidden[0]), nn.ELU(alpha), nn.Linear(hidden[0], hidden[1]), nn.ELU())
+            self.policy_net = nn.Sequential(nn.Linear(hidden[1], hidden[2]), nn.ELU(), nn.Linear(hidden[2], 12))
+            self.value_net = nn.Sequential(nn.Linear(hidden[1], hidden[2]), nn.ELU(), nn.Linear(hidden[2], 1))
+
+    return M()
+
+
+def test_codenet_refuses_what_is_not_the_reference_layout():
+    import torch
+    import rubiks_cube_solver_amd as pkg
+    from rubiks_cube_solver_amd.codenet import CodeNet
+    assert pkg.CodeNet is CodeNet and "CodeNet" in pkg.__all__
+    with pytest.raises(TypeError, match="encoder_net"):
+        CodeNet(torch.nn.Linear(480, 1))
+    with pytest.raises(TypeError, match="alpha"):
+        CodeNet(_deepcube(alpha=0.5))
+    with pytest.raises(TypeError, match="in_features"):
+        CodeNet(_deepcube(in_features=481))
+    with pytest.raises(TypeError, match="in_features"):
+        CodeNet(_deepcube(in_features=147), cube_size=3)                 # a 2x2x2 net for 3x3x3 cubes
+    no_value = _deepcube()
+    del no_value.value_net
+    with pytest.raises(TypeError, match="value_net"):
+        CodeNet(no_value)
+    with pytest.raises(TypeError, match="Flatten, Linear, ELU"):
+        m = _deepcube()
+        m.encoder_net[2] = torch.nn.ReLU()
+        CodeNet(m)
+    with pytest.raises(ValueError, match="float16"):
+        CodeNet(_deepcube().half())
+    # the layout itself is accepted (no GPU needed to build the table), sizes are read off the module
+    net = CodeNet(_deepcube())
+    assert (net.cube_size, net.hidden) == (3, 32) and net.weight_t.shape == (480, 32) and net.weight_t.is_contiguous()
+    assert CodeNet(_deepcube(in_features=147)).cube_size == 2
+
+
+def test_codenet_table_follows_the_weight_in_the_same_storage():
+    """An in-place update (optimiser step) and a re-allocated weight are both seen by _sync(); the table keeps its address."""
+    import torch
+    from rubiks_cube_solver_amd.codenet import CodeNet
+    m = _deepcube()
+    net = CodeNet(m)
+    w = m.encoder_net[1].weight
+    at = net.weight_t.data_ptr()
+    assert torch.equal(net.weight_t, w.detach().t())
+    with torch.no_grad():
+        w.add_(1)
+    assert not torch.equal(net.weight_t, w.detach().t())
+    net._sync()
+    assert torch.equal(net.weight_t, w.detach().t()) and net.weight_t.data_ptr() == at
+    m.encoder_net[1].weight = torch.nn.Parameter(torch.zeros_like(w))           # re-allocated: another data_ptr
+    net._sync()
+    assert float(net.weight_t.abs().sum()) == 0 and net.weight_t.data_ptr() == at
+    net._sync()                                                                  # nothing changed: nothing copied
+    assert net._seen[0] == m.encoder_net[1].weight._version
+
+
+@pytest.mark.parametrize("cs", [3, 2])
+def test_restated_row_sum_is_the_dense_first_layer(cs):
+    """net_ref.first_layer (slot order, float32) against onehot @ W1.T + b1 in float64: within gamma_m * (|b| + sum |w|), m = SLOTS + 1
+    terms (Higham, Accuracy and Stability of Numerical Algorithms, 2nd ed., eq. 4.4).  bf16 rounding restated with integers equals torch's."""
+    import torch
+    cube = beam_ref.Cube(cs)
+    rng = np.random.default_rng(10 + cs)
+    H = 72
+    w1 = rng.standard_normal((H, cube.R * cube.C)).astype(np.float32)
+    b1 = rng.standard_normal(H).astype(np.float32)
+    st = net_ref.random_states(cube, 500, rng)
+    codes, oh = cube.codes(st), cube.onehot(st).reshape(len(st), -1)
+    got = net_ref.first_layer(cs, codes, np.ascontiguousarray(w1.T), b1)
+    exact = oh.astype(np.float64) @ w1.T.astype(np.float64) + b1
+    mag = oh.astype(np.float64) @ np.abs(w1.T).astype(np.float64) + np.abs(b1)
+    u, m = 2.0 ** -24, cube.slots + 1
+    gamma = (m - 1) * u / (1 - (m - 1) * u)
+    assert (np.abs(got - exact) <= gamma * mag).all()
+    x = np.concatenate([rng.standard_normal(5000).astype(np.float32) * 1e3, np.array([0.0, -0.0, np.inf, -np.inf, 1e-40, 3.3895314e38], np.float32),
+                        rng.integers(0, 1 << 32, 5000, dtype=np.uint64).astype(np.uint32).view(np.float32)])
+    x = x[~np.isnan(x)]
+    want = torch.tensor(x).to(torch.bfloat16).view(torch.int16).numpy().view(np.uint16)
+    assert (net_ref.bf16_bits(x) == want).all()
+    assert (net_ref.bf16_to_f32(want) == torch.tensor(x).to(torch.bfloat16).float().numpy()).all()
+    assert ((net_ref.bf16_bits(np.array([np.nan], np.float32)) & 0x7FFF) > 0x7F80).all()

@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
-"""Cross-compile rubikhip.hip for gfx950 to assembly (no GPU needed) and print one line per kernel: registers, scratch,
+"""Cross-compile rubikhip.hip (or --src another .hip of csrc/, e.g. rc_net.hip) for gfx950 to assembly (no GPU needed) and print one line per kernel: registers, scratch,
 LDS, VALU count and the FORM of every memory instruction (flat / global / buffer / scratch, 64-bit VALU address adds).
 
-    python tools/kernel_usage.py [filter ...] [--json profiles/r02_isa_summary.json]
+    python tools/kernel_usage.py [filter ...] [--json profiles/r02_isa_summary.json] [--src rc_net.hip]
 
 This is the check behind DESIGN.md's claims "0 scratch", "0 flat_store / no per-access v_lshl_add_u64 on the row paths"."""
 import collections
@@ -20,6 +20,10 @@ out_json = None
 if "--json" in args:
     i = args.index("--json")
     out_json = args[i + 1]
+    del args[i:i + 2]
+if "--src" in args:
+    i = args.index("--src")
+    SRC = os.path.join(os.path.dirname(SRC), os.path.basename(args[i + 1]))
     del args[i:i + 2]
 with tempfile.TemporaryDirectory() as tmp:
     asm = os.path.join(tmp, "rubikhip.s")
