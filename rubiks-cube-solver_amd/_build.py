@@ -2,8 +2,8 @@
 (-DRC_SRC_HASH=..., returned by rc_build_id() / rc_tree_build_id() / rc_search_build_id() / rc_net_build_id()) and recomputed from the tree at load time.
 
 A library whose embedded id differs from the tree's sources is STALE: __graft_entry__.build() recompiles it (it compares ids, not
-mtimes -- touching the .so hides nothing) and _lib.lib() / _tree.tree_lib() refuse to load it.  No torch import here: build() runs
-this before anything else is loaded."""
+mtimes -- touching the .so hides nothing) and _native.load() refuses to load it.  LIBRARIES below is the one description of the
+libraries: the build and the loader both read it.  No torch import here: build() runs this before anything else is loaded."""
 from __future__ import annotations
 
 import hashlib
@@ -13,12 +13,35 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_HERE)
 MARKER = b"rc-build-id:"                     # the id is stored in the binary as "rc-build-id:<16 hex digits>"
 
-HIP_SOURCES = (os.path.join(_HERE, "csrc", "rubikhip.hip"), os.path.join(_HERE, "csrc", "rc_device.h"), os.path.join(_HERE, "csrc", "rc_tables.h"),
-               os.path.join(_ROOT, "include", "rubikhip.h"))
-TREE_SOURCES = (os.path.join(_HERE, "csrc", "rc_tree.cpp"), os.path.join(_ROOT, "include", "rubiktree.h"))
-SEARCH_SOURCES = (os.path.join(_HERE, "csrc", "rc_search.hip"), os.path.join(_HERE, "csrc", "rc_device.h"),
-                  os.path.join(_HERE, "csrc", "rc_tables.h"), os.path.join(_ROOT, "include", "rubiksearch.h"))
-NET_SOURCES = (os.path.join(_HERE, "csrc", "rc_net.hip"), os.path.join(_ROOT, "include", "rubiknet.h"))
+_HIPCC = ("hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17")
+_GXX = ("g++", "-O2", "-std=c++17", "-fopenmp", "-ffp-contract=off", "-Wall", "-Wextra")
+
+
+class Library:
+    """One native library: what it is compiled from and how, its override variable, how a process asks it who it is.  To add a
+    library: one row in LIBRARIES here, and a binding module with its signature table (SIGNATURES, build_id(); see _native.load)."""
+
+    def __init__(self, name, binding, file, sources, toolchain, env, id_symbol, error_symbol):
+        self.name, self.binding, self.file, self.toolchain, self.env = name, binding, file, toolchain, env   # binding: its ctypes module
+        self.gpu = toolchain is _HIPCC                                              # device code: loaded after torch, to share its HIP runtime
+        self.id_symbol, self.error_symbol = id_symbol, error_symbol                 # error_symbol None: the library keeps no last error
+        # every file the id hashes, in this order (source_hash depends on it): the translation unit that is compiled and the
+        # headers it includes from csrc/, then the public header in include/
+        self.sources = (*(os.path.join(_HERE, "csrc", s) for s in sources[:-1]), os.path.join(_ROOT, "include", sources[-1]))
+        self.built = os.path.join(_HERE, file)                                      # where build() writes it, whatever `env` says
+
+    def command(self, src_id, out):
+        """The one compile line of each toolchain.  The id hashes the sources only: to fold the flags in, hash this list too."""
+        return [*self.toolchain, "-fPIC", "-shared", f"-DRC_SRC_HASH={src_id}", self.sources[0], "-o", out]
+
+
+LIBRARIES = {l.name: l for l in (
+    Library("hip", "_lib", "librubikhip.so", ("rubikhip.hip", "rc_device.h", "rc_tables.h", "rubikhip.h"), _HIPCC, "RUBIKHIP_LIB", "rc_build_id", "rc_last_error"),
+    Library("tree", "_tree", "librubiktree.so", ("rc_tree.cpp", "rubiktree.h"), _GXX, "RUBIKTREE_LIB", "rc_tree_build_id", None),
+    Library("search", "_search_lib", "librubiksearch.so", ("rc_search.hip", "rc_device.h", "rc_tables.h", "rubiksearch.h"), _HIPCC, "RUBIKSEARCH_LIB",
+            "rc_search_build_id", "rc_search_last_error"),
+    Library("net", "_net_lib", "librubiknet.so", ("rc_net.hip", "rubiknet.h"), _HIPCC, "RUBIKNET_LIB", "rc_net_build_id", "rc_net_last_error"))}
+HIP_SOURCES, TREE_SOURCES, SEARCH_SOURCES, NET_SOURCES = (LIBRARIES[n].sources for n in ("hip", "tree", "search", "net"))
 
 
 def source_hash(paths) -> str | None:

@@ -7,107 +7,77 @@ or was not built, importing this module's `lib()` raises, loudly.
 from __future__ import annotations
 
 import ctypes
-import os
-import threading
 
 import torch  # must be imported before the library so both share one HIP runtime (libamdhip64.so.7)
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("RUBIKHIP_LIB") or os.path.join(_HERE, "librubikhip.so")   # env override: A/B builds in experiments
+from . import _native
+from ._native import RubikHipError  # noqa: F401  -- the package's error type lives with the loader; importable from here as before
+
+LIB_PATH = _native.path("hip")
 
 FMT_NONE, FMT_CODE, FMT_U8, FMT_F16, FMT_F32, FMT_BF16 = 0, 1, 2, 3, 4, 5
 _FMT_DTYPE = {FMT_U8: torch.uint8, FMT_F16: torch.float16, FMT_F32: torch.float32, FMT_BF16: torch.bfloat16}
 STATUS_BAD_ACTION = 1
 
-_lock = threading.Lock()
-_lib = None
 _inited = set()
 
-
-class RubikHipError(RuntimeError):
-    pass
-
-
-def _declare(L):
-    vp, i64, i32, u64 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_uint64
-    L.rc_version.restype = i32
-    L.rc_build_id.restype = ctypes.c_char_p
-    L.rc_last_error.restype = ctypes.c_char_p
-    L.rc_init.argtypes = [i32]
-    L.rc_get_tables.argtypes = [i32, vp, vp, vp, vp, vp, vp, vp]
-    L.rc_fill_solved.argtypes = [vp, i64, i64, i32, vp]
-    L.rc_apply_moves.argtypes = [vp, vp, vp, i64, i64, i64, i32, vp, vp, vp, i32, i64, vp]
-    L.rc_apply_moves_ex.argtypes = [vp, vp, vp, i64, i64, i64, i32, vp, vp, vp, i32, i64, vp, i32]
-    L.rc_apply_moves_ws.argtypes = [vp, vp, vp, i64, i64, i64, i32, vp, vp, vp, i32, i64, vp, i64, vp]
-    L.rc_encode_ws.argtypes = [vp, i64, i64, i32, vp, i32, i64, vp, i64, vp]
-    L.rc_workspace_bytes.argtypes = [i32, i32, i64, i32]
-    L.rc_workspace_bytes.restype = i64
-    L.rc_facade_step.argtypes = [vp, i64, i32, i32, vp, ctypes.c_uint32, i32, vp]
-    L.rc_facade_steps.argtypes = [vp, i64, i32, vp, i32, vp, ctypes.c_uint32, i32, vp]
-    L.rc_facade_expand.argtypes = [vp, i64, i32, vp, ctypes.c_uint32, i32, i32, vp]
-    L.rc_scramble.argtypes = [vp, i64, i64, i32, i32, u64, u64, i64, vp, vp, i64, vp, vp, vp]
-    L.rc_legacy_scramble_actions.argtypes = [vp, vp, i32, i32, i64, i32, vp, i64, vp]
-    L.rc_is_solved.argtypes = [vp, i64, i64, i32, vp, vp, vp]
-    L.rc_encode.argtypes = [vp, i64, i64, i32, vp, i32, i64, vp]
-    L.rc_onehot_from_code.argtypes = [vp, i64, i64, i32, vp, i32, vp]
-    L.rc_onehot_from_code_ex.argtypes = [vp, i64, i64, i32, vp, i32, vp, i32]
-    L.rc_onehot_from_code_blocks.argtypes = [vp, i64, i64, i32, vp, i32, i32, i64, i64, vp]
-    L.rc_expand_children.argtypes = [vp, i64, i64, i32, vp, vp, vp, i64, vp]
-    L.rc_expand_children_ex.argtypes = [vp, i64, i64, i32, vp, vp, vp, i64, vp, i32]
-    L.rc_adi_generate.argtypes = [u64, u64, i64, i64, i32, i32, i64, vp, vp, vp, vp, vp, vp, vp, vp]
-    L.rc_adi_generate_ex.argtypes = [u64, u64, i64, i64, i32, i32, i64, vp, vp, vp, vp, vp, vp, vp, vp, i32]
-    L.rc_adi_generate_family.argtypes = [u64, u64, i64, i64, i32, i32, i64, vp, vp, vp, vp, vp, vp, i32]
-    L.rc_family_layout.argtypes = [i32, vp, vp]
-    L.rc_onehot_from_family.argtypes = [vp, i64, i64, i32, vp, i32, i64, vp]
-    L.rc_adi_targets.argtypes = [vp, vp, vp, vp, i64, i64, i32, vp, vp, vp, vp]
-    L.rc_adi_targets_depths.argtypes = [vp, i64, i64, vp, i64, vp, i64, vp, i64, i32, i32, vp, vp, vp, i64, vp]
-    L.rc_onehot_from_family_depths.argtypes = [vp, i64, i64, i32, vp, i32, i64, i32, vp]
-    L.rc_legacy_scramble_actions_ex.argtypes = [vp, vp, i32, i32, i64, i32, vp, i64, vp, i32]
-    L.rc_read_status.argtypes = [vp, vp]
-    L.rc_describe_dispatch.argtypes = [i32, i32, i64, i32, ctypes.c_uint32, i32, i32, ctypes.c_char_p, i32]
-    L.rc_facade_release.argtypes = [vp]
-    L.rc_host_alias.argtypes = [vp, vp]
-    L.rc_scramble_from.argtypes = [vp, vp, i64, i64, i32, i32, u64, u64, i64, vp, vp, i64, vp, vp, vp]
-    L.rc_search_pack.argtypes = [vp, vp, vp, i64, i64, i32, vp, vp, vp, vp]
-    for name in ("rc_init", "rc_get_tables", "rc_fill_solved", "rc_apply_moves", "rc_apply_moves_ex", "rc_facade_step", "rc_facade_steps", "rc_facade_expand", "rc_scramble",
-                 "rc_legacy_scramble_actions", "rc_is_solved", "rc_encode", "rc_onehot_from_code", "rc_expand_children",
-                 "rc_expand_children_ex", "rc_adi_generate", "rc_adi_generate_ex", "rc_adi_targets", "rc_read_status",
-                 "rc_describe_dispatch", "rc_facade_release", "rc_onehot_from_code_ex", "rc_apply_moves_ws", "rc_encode_ws", "rc_adi_generate_family", "rc_family_layout",
-                 "rc_onehot_from_family", "rc_adi_targets_depths", "rc_onehot_from_family_depths", "rc_legacy_scramble_actions_ex", "rc_host_alias", "rc_scramble_from", "rc_search_pack", "rc_onehot_from_code_blocks"):
-        getattr(L, name).restype = i32
+vp, i64, i32, u64 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_uint64
+# every function of include/rubikhip.h, once: argument types, or (argument types, result type) where the result is not a C int
+SIGNATURES = {
+    "rc_version": [],
+    "rc_build_id": ([], ctypes.c_char_p),
+    "rc_last_error": ([], ctypes.c_char_p),
+    "rc_init": [i32],
+    "rc_get_tables": [i32, vp, vp, vp, vp, vp, vp, vp],
+    "rc_fill_solved": [vp, i64, i64, i32, vp],
+    "rc_apply_moves": [vp, vp, vp, i64, i64, i64, i32, vp, vp, vp, i32, i64, vp],
+    "rc_apply_moves_ex": [vp, vp, vp, i64, i64, i64, i32, vp, vp, vp, i32, i64, vp, i32],
+    "rc_apply_moves_ws": [vp, vp, vp, i64, i64, i64, i32, vp, vp, vp, i32, i64, vp, i64, vp],
+    "rc_encode_ws": [vp, i64, i64, i32, vp, i32, i64, vp, i64, vp],
+    "rc_workspace_bytes": ([i32, i32, i64, i32], i64),
+    "rc_facade_step": [vp, i64, i32, i32, vp, ctypes.c_uint32, i32, vp],
+    "rc_facade_steps": [vp, i64, i32, vp, i32, vp, ctypes.c_uint32, i32, vp],
+    "rc_facade_expand": [vp, i64, i32, vp, ctypes.c_uint32, i32, i32, vp],
+    "rc_scramble": [vp, i64, i64, i32, i32, u64, u64, i64, vp, vp, i64, vp, vp, vp],
+    "rc_legacy_scramble_actions": [vp, vp, i32, i32, i64, i32, vp, i64, vp],
+    "rc_is_solved": [vp, i64, i64, i32, vp, vp, vp],
+    "rc_encode": [vp, i64, i64, i32, vp, i32, i64, vp],
+    "rc_onehot_from_code": [vp, i64, i64, i32, vp, i32, vp],
+    "rc_onehot_from_code_ex": [vp, i64, i64, i32, vp, i32, vp, i32],
+    "rc_onehot_from_code_blocks": [vp, i64, i64, i32, vp, i32, i32, i64, i64, vp],
+    "rc_expand_children": [vp, i64, i64, i32, vp, vp, vp, i64, vp],
+    "rc_expand_children_ex": [vp, i64, i64, i32, vp, vp, vp, i64, vp, i32],
+    "rc_adi_generate": [u64, u64, i64, i64, i32, i32, i64, vp, vp, vp, vp, vp, vp, vp, vp],
+    "rc_adi_generate_ex": [u64, u64, i64, i64, i32, i32, i64, vp, vp, vp, vp, vp, vp, vp, vp, i32],
+    "rc_adi_generate_family": [u64, u64, i64, i64, i32, i32, i64, vp, vp, vp, vp, vp, vp, i32],
+    "rc_family_layout": [i32, vp, vp],
+    "rc_onehot_from_family": [vp, i64, i64, i32, vp, i32, i64, vp],
+    "rc_adi_targets": [vp, vp, vp, vp, i64, i64, i32, vp, vp, vp, vp],
+    "rc_adi_targets_depths": [vp, i64, i64, vp, i64, vp, i64, vp, i64, i32, i32, vp, vp, vp, i64, vp],
+    "rc_onehot_from_family_depths": [vp, i64, i64, i32, vp, i32, i64, i32, vp],
+    "rc_legacy_scramble_actions_ex": [vp, vp, i32, i32, i64, i32, vp, i64, vp, i32],
+    "rc_read_status": [vp, vp],
+    "rc_describe_dispatch": [i32, i32, i64, i32, ctypes.c_uint32, i32, i32, ctypes.c_char_p, i32],
+    "rc_facade_release": [vp],
+    "rc_host_alias": [vp, vp],
+    "rc_scramble_from": [vp, vp, i64, i64, i32, i32, u64, u64, i64, vp, vp, i64, vp, vp, vp],
+    "rc_search_pack": [vp, vp, vp, i64, i64, i32, vp, vp, vp, vp],
+}
 
 
 def lib():
     """The loaded library (loads on first use).  Raises if it was not built."""
-    global _lib
-    if _lib is None:
-        with _lock:
-            if _lib is None:
-                if not os.path.exists(LIB_PATH):
-                    raise RubikHipError(
-                        f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
-                        "(hipcc --offload-arch=gfx950). There is no CPU fallback.")
-                L = ctypes.CDLL(LIB_PATH)
-                if not hasattr(L, "rc_build_id"):
-                    raise RubikHipError(f"{LIB_PATH} predates rc_build_id (ABI < 600): rebuild it with __graft_entry__.build()")
-                _declare(L)
-                from . import _build
-                try:                                                 # the binary must be the tree's sources (RC_ALLOW_STALE=1: A/B experiments)
-                    _build.check_loaded(LIB_PATH, L.rc_build_id().decode(), _build.HIP_SOURCES)
-                except RuntimeError as e:
-                    raise RubikHipError(str(e)) from None
-                _lib = L
-    return _lib
+    return _native.load("hip", SIGNATURES)
 
 
 def build_id() -> str:
     """The source hash the loaded library was built from (rc_build_id)."""
-    return lib().rc_build_id().decode()
+    return _native.build_id("hip", lib())
 
 
 def check(rc):
     if rc != 0:
-        raise RubikHipError(f"librubikhip error {rc}: {lib().rc_last_error().decode()}")
+        raise _native.error("hip", lib(), rc)
 
 
 def init(device: torch.device):

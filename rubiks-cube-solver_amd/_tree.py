@@ -1,41 +1,41 @@
 """ctypes binding of librubiktree.so (include/rubiktree.h): the host-side trees of the lockstep search.
 
-Built by __graft_entry__.build() with g++ (no GPU code).  Like _lib.py there is no silent fallback: if the library is
-missing, tree() raises."""
+Built by __graft_entry__.build() with g++ (no GPU code) and loaded by _native.load without torch.  Like _lib.py there is no silent
+fallback: if the library is missing or stale, tree_lib() raises."""
 from __future__ import annotations
 
 import ctypes
 import os
+from ctypes import c_double as dbl, c_int as i32, c_void_p as vp
 
 import numpy as np
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("RUBIKTREE_LIB") or os.path.join(_HERE, "librubiktree.so")   # env override: sanitizer builds (tools/sanitize_cpu.sh)
-_lib = None
+from . import _native
+
+LIB_PATH = _native.path("tree")
+SIGNATURES = {
+    "rc_tree_build_id": ([], ctypes.c_char_p),
+    "rc_tree_create": ([i32, i32, i32, dbl, dbl, dbl], vp),
+    "rc_tree_destroy": ([vp], None),
+    "rc_tree_set_threads": [vp, i32],
+    "rc_tree_set_rng": [vp, i32, vp],
+    "rc_tree_get_rng": [vp, vp],
+    "rc_tree_select": [vp],
+    "rc_tree_paths": [vp, vp, i32],
+    "rc_tree_update": [vp, vp, vp, vp, vp, vp],
+    "rc_tree_solution": [vp, i32, vp, i32],
+    "rc_tree_sims_used": [vp, vp],
+    "rc_tree_root_stats": [vp, i32, vp, vp],
+}
 
 
 def tree_lib():
-    global _lib
-    if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise RuntimeError(f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'`")
-        L = ctypes.CDLL(LIB_PATH)
-        vp, i32, dbl = ctypes.c_void_p, ctypes.c_int, ctypes.c_double
-        from . import _build
-        L.rc_tree_build_id.restype = ctypes.c_char_p
-        _build.check_loaded(LIB_PATH, L.rc_tree_build_id().decode(), _build.TREE_SOURCES)      # a stale build is refused, not used
-        L.rc_tree_create.restype = vp
-        L.rc_tree_create.argtypes = [i32, i32, i32, dbl, dbl, dbl]
-        L.rc_tree_destroy.argtypes = [vp]
-        L.rc_tree_destroy.restype = None
-        for name, args in (("rc_tree_set_threads", [vp, i32]), ("rc_tree_set_rng", [vp, i32, vp]), ("rc_tree_get_rng", [vp, vp]), ("rc_tree_select", [vp]),
-                           ("rc_tree_paths", [vp, vp, i32]), ("rc_tree_update", [vp, vp, vp, vp, vp, vp]),
-                           ("rc_tree_solution", [vp, i32, vp, i32]), ("rc_tree_sims_used", [vp, vp]),
-                           ("rc_tree_root_stats", [vp, i32, vp, vp])):
-            f = getattr(L, name)
-            f.argtypes, f.restype = args, i32
-        _lib = L
-    return _lib
+    return _native.load("tree", SIGNATURES)
+
+
+def build_id() -> str:
+    """The source hash the loaded library was built from (rc_tree_build_id)."""
+    return _native.build_id("tree", tree_lib())
 
 
 def cpu_share():

