@@ -53,6 +53,7 @@ class CubeEnv(_EnvBase):
         self._fast = None  # pinned result buffer + cached call arguments of the facade step path
         self._adi_plans = {}  # get_random_samples: static buffers (and, with adi_graph, the captured hipGraph) per call shape
         self.adi_graph = False  # True: get_random_samples replays its one-hot -> net -> targets body as a hipGraph (adi.AdiPlan)
+        self.adi_front = "dense"  # "codes": get_random_samples sums the net's first layer from the compact codes (adi.AdiPlan front="codes")
         self.init_state()
 
     def _make_vec(self, compute_device):
@@ -238,7 +239,7 @@ class CubeEnv(_EnvBase):
             # about 150 MB at 200 x 30, held until close()).  The plan freezes the dtype the net computes in and where its parameters
             # live, so both are part of the key: after an in-place model.half() / model.to(...) the next call builds a new plan
             key = (id(model), sample_scramble_count, sample_cube_count, float(temperature), not tensor_sink, bool(self.adi_graph),
-                   str(_module_dtype(model)), str(_module_device(model, None)))
+                   str(_module_dtype(model)), str(_module_device(model, None)), self.adi_front)
             plan = self._adi_plans.get(key)
             if plan is None or plan.model is not model:
                 self._adi_plans.clear()
@@ -260,7 +261,7 @@ class CubeEnv(_EnvBase):
         """The device plan behind get_random_samples (adi.AdiPlan: generator launch, one-hot blocks, the caller's net, target assembly)."""
         from .adi import AdiPlan
         return AdiPlan(model, self.cube_size, n_walks, depth, temperature, device=self._vec.device, model_device=self.device,
-                       want_state_dense=want_state_dense, graph=bool(self.adi_graph))
+                       want_state_dense=want_state_dense, graph=bool(self.adi_graph), front=self.adi_front)
 
     def get_target_value(self, model, scramble_count, temperature):
         """(target_value, target_policy, error) of the CURRENT state (cube_env.py:196-252)."""
