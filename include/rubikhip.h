@@ -17,7 +17,15 @@
  *     tiles need a power-of-two pitch >= 512 (the widest wave span); 16384-32768 measured best on MI355X at 4M cubes
  *     (+12..24 % HBM throughput over one 4M-wide tile: every wave's 54 row segments then sit
  *     within 54 * pitch bytes).  RC_FMT_CODE buffers are tiled the same way with SLOTS rows.
- *     Buffers described as "plain" below are one tile.  Base pointers are 16-byte aligned.
+ *     Buffers described as "plain" below are one tile.
+ *   - Alignment.  Every device pointer that a kernel reads or writes in packs must be 16-byte aligned, and 16 bytes is all it
+ *     needs (a buffer carved 16 bytes into a larger allocation is fine): state / code / family buffers, children, child_code,
+ *     child_solved, dense one-hots, workspaces, the uint8 per-cube arrays `actions`, `actions_in`, `actions_out` and `done` (one
+ *     4- or 8-byte pack per lane) and `reward` (float4 stores).  A pointer that breaks the rule is RC_EINVAL before anything is
+ *     launched; the message names the operand.  Arrays that are only indexed element by element need the NATURAL alignment of
+ *     their element type and nothing more: rc_legacy_scramble_actions seeds / counts, rc_adi_targets* child_value / child_solved /
+ *     parent_value / weight / target_value / target_policy / error, and every operand of rc_search_pack (bytes).  The facade's
+ *     `st` is read one sticker per lane (natural); its host_out has its own 512-byte contract.
  *   - actions are uint8 in the env's action order U,U',F,F',R,R'[,D,D',B,B',L,L']
  *     (gym-cube/gym_cube/envs/cube_env.py:24-28); A = 12 | 6.
  *   - `stream` is a hipStream_t passed as void* (NULL = the default stream).  Calls are
@@ -102,7 +110,8 @@ int rc_fill_solved(uint8_t *st, int64_t n_cubes, int64_t pitch, int cube_size, v
  * done[n] = solved, reward[n] = done ? +1.0f : -1.0f, and the one-hot of the NEW state.
  * `out` may alias `in` (in-place); reward, done, onehot may be NULL (onehot NULL requires
  * fmt RC_FMT_NONE).  code_pitch is the row pitch of an RC_FMT_CODE buffer (ignored for
- * dense formats).  Replaces CubeEnv.step (cube_env.py:71-111) = doMove_3 (py333.py:220-222)
+ * dense formats).  RC_EINVAL: a NULL or not 16-byte aligned in / out / actions, a reward, done or onehot that is not 16-byte
+ * aligned, a bad pitch, fmt or cube_size, onehot and fmt that disagree.  Replaces CubeEnv.step (cube_env.py:71-111) = doMove_3 (py333.py:220-222)
  * + sim_state_to_state (cube_env.py:132-152) + isSolved_3 (py333.py:229-233). */
 int rc_apply_moves(const uint8_t *in, uint8_t *out, const uint8_t *actions, int64_t n_cubes,
                    int64_t pitch_in, int64_t pitch_out, int cube_size, float *reward,
@@ -165,7 +174,9 @@ int rc_host_alias(const void *host, void **device_alias);
  * (cube_env.py:65-67) for n_cubes cubes at once.  actions_in[d * act_pitch + n] replays given
  * moves (e.g. the host's legacy-numpy draws, for bit-exact reset(seed)); NULL draws them on
  * the device exactly like rc_adi_generate (walk = walk_offset + n).  actions_out (same layout,
- * NULL to skip) receives the moves used.  done/reward (NULL to skip) describe the final state. */
+ * NULL to skip) receives the moves used.  done/reward (NULL to skip) describe the final state.
+ * RC_EINVAL: a NULL or not 16-byte aligned st (src), an actions_in, actions_out, done or reward that is not 16-byte aligned, a bad
+ * pitch / act_pitch / cube_size, negative n_cubes or depth. */
 int rc_scramble(uint8_t *st, int64_t n_cubes, int64_t pitch, int cube_size, int depth, uint64_t seed,
                 uint64_t stream_id, int64_t walk_offset, const uint8_t *actions_in, uint8_t *actions_out,
                 int64_t act_pitch, uint8_t *done, float *reward, void *stream);
@@ -200,7 +211,8 @@ int rc_legacy_scramble_actions_ex(const uint32_t *seeds, const int32_t *counts, 
                                   int64_t n_envs, int cube_size, uint8_t *actions_out, int64_t pitch,
                                   void *stream, int variant);
 
-/* done / reward of the given states, no move.  Replaces isSolved_3 (py333.py:229-233). */
+/* done / reward of the given states, no move (at least one of them; each 16-byte aligned, else RC_EINVAL).  Replaces isSolved_3
+ * (py333.py:229-233). */
 int rc_is_solved(const uint8_t *st, int64_t n_cubes, int64_t pitch, int cube_size,
                  uint8_t *done, float *reward, void *stream);
 

@@ -1701,6 +1701,9 @@ static int step_common(const uint8_t *in, uint8_t *out, const uint8_t *actions, 
     if (!in || !aligned16(in) || n < 0 || sh_in < 0) return fail(RC_EINVAL, "bad input state buffer / pitch%s");
     if (store && (!out || !aligned16(out) || sh_out < 0)) return fail(RC_EINVAL, "bad output state buffer / pitch%s");
     if (move && !actions) return fail(RC_EINVAL, "actions is NULL%s");
+    // actions and done are read / written one pack (4 or 8 bytes) per lane: the header's 16-byte rule holds for them like for the rows
+    if (move && !aligned16(actions)) return fail(RC_EINVAL, "actions must be 16-byte aligned%s");
+    if (done && !aligned16(done)) return fail(RC_EINVAL, "done must be 16-byte aligned%s");
     if (reward && (reinterpret_cast<uintptr_t>(reward) & 15u)) return fail(RC_EINVAL, "reward must be 16-byte aligned%s");
     if (int rc = check_fmt(onehot, fmt, code_pitch, n, &sh_code)) return rc;
     if (n == 0) return RC_OK;
@@ -1778,6 +1781,7 @@ int rc_scramble_from(const uint8_t *src, uint8_t *stp, int64_t n, int64_t pitch,
     if (!stp || !aligned16(stp) || !src || !aligned16(src) || n < 0 || depth < 0 || sh < 0) return fail(RC_EINVAL, "rc_scramble: bad state buffer / pitch%s");
     if ((actions_in || actions_out) && bad_pitch(act_pitch, n)) return fail(RC_EINVAL, "rc_scramble: bad act_pitch%s");
     if ((actions_in && !aligned16(actions_in)) || (actions_out && !aligned16(actions_out))) return fail(RC_EINVAL, "rc_scramble: action buffers must be 16-byte aligned%s");
+    if (done && !aligned16(done)) return fail(RC_EINVAL, "rc_scramble: done must be 16-byte aligned%s");
     if (reward && (reinterpret_cast<uintptr_t>(reward) & 15u)) return fail(RC_EINVAL, "reward must be 16-byte aligned%s");
     if (n == 0) return RC_OK;
     return by_size(cube_size, [&](auto t) {

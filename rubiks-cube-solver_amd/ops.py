@@ -88,11 +88,15 @@ def alloc_code(n, cube_size, device, pitch=None):
     return torch.empty((tiles, SL, pitch), dtype=torch.uint8, device=device)
 
 
-def _vec(t, n, dtype, what):
+def _vec(t, n, dtype, what, out=False):
+    """[n] array.  out: an output the kernel writes in packs -- it must start 16-byte aligned (include/rubikhip.h "Alignment"), and an
+    output cannot be realigned behind the caller's back, so a misaligned one (a slice of a larger tensor) is an error."""
     if t is None:
         return None
     if t.dtype != dtype or not t.is_cuda or not t.is_contiguous() or t.numel() < n:
         raise RubikHipError(f"{what}: need a contiguous {dtype} HIP tensor with >= {n} elements")
+    if out and t.data_ptr() % 16:
+        raise RubikHipError(f"{what}: output tensor must start 16-byte aligned (a slice at an odd offset?): write into a tensor of its own")
     return t
 
 
@@ -164,8 +168,10 @@ def apply_moves(src, dst, actions, n, cube_size, reward=None, done=None, onehot=
     S, _, _ = _size(cube_size)
     p_in, p_out = _tiled(src, S, n, "apply_moves src"), _tiled(dst, S, n, "apply_moves dst")
     _vec(actions, n, torch.uint8, "actions")
-    _vec(reward, n, torch.float32, "reward")
-    _vec(done, n, torch.uint8, "done")
+    if actions.data_ptr() % 16:
+        actions = actions.clone()                  # an input slice at an odd offset: one copy into a fresh (aligned) tensor, capture-safe
+    _vec(reward, n, torch.float32, "reward", out=True)
+    _vec(done, n, torch.uint8, "done", out=True)
     oh, cp = _onehot_args(onehot, fmt, n, cube_size, "apply_moves")
     _lib.init(src.device)
     if variant:
@@ -208,8 +214,8 @@ def scramble(st, n, cube_size, depth, seed=0, stream_id=0, walk_offset=0, action
         if actions_in is not None and ap2 != ap:
             raise RubikHipError("scramble: actions_in and actions_out must share one pitch")
         ap = ap2
-    _vec(reward, n, torch.float32, "reward")
-    _vec(done, n, torch.uint8, "done")
+    _vec(reward, n, torch.float32, "reward", out=True)
+    _vec(done, n, torch.uint8, "done", out=True)
     _lib.init(st.device)
     if src is not None:
         check(lib().rc_scramble_from(ptr(src), ptr(st), n, pitch, cube_size, depth, seed, stream_id, walk_offset, a_in,
@@ -267,8 +273,8 @@ def legacy_scramble_actions(seeds, cube_size, scramble_count, device=None, varia
 def is_solved(st, n, cube_size, done=None, reward=None):
     S, _, _ = _size(cube_size)
     pitch = _tiled(st, S, n, "is_solved")
-    _vec(reward, n, torch.float32, "reward")
-    _vec(done, n, torch.uint8, "done")
+    _vec(reward, n, torch.float32, "reward", out=True)
+    _vec(done, n, torch.uint8, "done", out=True)
     _lib.init(st.device)
     check(lib().rc_is_solved(ptr(st), n, pitch, cube_size, ptr(done), ptr(reward), stream_ptr(st.device)))
 

@@ -1,0 +1,724 @@
+"""Memory layout promises of include/rubikhip.h on the device.  GPU only.
+
+  A  one tiling per operand: every entry point with more than one layout parameter (pitch_in / pitch_out / code_pitch / act_pitch) is
+     run with every ordered combination of the four layouts of tests/layout_cases.py (tight, padded, 512- and 1024-cube tiles) at
+     n = 513, 1029, 2565, both cube sizes, every pack width / policy / form of the tuning override -- a kernel that addressed one
+     operand with another operand's pitch or tile shift fails (tests/test_layouts_host.py::test_teeth proves that it must);
+  B  every pointer at the contract's minimum alignment: each launching entry point once with EVERY device pointer carved 16 bytes
+     past a 32-byte boundary of a larger allocation;
+  C  misaligned `actions` / `done` never reach a kernel: RC_EINVAL from the C ABI, a copy (inputs) or an error (outputs) from ops.
+
+Every comparison is exact, against the oracle in [n, rows] form (the beam and net libraries: against tests/beam_ref.py and
+tests/net_ref.py), over cubes < n only, and every test ends with a clean status word."""
+import ctypes
+import os
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import layout_cases as C  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda"
+S_OF, A_OF, SL_OF, RC_OF = C.S_OF, C.A_OF, C.SL_OF, C.RC_OF
+
+
+@pytest.fixture(scope="module")
+def ops():
+    from rubiks_cube_solver_amd import ops as o
+    return o
+
+
+@pytest.fixture(scope="module")
+def L():
+    from rubiks_cube_solver_amd import _lib
+    return _lib
+
+
+# ------------------------------------------------------------------------------------------------------------------ helpers
+def dev(a):
+    return torch.as_tensor(np.ascontiguousarray(a)).to(DEV)
+
+
+def put(ops, aos, name, n):
+    """[n, rows] host array -> device buffer in layout `name`"""
+    buf = ops.from_aos(aos, DEV, C.layout(name, n)[0])
+    assert tuple(buf.shape) == C.shape(name, n, aos.shape[1])
+    return buf
+
+
+def fresh(name, n, rows, lead=()):
+    tiles, rows, pitch = C.shape(name, n, rows)
+    return torch.full((*lead, tiles, rows, pitch), 0xEE, dtype=torch.uint8, device=DEV)
+
+
+def same(ops, buf, n, want):
+    """tiled buffer [tiles, rows, pitch] == [n, rows] device tensor, cubes < n only"""
+    return torch.equal(ops.to_aos(buf, n), want)
+
+
+def same_lead(ops, buf, n, want):
+    """[A, tiles, rows, pitch] == [n, A, rows]"""
+    return all(same(ops, buf[a], n, want[:, a]) for a in range(buf.shape[0]))
+
+
+def dense_of(cs, code):
+    """oracle-side dense one-hot from codes (uint8 [n, R, C])"""
+    n = len(code)
+    R, Cc = RC_OF[cs]
+    oh = np.zeros((n, R, Cc), np.uint8)
+    idx = np.arange(n)
+    for slot in range(SL_OF[cs]):
+        c = code[:, slot].astype(np.int64)
+        if cs == 3:
+            oh[idx, slot, c] = 1
+        else:
+            oh[idx, c // 3, slot * 3 + c % 3] = 1
+    return oh
+
+
+def dense_buf(L, n, cs, fmt_name):
+    fmt = getattr(L, "FMT_" + fmt_name)
+    return fmt, torch.full((n, *RC_OF[cs]), 3, dtype=L.dense_dtype(fmt), device=DEV)
+
+
+def same_dense(oh, want_u8):
+    return torch.equal(oh.float(), want_u8.float())                # 0 and 1 are exact in every format
+
+
+_REF = {}
+
+
+def ref(oracle, cs, n):
+    """The shared reference of one (cube size, n): computed once, never written.  Input states are oracle random walks whose first
+    n // 5 cubes are one move from solved, so that done / reward / the child flags take both values."""
+    if (cs, n) in _REF:
+        return _REF[cs, n]
+    A = A_OF[cs]
+    rng = np.random.default_rng(1000 * cs + n)
+    walks = rng.integers(0, A, (n, 17), dtype=np.uint8)
+    states = oracle.adi(cs, n, 17, actions_in=walks, want_children=False, threads=4)["parents"][:, -1].copy()
+    acts = rng.integers(0, A, n, dtype=np.uint8)
+    k = n // 5
+    states[:k] = oracle.step(cs, oracle.solved(cs, k), acts[:k] ^ 1)[0]
+    st, code, done, rew = oracle.step(cs, states, acts, threads=4)
+    assert done[:k].all() and not done.all() and (rew[:k] == 1.0).all() and (rew == -1.0).any()
+    code_o, oh = oracle.encode(cs, st)
+    assert (code_o == code).all() and (oh == dense_of(cs, code)).all()
+    ch, cc, cso = oracle.expand(cs, states, threads=4)
+    assert cso.any() and not cso.all()
+    r = dict(states=states, acts=acts, st=st, code=code, done=done.astype(np.uint8), rew=rew.astype(np.float32), oh=oh, ch=ch, cc=cc,
+             cso=cso.astype(np.uint8))
+    r.update({"d_" + key: dev(v) for key, v in list(r.items())})
+    _REF[cs, n] = r
+    return r
+
+
+# =================================================================================================== A. one tiling per operand
+@pytest.mark.parametrize("cs", C.CUBE_SIZES)
+@pytest.mark.parametrize("n", C.SIZES)
+def test_step_with_code_every_triple(ops, L, oracle, cs, n):
+    """rc_apply_moves_ex + compact code: every ordered triple (in, out, code) for pack 1 and 2, every other row policy on a triple of
+    three different layouts, in place with the code in every other layout: stickers, code, done, reward."""
+    R = ref(oracle, cs, n)
+    S, SL = S_OF[cs], SL_OF[cs]
+    srcs = {name: put(ops, R["states"], name, n) for name in C.LAYOUTS}
+    for li, lo, lc, variant, in_place in C.step_code_cases():
+        C.check_premise(n, li, lo, lc)
+        if in_place:
+            assert lo == li and lc != li and C.all_differ(n, li, lc)
+        if variant >= 10:
+            assert C.all_differ(n, li, lo, lc)
+        src = srcs[li].clone() if in_place else srcs[li]
+        dst = src if in_place else fresh(lo, n, S)
+        code = fresh(lc, n, SL)
+        rew = torch.zeros(n, dtype=torch.float32, device=DEV)
+        done = torch.full((n,), 7, dtype=torch.uint8, device=DEV)
+        ops.apply_moves(src, dst, R["d_acts"], n, cs, rew, done, code, L.FMT_CODE, variant=variant)
+        tag = (li, lo, lc, variant, in_place)
+        assert same(ops, dst, n, R["d_st"]), tag
+        assert same(ops, code, n, R["d_code"]), tag
+        assert torch.equal(done, R["d_done"]) and torch.equal(rew, R["d_rew"]), tag
+        if not in_place:
+            assert same(ops, src, n, R["d_states"]), tag            # the input is left alone
+    assert L.read_status() == 0
+
+
+@pytest.mark.parametrize("cs", C.CUBE_SIZES)
+@pytest.mark.parametrize("fmt_name", C.DENSE)
+@pytest.mark.parametrize("n", C.SIZES)
+def test_step_with_dense_onehot_every_pair(ops, L, oracle, cs, fmt_name, n):
+    """rc_apply_moves_ex + dense one-hot: every ordered (in, out), both fused tile forms, every format (the 2x2x2 has 320- and
+    640-thread writers of its own)."""
+    R = ref(oracle, cs, n)
+    srcs = {name: put(ops, R["states"], name, n) for name in C.LAYOUTS}
+    for li, lo, variant in C.step_dense_cases():
+        C.check_premise(n, li, lo)
+        dst = fresh(lo, n, S_OF[cs])
+        fmt, oh = dense_buf(L, n, cs, fmt_name)
+        rew = torch.zeros(n, dtype=torch.float32, device=DEV)
+        done = torch.full((n,), 7, dtype=torch.uint8, device=DEV)
+        ops.apply_moves(srcs[li], dst, R["d_acts"], n, cs, rew, done, oh, fmt, variant=variant)
+        tag = (li, lo, variant)
+        assert same(ops, dst, n, R["d_st"]), tag
+        assert same_dense(oh, R["d_oh"]), tag
+        assert torch.equal(done, R["d_done"]) and torch.equal(rew, R["d_rew"]), tag
+    assert L.read_status() == 0
+
+
+def workspace_reference(oracle):
+    w = C.WORKSPACE_CASE
+    key = ("ws", w["n"])
+    if key not in _REF:
+        cs, n = w["cs"], w["n"]
+        rng = np.random.default_rng(n)
+        walks = rng.integers(0, 12, (n, 11), dtype=np.uint8)
+        states = oracle.adi(cs, n, 11, actions_in=walks, want_children=False, threads=8)["parents"][:, -1].copy()
+        acts = rng.integers(0, 12, n, dtype=np.uint8)
+        k = n // 5
+        states[:k] = oracle.step(cs, oracle.solved(cs, k), acts[:k] ^ 1, threads=8)[0]
+        st, code, done, rew = oracle.step(cs, states, acts, threads=8)
+        _REF[key] = dict(states=states, d_acts=dev(acts), d_st=dev(st), d_code=dev(code), d_done=dev(done.astype(np.uint8)),
+                         d_rew=dev(rew.astype(np.float32)))
+    return _REF[key]
+
+
+def same_dense_as_code(oh, d_code):
+    """3x3x3 dense one-hot == one_hot(code) on the device"""
+    return torch.equal(oh.to(torch.uint8), torch.nn.functional.one_hot(d_code.long(), 24).to(torch.uint8))
+
+
+def test_step_workspace_route_tiled_in_one_tile_out(ops, L, oracle):
+    """The two-launch route of rc_apply_moves_ws (step + code into the 32768-tile workspace, then the front writer): 3x3x3, bf16,
+    n = 2^17 + 5, `in` in 512-cube tiles, `out` one tile."""
+    w = C.WORKSPACE_CASE
+    cs, n = w["cs"], w["n"]
+    R = workspace_reference(oracle)
+    C.check_premise(n, w["lin"], w["lout"])
+    assert C.layout(w["lin"], n) == (512, 257) and C.layout(w["lout"], n) == (n + 11, 1)
+    fmt = getattr(L, "FMT_" + w["fmt"])
+    d = L.describe(L.OP_STEP, cs, n, outputs=L.OUT_STATES | L.OUT_WORKSPACE, fmt=fmt)
+    assert d.startswith("k_step<Cube3") and "code" in d and "+ k_code_to_dense_front<Cube3,bf16" in d, d
+    assert L.lib().rc_workspace_bytes(L.OP_STEP, cs, n, fmt) == 5 * 32768 * 20
+    src = put(ops, R["states"], w["lin"], n)
+    dst = fresh(w["lout"], n, 54)
+    oh = torch.full((n, 20, 24), 3, dtype=torch.bfloat16, device=DEV)
+    rew = torch.zeros(n, dtype=torch.float32, device=DEV)
+    done = torch.full((n,), 7, dtype=torch.uint8, device=DEV)
+    ops.apply_moves(src, dst, R["d_acts"], n, cs, rew, done, oh, fmt)              # variant 0 with a dense fmt: rc_apply_moves_ws
+    assert same(ops, dst, n, R["d_st"])
+    assert same_dense_as_code(oh, R["d_code"])
+    assert torch.equal(done, R["d_done"]) and torch.equal(rew, R["d_rew"])
+    assert L.read_status() == 0
+
+
+@pytest.mark.parametrize("cs", C.CUBE_SIZES)
+@pytest.mark.parametrize("n", C.SIZES)
+def test_encode_and_is_solved_every_pair(ops, L, oracle, cs, n):
+    """rc_encode: state layout x code layout and x every dense format; rc_is_solved: every state layout."""
+    R = ref(oracle, cs, n)
+    srcs = {name: put(ops, R["st"], name, n) for name in C.LAYOUTS}
+    for ls, what in C.encode_cases():
+        if what in C.LAYOUTS:
+            C.check_premise(n, ls, what)
+            code = fresh(what, n, SL_OF[cs])
+            ops.encode(srcs[ls], n, cs, code, L.FMT_CODE)
+            assert same(ops, code, n, R["d_code"]), (ls, what)
+        elif what in C.DENSE:
+            C.check_premise(n, ls)
+            fmt, oh = dense_buf(L, n, cs, what)
+            ops.encode(srcs[ls], n, cs, oh, fmt)
+            assert same_dense(oh, R["d_oh"]), (ls, what)
+        else:
+            C.check_premise(n, ls)
+            rew = torch.zeros(n, dtype=torch.float32, device=DEV)
+            done = torch.full((n,), 7, dtype=torch.uint8, device=DEV)
+            ops.is_solved(srcs[ls], n, cs, done, rew)
+            assert torch.equal(done, R["d_done"]) and torch.equal(rew, R["d_rew"]), ls
+    assert L.read_status() == 0
+
+
+@pytest.mark.parametrize("cs", C.CUBE_SIZES)
+@pytest.mark.parametrize("n", C.SIZES)
+def test_expand_children_every_pair(ops, L, oracle, cs, n):
+    """rc_expand_children_ex: every ordered (in, output tiling); children + codes + flags and flags alone for pack 1 / 2 x parts
+    1 / 3 / A with the streaming form excluded; the streaming form forced (children + flags, the only outputs it serves)."""
+    R = ref(oracle, cs, n)
+    S, A, SL = S_OF[cs], A_OF[cs], SL_OF[cs]
+    assert L.describe(L.OP_EXPAND, cs, n, outputs=L.OUT_STATES | L.OUT_FLAGS, variant=100).startswith("k_expand_stream<")
+    assert L.describe(L.OP_EXPAND, cs, n, outputs=L.OUT_STATES | L.OUT_FLAGS, variant=102).startswith("k_expand_stream<")
+    assert L.describe(L.OP_EXPAND, cs, n, outputs=L.OUT_STATES | L.OUT_FLAGS, variant=802).startswith("k_expand<")
+    srcs = {name: put(ops, R["states"], name, n) for name in C.LAYOUTS}
+    for li, lo, base, parts, outputs in C.expand_cases():
+        C.check_premise(n, li, lo)
+        pitch, tiles = C.layout(lo, n)
+        want_ch, want_fl, want_cc = C.EXPAND_OUTPUTS[outputs]
+        children = fresh(lo, n, S, (A,)) if want_ch else None
+        code = fresh(lo, n, SL, (A,)) if want_cc else None
+        flags = torch.full((A, tiles * pitch), 0xEE, dtype=torch.uint8, device=DEV)
+        ops.expand_children(srcs[li], n, cs, children, flags, code, pitch=pitch, variant=C.expand_variant(base, parts, A))
+        tag = (li, lo, base, parts, outputs)
+        assert torch.equal(flags[:, :n].T, R["d_cso"]), tag
+        if want_ch:
+            assert same_lead(ops, children, n, R["d_ch"]), tag
+        if want_cc:
+            assert same_lead(ops, code, n, R["d_cc"]), tag
+    assert L.read_status() == 0
+
+
+@pytest.mark.parametrize("cs", C.CUBE_SIZES)
+@pytest.mark.parametrize("fmt_name", C.DENSE)
+@pytest.mark.parametrize("n", C.SIZES)
+def test_onehot_from_code_every_layout_and_form(ops, L, oracle, cs, fmt_name, n):
+    """rc_onehot_from_code_ex: every code layout x every form check_variant accepts (tile forms 1 / 2, the wide form with and without
+    its skew / group fields, the front form with 1 / 2 / 4 fronts x linear / gather / LDS fetch, and the default-front fields)."""
+    R = ref(oracle, cs, n)
+    codes = {name: put(ops, R["code"], name, n) for name in C.LAYOUTS}
+    for lc, variant in C.code_to_dense_cases():
+        C.check_premise(n, lc)
+        fmt, oh = dense_buf(L, n, cs, fmt_name)
+        ops.onehot_from_code(codes[lc], n, cs, oh, variant=variant)
+        assert same_dense(oh, R["d_oh"]), (lc, variant)
+    assert L.read_status() == 0
+
+
+def scramble_reference(oracle, cs, n):
+    """depth-3 scrambles from random-walk states: `replay` with given actions, `drawn` with the device RNG's draws for (seed 9, stream 1,
+    offset 5) as oracle.adi draws them.  The first n // 5 start states are the inverse walk from solved: they END solved."""
+    key = ("scr", cs, n)
+    if key in _REF:
+        return _REF[key]
+    A, depth, k = A_OF[cs], 3, n // 5
+    rng = np.random.default_rng(77 * cs + n)
+    out = dict(depth=depth, seed=9, stream=1, offset=5)
+    drawn = oracle.adi(cs, n, depth, seed=9, stream=1, walk0=5, want_children=False)["actions"]
+    for mode, acts in (("replay", rng.integers(0, A, (n, depth), dtype=np.uint8)), ("drawn", drawn)):
+        start = ref(oracle, cs, n)["states"].copy()
+        back = oracle.solved(cs, k)
+        for d in reversed(range(depth)):
+            back = oracle.step(cs, back, acts[:k, d] ^ 1)[0]
+        start[:k] = back
+        end = start
+        for d in range(depth):
+            end = oracle.step(cs, end, acts[:, d])[0]
+        done = oracle.is_solved(cs, end)
+        assert done[:k].all() and not done.all()
+        out[mode] = dict(acts=acts, start=start, d_acts=dev(acts), d_start=dev(start), d_end=dev(end), d_done=dev(done),
+                         d_done0=dev(oracle.is_solved(cs, start)))
+    _REF[key] = out
+    return out
+
+
+@pytest.mark.parametrize("cs", C.CUBE_SIZES)
+@pytest.mark.parametrize("n", C.SIZES)
+def test_scramble_every_state_layout_and_act_pitch(ops, L, oracle, cs, n):
+    """rc_scramble / rc_scramble_from: state layout x act_pitch, replayed actions from device memory, device-drawn actions with
+    actions_out, and depth 0 (the copy): final stickers, done, reward, actions_out."""
+    R = scramble_reference(oracle, cs, n)
+    depth = R["depth"]
+    for ls, ap, mode, from_src in C.scramble_cases(n):
+        C.check_premise(n, ls)
+        assert ap % 16 == 0 and ap >= n and ap in (C.ceil16(n), C.ceil16(n) + 32)
+        M = R["replay" if mode == "copy" else mode]
+        start = put(ops, M["start"], ls, n)
+        st = fresh(ls, n, S_OF[cs]) if from_src else start.clone()
+        done = torch.full((n,), 7, dtype=torch.uint8, device=DEV)
+        rew = torch.zeros(n, dtype=torch.float32, device=DEV)
+        kw = dict(done=done, reward=rew, src=start if from_src else None)
+        a_out = None
+        if mode == "replay":
+            a_in = torch.full((depth, ap), A_OF[cs], dtype=torch.uint8, device=DEV)
+            a_in[:, :n] = M["d_acts"].T
+            ops.scramble(st, n, cs, depth, actions_in=a_in, **kw)
+        elif mode == "drawn":
+            a_out = torch.full((depth, ap), 0xEE, dtype=torch.uint8, device=DEV)
+            ops.scramble(st, n, cs, depth, seed=R["seed"], stream_id=R["stream"], walk_offset=R["offset"], actions_out=a_out, **kw)
+        else:
+            ops.scramble(st, n, cs, 0, **kw)
+        tag = (ls, ap, mode, from_src)
+        want_end, want_done = (M["d_start"], M["d_done0"]) if mode == "copy" else (M["d_end"], M["d_done"])
+        assert same(ops, st, n, want_end), tag
+        assert torch.equal(done, want_done) and torch.equal(rew, want_done.float() * 2 - 1), tag
+        if a_out is not None:
+            assert torch.equal(a_out[:, :n].T, M["d_acts"]), tag
+        if from_src:
+            assert same(ops, start, n, M["d_start"]), tag
+    assert L.read_status() == 0
+
+
+# =================================================================================================== B. carved operands
+N_CARVE = 1029
+
+
+class Carver:
+    """carve(shape, dtype): a contiguous view that starts `offset` bytes into a uint8 allocation of offset + nbytes + 64 bytes, with
+    offsets 16, 48, 80, ... in turn: 16-byte aligned, never 32-byte aligned, no two of eight consecutive operands in one phase of 256."""
+
+    def __init__(self):
+        self.count = 0
+
+    def __call__(self, shape, dtype=torch.uint8, fill=0xEE, offset=None):
+        return carve(shape, dtype, self.next_offset() if offset is None else offset, fill)
+
+    def next_offset(self):
+        self.count += 1
+        return C.carve_offsets(self.count)[-1]
+
+    def like(self, t):
+        out = self(tuple(t.shape), t.dtype)
+        out.copy_(t)
+        return out
+
+
+def carve(shape, dtype, offset, fill=0xEE):
+    size = int(np.prod(shape)) * torch.empty((), dtype=dtype).element_size()
+    raw = torch.full((offset + size + 64,), fill, dtype=torch.uint8, device=DEV)
+    view = raw[offset:offset + size].view(dtype).reshape(shape)
+    assert view.is_contiguous() and view.data_ptr() % 16 == 0 and view.data_ptr() % 32 == 16
+    return view
+
+
+P = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())  # noqa: E731
+
+
+@pytest.mark.parametrize("cs", C.CUBE_SIZES)
+def test_carved_fill_step_encode_is_solved(ops, L, oracle, cs):
+    """rc_fill_solved, rc_apply_moves (code and f32), rc_apply_moves_ws at a size without a workspace route, rc_encode, rc_is_solved."""
+    n = N_CARVE
+    R = ref(oracle, cs, n)
+    S, SL = S_OF[cs], SL_OF[cs]
+    cv = Carver()
+    st = cv(C.shape("t512", n, S))
+    ops.fill_solved(st, n, cs)
+    assert same(ops, st, n, dev(oracle.solved(cs, n)))
+    src = cv.like(put(ops, R["states"], "t512", n))
+    dst, code = cv(C.shape("padded", n, S)), cv(C.shape("t1024", n, SL))
+    acts, rew, done = cv.like(R["d_acts"]), cv((n,), torch.float32), cv((n,))
+    C.check_premise(n, "t512", "padded", "t1024")
+    ops.apply_moves(src, dst, acts, n, cs, rew, done, code, L.FMT_CODE)           # variant 0, compact code: rc_apply_moves
+    assert same(ops, dst, n, R["d_st"]) and same(ops, code, n, R["d_code"])
+    assert torch.equal(done, R["d_done"]) and torch.equal(rew, R["d_rew"])
+    dst2, oh, rew2, done2 = cv(C.shape("tight", n, S)), cv((n, *RC_OF[cs]), torch.float32), cv((n,), torch.float32), cv((n,))
+    assert L.lib().rc_workspace_bytes(L.OP_STEP, cs, n, L.FMT_F32) == 0
+    ops.apply_moves(src, dst2, acts, n, cs, rew2, done2, oh, L.FMT_F32)           # no workspace route at this size: rc_apply_moves
+    assert same(ops, dst2, n, R["d_st"]) and same_dense(oh, R["d_oh"])
+    assert torch.equal(done2, R["d_done"]) and torch.equal(rew2, R["d_rew"])
+    dst3, oh3, rew3, done3, ws = cv(C.shape("t1024", n, S)), cv((n, *RC_OF[cs]), torch.float32), cv((n,), torch.float32), cv((n,)), cv((1 << 16,))
+    L.check(L.lib().rc_apply_moves_ws(P(src), P(dst3), P(acts), n, 512, 1024, cs, P(rew3), P(done3), P(oh3), L.FMT_F32, 0, P(ws), ws.numel(),
+                                      L.stream_ptr(torch.device(DEV))))
+    assert same(ops, dst3, n, R["d_st"]) and same_dense(oh3, R["d_oh"])
+    assert torch.equal(done3, R["d_done"]) and torch.equal(rew3, R["d_rew"])
+    code2, oh2 = cv(C.shape("tight", n, SL)), cv((n, *RC_OF[cs]), torch.bfloat16)
+    ops.encode(dst, n, cs, code2, L.FMT_CODE)
+    ops.encode(dst, n, cs, oh2, L.FMT_BF16)
+    assert same(ops, code2, n, R["d_code"]) and same_dense(oh2, R["d_oh"])
+    rew4, done4 = cv((n,), torch.float32), cv((n,))
+    ops.is_solved(dst, n, cs, done4, rew4)
+    assert torch.equal(done4, R["d_done"]) and torch.equal(rew4, R["d_rew"])
+    assert L.read_status() == 0
+
+
+def test_carved_workspace_route(ops, L, oracle):
+    """rc_apply_moves_ws on its two-launch route with every operand carved, the workspace included."""
+    w = C.WORKSPACE_CASE
+    cs, n = w["cs"], w["n"]
+    R = workspace_reference(oracle)
+    fmt = getattr(L, "FMT_" + w["fmt"])
+    need = L.lib().rc_workspace_bytes(L.OP_STEP, cs, n, fmt)
+    assert need > 0
+    cv = Carver()
+    src = cv.like(put(ops, R["states"], w["lin"], n))
+    dst, oh = cv(C.shape(w["lout"], n, 54)), cv((n, 20, 24), torch.bfloat16)
+    acts, rew, done, ws = cv.like(R["d_acts"]), cv((n,), torch.float32), cv((n,)), cv((need,))
+    L.check(L.lib().rc_apply_moves_ws(P(src), P(dst), P(acts), n, src.shape[2], dst.shape[2], cs, P(rew), P(done), P(oh), fmt, 0, P(ws), need,
+                                      L.stream_ptr(torch.device(DEV))))
+    assert same(ops, dst, n, R["d_st"]) and same_dense_as_code(oh, R["d_code"])
+    assert torch.equal(done, R["d_done"]) and torch.equal(rew, R["d_rew"])
+    assert L.read_status() == 0
+
+
+@pytest.mark.parametrize("cs", C.CUBE_SIZES)
+def test_carved_scramble_legacy_actions_expand(ops, L, oracle, cs):
+    """rc_scramble_from, rc_legacy_scramble_actions, rc_expand_children."""
+    n = N_CARVE
+    R, M = ref(oracle, cs, n), scramble_reference(oracle, cs, n)
+    S, A, SL, depth = S_OF[cs], A_OF[cs], SL_OF[cs], M["depth"]
+    cv = Carver()
+    sp = L.stream_ptr(torch.device(DEV))
+    start = cv.like(put(ops, M["drawn"]["start"], "t512", n))
+    st, a_out, done, rew = cv(C.shape("t512", n, S)), cv((depth, C.ceil16(n) + 32)), cv((n,)), cv((n,), torch.float32)
+    ops.scramble(st, n, cs, depth, seed=M["seed"], stream_id=M["stream"], walk_offset=M["offset"], actions_out=a_out, done=done, reward=rew,
+                 src=start)
+    assert same(ops, st, n, M["drawn"]["d_end"]) and torch.equal(a_out[:, :n].T, M["drawn"]["d_acts"])
+    assert torch.equal(done, M["drawn"]["d_done"]) and torch.equal(rew, done.float() * 2 - 1)
+    st2 = cv(C.shape("t512", n, S))
+    ops.scramble(st2, n, cs, depth, actions_in=a_out, src=start)                  # the carved draws replayed
+    assert same(ops, st2, n, M["drawn"]["d_end"])
+    # the reference's reset(seed, k) draws: numpy's legacy generator, per-env counts
+    seeds_np = np.arange(n, dtype=np.int64) * 7919 % (2 ** 31)
+    counts_np = (1 + np.arange(n) % 9).astype(np.int32)
+    kmax, ap = 9, C.ceil16(n) + 48
+    seeds, counts, out = cv.like(dev(seeds_np.astype(np.int32))), cv.like(dev(counts_np)), cv((kmax, ap))
+    L.check(L.lib().rc_legacy_scramble_actions(P(seeds), P(counts), 0, kmax, n, cs, P(out), ap, sp))
+    got = out[:, :n].T.cpu().numpy()
+    saved = np.random.get_state()
+    try:
+        for i in range(0, n, 41):
+            np.random.seed(int(seeds_np[i]))
+            k = int(counts_np[i])
+            assert (got[i, :k] == np.random.randint(A, size=k)).all() and (got[i, k:] == A).all(), i
+    finally:
+        np.random.set_state(saved)
+    src = cv.like(put(ops, R["states"], "padded", n))
+    pitch, tiles = C.layout("t512", n)
+    children, code, flags = cv((A, tiles, S, pitch)), cv((A, tiles, SL, pitch)), cv((A, tiles * pitch))
+    ops.expand_children(src, n, cs, children, flags, code, pitch=pitch)           # variant 0 = rc_expand_children
+    assert same_lead(ops, children, n, R["d_ch"]) and same_lead(ops, code, n, R["d_cc"]) and torch.equal(flags[:, :n].T, R["d_cso"])
+    assert L.read_status() == 0
+
+
+@pytest.mark.parametrize("cs", C.CUBE_SIZES)
+def test_carved_adi_and_code_to_dense(ops, L, oracle, cs):
+    """rc_adi_generate, rc_adi_generate_family, rc_onehot_from_code, rc_onehot_from_code_blocks, rc_onehot_from_family_depths."""
+    n, depth = N_CARVE, 3
+    S, A, SL = S_OF[cs], A_OF[cs], SL_OF[cs]
+    Rr, Cc = RC_OF[cs]
+    key = ("adi", cs, n)
+    if key not in _REF:
+        _REF[key] = oracle.adi(cs, n, depth, seed=2024, stream=3, walk0=11, threads=4)
+    E = _REF[key]
+    cv = Carver()
+    pitch, tiles = C.layout("t512", n)
+    wp = tiles * pitch
+    bufs = dict(actions_out=cv((depth, wp)), parents=cv((depth, tiles, S, pitch)), parent_code=cv((depth, tiles, SL, pitch)),
+                children=cv((depth, A, tiles, S, pitch)), child_code=cv((depth, A, tiles, SL, pitch)), child_solved=cv((depth, A, wp)))
+    ops.adi_generate(n, depth, cs, pitch, DEV, seed=2024, stream_id=3, walk_offset=11, **bufs)
+    assert torch.equal(bufs["actions_out"][:, :n].T, dev(E["actions"]))
+    d_pc, d_cc = dev(E["parent_code"]), dev(E["child_code"])                     # [n, depth, SL], [n, depth, A, SL]
+    for d in range(depth):
+        assert same(ops, bufs["parents"][d], n, dev(E["parents"][:, d]))
+        assert same(ops, bufs["parent_code"][d], n, d_pc[:, d])
+        assert same_lead(ops, bufs["children"][d], n, dev(E["children"][:, d]))
+        assert same_lead(ops, bufs["child_code"][d], n, d_cc[:, d])
+    assert torch.equal(bufs["child_solved"][:, :, :n].permute(2, 0, 1), dev(E["child_solved"]))
+    # replay of the carved actions into the family record
+    nf, rows = L.family_layout(cs)
+    fam = dict(actions_out=cv((depth, wp)), parents=cv((depth, tiles, S, pitch)), family=cv((depth, tiles, nf, pitch)), child_solved=cv((depth, A, wp)))
+    ops.adi_generate(n, depth, cs, pitch, DEV, seed=2024, stream_id=3, walk_offset=11, actions_in=bufs["actions_out"], **fam)
+    assert torch.equal(fam["actions_out"][:, :n], bufs["actions_out"][:, :n])
+    assert torch.equal(fam["child_solved"][:, :, :n], bufs["child_solved"][:, :, :n])
+    rows_t = torch.as_tensor(rows.astype(np.int64)).to(DEV)                      # [A + 1, SL]: the family row that is slot p's code of child a
+    for d in range(depth):
+        assert same(ops, fam["parents"][d], n, dev(E["parents"][:, d]))
+        f = ops.to_aos(fam["family"][d], n)                                      # [n, NF]
+        assert torch.equal(f[:, rows_t[A]], d_pc[:, d])
+        for a in range(A):
+            assert torch.equal(f[:, rows_t[a]], d_cc[:, d, a]), (d, a)
+    # codes -> dense, one buffer and A blocks at once
+    want_parent = dev(dense_of(cs, E["parent_code"][:, 0]))
+    oh = cv((n, Rr, Cc), torch.float16)
+    ops.onehot_from_code(bufs["parent_code"][0], n, cs, oh)
+    assert same_dense(oh, want_parent)
+    stride = C.ceil16(n) + 16
+    ohb = cv(((A - 1) * stride + n, Rr, Cc), torch.float32)
+    ops.onehot_from_code_blocks(bufs["child_code"][0], n, cs, ohb, stride)
+    for a in range(A):
+        assert same_dense(ohb[a * stride:a * stride + n], dev(dense_of(cs, E["child_code"][:, 0, a]))), a
+    if cs == 3:                                                                   # the family -> dense writer is 3x3x3 only
+        ohf = cv(((depth * (A + 1) - 1) * stride + n, Rr, Cc), torch.bfloat16)
+        ops.onehot_from_family(fam["family"], n, cs, ohf, stride, n_depths=depth)
+        for d in range(depth):
+            for a in range(A + 1):
+                b0 = (d * (A + 1) + a) * stride
+                want = d_pc[:, d] if a == A else d_cc[:, d, a]
+                assert same_dense_as_code(ohf[b0:b0 + n], want), (d, a)
+    assert L.read_status() == 0
+
+
+@pytest.mark.parametrize("cs", C.CUBE_SIZES)
+def test_carved_adi_targets_and_search_pack(ops, L, oracle, cs):
+    """rc_adi_targets, rc_adi_targets_depths (element-wise arrays: natural alignment is all they need, 16 bytes more than enough) and
+    rc_search_pack, against the rule of cube_env.py:229-251 in numpy and the oracle's expansion."""
+    n, G = N_CARVE, 2
+    R = ref(oracle, cs, n)
+    A, SL = A_OF[cs], SL_OF[cs]
+    cv = Carver()
+    sp = L.stream_ptr(torch.device(DEV))
+    g = torch.Generator().manual_seed(cs)
+    pitch = C.ceil16(n) + 48
+    cv_h = torch.randn((G, A, pitch), generator=g)
+    cv_h[:, :, 5] = 0.25
+    cv_h[0, 3, 6] = cv_h[0, 5, 6] = 9.0
+    so_h = (torch.rand((G, A, pitch), generator=g) < 0.05).to(torch.uint8)
+    pv_h = torch.randn((G, pitch), generator=g)
+    w_h = torch.tensor([float(1 + i % 30) ** -0.3 for i in range(n)], dtype=torch.float64)
+    wd_h = torch.tensor([1.0, 2.0 ** -0.3], dtype=torch.float64)
+
+    def expected(gi, weight):
+        v = cv_h[gi, :, :n].numpy() + np.float32(-1.0)
+        s = so_h[gi, :, :n].numpy().astype(bool)
+        tp = np.where(s.any(0), np.argmax(s, 0), np.argmax(v, 0)).astype(np.int32)
+        tv = np.where(s.any(0), np.float32(1.0), v.max(0)).astype(np.float32)
+        return tv, tp, np.abs(pv_h[gi, :n].numpy().astype(np.float64) - tv.astype(np.float64)) * weight
+
+    d_cv, d_so, d_pv, d_w, d_wd = cv.like(cv_h.to(DEV)), cv.like(so_h.to(DEV)), cv.like(pv_h.to(DEV)), cv.like(w_h.to(DEV)), cv.like(wd_h.to(DEV))
+    tv, tp, err = cv((n,), torch.float32), cv((n,), torch.int32), cv((n,), torch.float64)
+    L.check(L.lib().rc_adi_targets(P(d_cv), P(d_so), P(d_pv), P(d_w), n, pitch, cs, P(tv), P(tp), P(err), sp))
+    e_tv, e_tp, e_err = expected(0, w_h.numpy())
+    assert (tv.cpu().numpy() == e_tv).all() and (tp.cpu().numpy() == e_tp).all() and (err.cpu().numpy() == e_err).all()
+    stride = G + 3
+    tv2, tp2, err2 = cv((n, stride), torch.float32), cv((n, stride), torch.int32), cv((n, stride), torch.float64)
+    L.check(L.lib().rc_adi_targets_depths(P(d_cv), A * pitch, pitch, P(d_so), pitch, P(d_pv), pitch, P(d_wd), n, G, cs, P(tv2), P(tp2), P(err2), stride, sp))
+    for gi in range(G):
+        e_tv, e_tp, e_err = expected(gi, float(wd_h[gi]))
+        assert (tv2[:, gi].cpu().numpy() == e_tv).all() and (tp2[:, gi].cpu().numpy() == e_tp).all() and (err2[:, gi].cpu().numpy() == e_err).all(), gi
+    # rc_search_pack: leaf codes + one expansion -> one record per root
+    lp, tiles = C.layout("t512", n)
+    leaf = cv.like(put(ops, oracle.encode(cs, R["states"])[0], "t512", n))
+    src = cv.like(put(ops, R["states"], "tight", n))
+    code, flags = cv((A, tiles, SL, lp)), cv((A, tiles * lp))
+    ops.expand_children(src, n, cs, None, flags, code, pitch=lp)
+    leaf_out, child_out, solved_out = cv((n, SL)), cv((n, A, SL)), cv((n, A))
+    ops.search_pack(leaf, code, flags, n, cs, leaf_out, child_out, solved_out)
+    assert torch.equal(leaf_out, dev(oracle.encode(cs, R["states"])[0]))
+    assert torch.equal(child_out, R["d_cc"]) and torch.equal(solved_out, R["d_cso"])
+    assert L.read_status() == 0
+
+
+@pytest.mark.parametrize("cs", C.CUBE_SIZES)
+def test_carved_search_stages(ops, L, cs):
+    """rc_search_init / expand / select / advance / backtrack, one depth, every buffer of the plan (and the roots) carved: the result
+    of tests/beam_ref.py's search."""
+    import beam_ref
+    from rubiks_cube_solver_amd import search
+    import test_gpu_search as base                                                # Stub, scrambles: helpers only
+    Pn, W, D = N_CARVE, 2, 1
+    cube = beam_ref.Cube(cs)
+    scr = base.scrambles(cs, [i % 4 for i in range(Pn)], seed=cs)
+    roots_aos = cube.scramble(scr)
+    want = beam_ref.beam_search(cube, roots_aos, W, D, lambda x: x.reshape(len(x), -1) @ beam_ref.stub_weights(cs, 0))
+    plan = search.BeamPlan(Pn, cs, W, D, DEV)
+    cv = Carver()
+    for name, t in list(vars(plan).items()):
+        if isinstance(t, torch.Tensor) and t.is_cuda:
+            setattr(plan, name, cv.like(t))
+    plan.beams = [cv.like(b) for b in plan.beams]
+    roots = cv.like(put(ops, roots_aos, "padded", Pn))
+    model = base.Stub(cs).to(DEV)
+    with torch.no_grad():
+        plan.init(roots, roots.shape[2])
+        plan.step(model, 0)
+        plan.backtrack()
+    assert (plan.length.cpu().numpy() == want["length"]).all() and (want["length"] == 1).any() and (want["length"] == 0).any()
+    assert (plan.actions[:D].cpu().numpy() == want["actions"]).all()
+    assert ((plan.length >= 0).cpu().numpy() == want["solved"]).all() and not want["solved"].all()
+    assert L.read_status() == 0
+
+
+@pytest.mark.parametrize("cs", C.CUBE_SIZES)
+@pytest.mark.parametrize("fmts", [(4, 4), (5, 5)], ids=["f32", "bf16"])
+def test_carved_net_first_layer(L, cs, fmts):
+    """rc_net_first_layer with codes, weights, bias and output carved: bit-equal to the slot-order sum of tests/net_ref.py."""
+    import beam_ref
+    import net_ref
+    import test_gpu_net_front as netf                                             # raw_first_layer, hard_table: helpers only
+    n, hidden = N_CARVE, 136
+    cube = beam_ref.Cube(cs)
+    rng = np.random.default_rng(cs)
+    codes = cube.codes(net_ref.random_states(cube, n, rng))
+    w, b = netf.hard_table(rng, cube.R * cube.C, hidden)
+    wfmt, ofmt = fmts
+    cv = Carver()
+    if wfmt == netf.BF16:
+        wt_dev, b_dev = cv.like(torch.tensor(w).to(torch.bfloat16).to(DEV)), cv.like(torch.tensor(b).to(torch.bfloat16).to(DEV))
+        w, b = wt_dev.float().cpu().numpy(), b_dev.float().cpu().numpy()
+    else:
+        wt_dev, b_dev = cv.like(torch.tensor(w).to(DEV)), cv.like(torch.tensor(b).to(DEV))
+    want = net_ref.first_layer(cs, codes, w, b)
+    pitch = 512
+    code_dev = cv.like(netf.device_codes(codes, pitch))
+    osz = 4 if ofmt == netf.F32 else 2
+    stride = hidden + 8
+    out = cv((n, stride * osz))
+    rc, msg = netf.raw_first_layer(code_dev, n, pitch, cs, wt_dev, b_dev, hidden, wfmt, 0, out, ofmt, stride)
+    assert rc == 0, msg
+    host = out.cpu().numpy()
+    if ofmt == netf.F32:
+        assert net_ref.same_bits(np.ascontiguousarray(host.view(np.float32).reshape(n, stride)[:, :hidden]), want)
+    else:
+        assert net_ref.same_bits(np.ascontiguousarray(host.view(np.uint16).reshape(n, stride)[:, :hidden]), net_ref.bf16_bits(want))
+    assert L.read_status() == 0
+
+
+# =================================================================================================== C. the unchecked pointers
+def test_misaligned_actions_and_done_are_refused(ops, L, oracle):
+    """actions + 1 and done + 1 (pointers inside valid allocations) through the C ABI: RC_EINVAL, the message names the operand,
+    nothing is launched (the outputs keep their fill)."""
+    n = 1029
+    lib, sp = L.lib(), L.stream_ptr(torch.device(DEV))
+    st = ops.alloc_states(n, 3, DEV)
+    ops.fill_solved(st, n, 3)
+    out = torch.full_like(st, 0xEE)
+    acts = torch.full((n + 16,), 12, dtype=torch.uint8, device=DEV)        # the no-op
+    done = torch.full((n + 16,), 0xEE, dtype=torch.uint8, device=DEV)
+    rew = torch.full((n + 16,), 9.0, dtype=torch.float32, device=DEV)
+    a_buf = torch.zeros((2, 1040), dtype=torch.uint8, device=DEV)            # U, U: would leave no cube solved
+    pitch = st.shape[2]
+    off = lambda t, k: ctypes.c_void_p(t.data_ptr() + k)
+    for k in (1, 4, 8):
+        assert lib.rc_apply_moves(P(st), P(out), off(acts, k), n, pitch, pitch, 3, P(rew), P(done), None, 0, 0, sp) == -1
+        assert b"actions must be 16-byte aligned" in lib.rc_last_error()
+        assert lib.rc_apply_moves(P(st), P(out), P(acts), n, pitch, pitch, 3, P(rew), off(done, k), None, 0, 0, sp) == -1
+        assert b"done must be 16-byte aligned" in lib.rc_last_error()
+        assert lib.rc_apply_moves_ex(P(st), P(out), off(acts, k), n, pitch, pitch, 3, None, None, None, 0, 0, sp, 2) == -1
+        assert lib.rc_is_solved(P(st), n, pitch, 3, off(done, k), P(rew), sp) == -1
+        assert b"done must be 16-byte aligned" in lib.rc_last_error()
+        assert lib.rc_scramble(P(st), n, pitch, 3, 2, 0, 0, 0, P(a_buf), None, 1040, off(done, k), None, sp) == -1
+        assert b"rc_scramble: done must be 16-byte aligned" in lib.rc_last_error()
+        assert lib.rc_scramble_from(P(st), P(out), n, pitch, 3, 2, 0, 0, 0, None, None, 0, off(done, k), None, sp) == -1
+        assert b"done" in lib.rc_last_error()
+    torch.cuda.synchronize()
+    assert bool((out == 0xEE).all()) and bool((done == 0xEE).all()) and bool((rew == 9.0).all())
+    assert same(ops, st, n, dev(oracle.solved(3, n)))                            # still solved: rc_scramble did not run
+    # the aligned calls succeed (16 bytes in is enough)
+    assert lib.rc_apply_moves(P(st), P(out), off(acts, 16), n, pitch, pitch, 3, None, off(done, 16), None, 0, 0, sp) == 0
+    assert bool((done[16:16 + n] == 1).all())
+    # ops: outputs cannot be realigned behind the caller's back
+    for fn in (lambda: ops.apply_moves(st, out, acts[:n], n, 3, None, done[1:n + 1]),
+               lambda: ops.apply_moves(st, out, acts[:n], n, 3, rew[1:n + 1], None),
+               lambda: ops.is_solved(st, n, 3, done[3:n + 3]),
+               lambda: ops.is_solved(st, n, 3, None, rew[2:n + 2]),
+               lambda: ops.scramble(out, n, 3, 0, done=done[8:n + 8], src=st),
+               lambda: ops.scramble(out, n, 3, 0, reward=rew[1:n + 1], src=st)):
+        with pytest.raises(L.RubikHipError):
+            fn()
+    assert L.read_status() == 0
+
+
+@pytest.mark.parametrize("cs", C.CUBE_SIZES)
+@pytest.mark.parametrize("obs", ["onehot", "code", None])
+def test_vec_env_steps_from_an_odd_action_slice(ops, L, oracle, cs, obs):
+    """VecCubeEnv.step(flat[1:n + 1]): the slice starts at an odd address; ops.apply_moves copies it to an aligned tensor."""
+    from rubiks_cube_solver_amd import VecCubeEnv
+    n = 1029
+    R = ref(oracle, cs, n)
+    env = VecCubeEnv(n, DEV, cs, obs=obs)
+    env.set_sim_cube(R["states"])
+    flat = torch.zeros(n + 32, dtype=torch.uint8, device=DEV)
+    flat[1:n + 1] = R["d_acts"]
+    sl = flat[1:n + 1]
+    assert sl.data_ptr() % 2 == 1 and sl.is_contiguous()
+    o, rew, done, _ = env.step(sl)
+    assert same(ops, env.stickers, n, R["d_st"])
+    assert torch.equal(done, R["d_done"]) and torch.equal(rew, R["d_rew"])
+    if obs == "onehot":
+        assert same_dense(o, R["d_oh"])
+    elif obs == "code":
+        assert same(ops, o, n, R["d_code"])
+    else:
+        assert o is None
+    assert torch.equal(flat[1:n + 1], R["d_acts"])                                # the caller's tensor is untouched
+    assert L.read_status() == 0
