@@ -21,13 +21,14 @@ class Library:
     """One native library: what it is compiled from and how, its override variable, how a process asks it who it is.  To add a
     library: one row in LIBRARIES here, and a binding module with its signature table (SIGNATURES, build_id(); see _native.load)."""
 
-    def __init__(self, name, binding, file, sources, toolchain, env, id_symbol, error_symbol):
+    def __init__(self, name, binding, file, sources, toolchain, env, id_symbol, error_symbol, headers=()):
         self.name, self.binding, self.file, self.toolchain, self.env = name, binding, file, toolchain, env   # binding: its ctypes module
         self.gpu = toolchain is _HIPCC                                              # device code: loaded after torch, to share its HIP runtime
         self.id_symbol, self.error_symbol = id_symbol, error_symbol                 # error_symbol None: the library keeps no last error
         # every file the id hashes, in this order (source_hash depends on it): the translation unit that is compiled and the
-        # headers it includes from csrc/, then the public header in include/
-        self.sources = (*(os.path.join(_HERE, "csrc", s) for s in sources[:-1]), os.path.join(_ROOT, "include", sources[-1]))
+        # headers it includes from csrc/, then the public header in include/, then `headers`: further public headers of include/
+        # (an extension of the library with a header of its own, e.g. rubikepisode.h)
+        self.sources = (*(os.path.join(_HERE, "csrc", s) for s in sources[:-1]), *(os.path.join(_ROOT, "include", h) for h in (sources[-1], *headers)))
         self.built = os.path.join(_HERE, file)                                      # where build() writes it, whatever `env` says
 
     def command(self, src_id, out):
@@ -36,7 +37,8 @@ class Library:
 
 
 LIBRARIES = {l.name: l for l in (
-    Library("hip", "_lib", "librubikhip.so", ("rubikhip.hip", "rc_device.h", "rc_tables.h", "rubikhip.h"), _HIPCC, "RUBIKHIP_LIB", "rc_build_id", "rc_last_error"),
+    Library("hip", "_lib", "librubikhip.so", ("rubikhip.hip", "rc_device.h", "rc_tables.h", "rc_episode.h", "rubikhip.h"), _HIPCC, "RUBIKHIP_LIB", "rc_build_id",
+            "rc_last_error", headers=("rubikepisode.h",)),
     Library("tree", "_tree", "librubiktree.so", ("rc_tree.cpp", "rubiktree.h"), _GXX, "RUBIKTREE_LIB", "rc_tree_build_id", None),
     Library("search", "_search_lib", "librubiksearch.so", ("rc_search.hip", "rc_device.h", "rc_tables.h", "rubiksearch.h"), _HIPCC, "RUBIKSEARCH_LIB",
             "rc_search_build_id", "rc_search_last_error"),

@@ -2284,3 +2284,6 @@ int rc_read_status(uint32_t *status, void *stream) {
 }
 
 }  // extern "C"
+
+// the rcx_* extension (include/rubikepisode.h): episode bookkeeping and the masked re-scramble
+#include "rc_episode.h"

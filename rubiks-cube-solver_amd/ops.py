@@ -225,6 +225,39 @@ def scramble(st, n, cube_size, depth, seed=0, stream_id=0, walk_offset=0, action
                             ptr(actions_out), ap, ptr(done), ptr(reward), stream_ptr(st.device)))
 
 
+def depth_range(depth):
+    """`depth` of episode_end / `scramble_count` of an auto-reset env: an int k or a pair (lo, hi), 0 <= lo <= hi  ->  (lo, hi)."""
+    lo, hi = (depth, depth) if isinstance(depth, int) else tuple(depth)
+    if not (isinstance(lo, int) and isinstance(hi, int)) or lo < 0 or hi < lo:
+        raise ValueError(f"scramble depth must be an int >= 0 or a pair (lo, hi) with 0 <= lo <= hi, got {depth!r}")
+    return lo, hi
+
+
+def episode_end(st, n, cube_size, done, elapsed, episode, ended, length, *, max_steps=0, depth, seed=0, stream_id=0, walk_offset=0,
+                walk_stride=0):
+    """The end of an env step (rcx_episode_end, include/rubikepisode.h), one launch after apply_moves: per cube elapsed += 1; a cube
+    whose `done` is set (terminated) or whose elapsed reached max_steps > 0 (truncated) gets ended = 1 | 2, length = its episode's
+    steps, elapsed = 0, episode += 1 and a fresh scramble of walk `walk_offset + episode * walk_stride + i` in st, `depth` moves deep
+    (an int, or (lo, hi): drawn per episode).  Every other cube keeps its stickers; ended = length = 0.
+    done (read), ended: uint8 [n]; elapsed, episode, length: int32 [n]; all but done are updated in place."""
+    S, _, _ = _size(cube_size)
+    pitch = _tiled(st, S, n, "episode_end")
+    lo, hi = depth_range(depth)
+    if max_steps < 0 or walk_stride < 0:
+        raise ValueError("episode_end: max_steps and walk_stride must be >= 0")
+    _vec(done, n, torch.uint8, "done", out=True)                  # read in packs: the same 16-byte rule as the outputs
+    _vec(ended, n, torch.uint8, "ended", out=True)
+    for t, what in ((elapsed, "elapsed"), (episode, "episode"), (length, "length")):
+        _vec(t, n, torch.int32, what, out=True)
+    for t, what in ((done, "done"), (elapsed, "elapsed"), (episode, "episode"), (ended, "ended"), (length, "length")):
+        if t is None:
+            raise RubikHipError(f"episode_end: {what} is required")
+    _lib.init(st.device)
+    from ._episode_lib import episode_lib
+    check(episode_lib().rcx_episode_end(ptr(st), n, pitch, cube_size, ptr(done), ptr(elapsed), max_steps, ptr(episode), lo, hi, seed, stream_id,
+                                        walk_offset, walk_stride, ptr(ended), ptr(length), stream_ptr(st.device)))
+
+
 def search_pack(leaf_code, child_code, child_solved, n, cube_size, leaf_out, child_out, solved_out):
     """The results of one expansion launch, laid out per root for the host trees of a lockstep search (rc_search_pack):
     leaf_code [tiles, SLOTS, pitch], child_code [A, tiles, SLOTS, pitch], child_solved [A, tiles * pitch]  ->

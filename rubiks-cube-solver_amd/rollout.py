@@ -88,3 +88,38 @@ def solve_percentage(model, cube_size, sample_scramble_count, sample_cube_count,
     res = greedy_rollout(model, env, max_timesteps, mask=mask, graph=graph)
     solved = res["solved"].view(sample_scramble_count, len(seeds)).float().mean(1) * 100.0
     return [float(x) for x in solved.cpu()]
+
+
+@torch.no_grad()
+def collect(model, env: VecCubeEnv, n_steps, generator=None):
+    """A fixed-length on-policy rollout of an auto-reset env (VecCubeEnv(auto_reset=True)), the shape PPO / A2C collectors and
+    evaluation at a fixed step budget expect: per time step ONE forward of `model` on the env's current observation, one action per
+    cube sampled from softmax(model(obs)[1]) with torch.multinomial (`generator`: a torch.Generator on the env's device, for
+    reproducible draws), one env.step.  Cubes whose episode ends restart inside the step; nothing is parked.
+
+    obs="onehot": the model gets the dense one-hot as float32;  obs="code": the model gets the compact code buffer itself
+    (e.g. a CodeNet wrapper) and the codes the actions were chosen from are returned as well.
+    Returns device tensors dict(actions uint8, reward float32, done uint8, ended uint8, each [T, N]) (+ codes uint8 [T, tiles, SLOTS,
+    pitch] with obs="code")."""
+    if not env.auto_reset:
+        raise ValueError("collect needs VecCubeEnv(auto_reset=True)")
+    if env.obs not in ("onehot", "code"):
+        raise ValueError("collect needs an observation: VecCubeEnv(obs='onehot' | 'code')")
+    n, dev, T = env.num_envs, env.device, int(n_steps)
+    out = {"actions": torch.empty((T, n), dtype=torch.uint8, device=dev), "reward": torch.empty((T, n), dtype=torch.float32, device=dev),
+           "done": torch.empty((T, n), dtype=torch.uint8, device=dev), "ended": torch.empty((T, n), dtype=torch.uint8, device=dev)}
+    if env.obs == "code":
+        out["codes"] = torch.empty((T, *env._obs_buf.shape), dtype=torch.uint8, device=dev)
+    obs = env._observe()
+    for t in range(T):
+        if env.obs == "code":
+            out["codes"][t].copy_(obs)
+        logits = model(obs if env.obs == "code" else obs.float())[1]
+        a = torch.multinomial(torch.softmax(logits.float(), dim=-1), 1, generator=generator).reshape(n).to(torch.uint8)
+        out["actions"][t].copy_(a)
+        obs, reward, done, info = env.step(a)
+        out["reward"][t].copy_(reward)
+        out["done"][t].copy_(done)
+        out["ended"][t].copy_(info["ended"])
+    env.check_actions()
+    return out

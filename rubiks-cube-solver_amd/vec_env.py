@@ -36,10 +36,25 @@ class VecCubeEnv:
          (lossless, 20 B per cube instead of 1920);  None -> no observation is produced.
     seed / stream_id: device RNG stream for reset() without explicit seeds (stream_id = rank in
          multi-GPU jobs gives every rank an independent stream, no communication).
+    auto_reset: a cube whose episode ended -- solved (terminated), or `max_episode_steps` > 0 steps without being solved
+         (truncated) -- starts a new episode within the same step(): a fresh scramble of `scramble_count` moves (an int k >= 0, or
+         (lo, hi): the depth is drawn per episode), see step().  `scramble_count` is required then.  Off (the default) nothing
+         changes: no further tensors, the same single launch per step.
     """
 
     def __init__(self, num_envs, device="cuda", cube_size=3, obs="onehot", onehot_dtype=torch.float32,
-                 seed=0, stream_id=0, debug_check_every=0):
+                 seed=0, stream_id=0, debug_check_every=0, auto_reset=False, max_episode_steps=0, scramble_count=None):
+        self.auto_reset = bool(auto_reset)
+        self._reset_depth = None
+        if self.auto_reset:
+            if scramble_count is None:
+                raise ValueError("auto_reset=True needs scramble_count (an int or (lo, hi)): the depth of the fresh scrambles")
+            self._reset_depth = ops.depth_range(scramble_count)
+        elif scramble_count is not None or max_episode_steps:
+            raise ValueError("scramble_count / max_episode_steps belong to auto_reset=True")
+        self.max_episode_steps = int(max_episode_steps)
+        if self.max_episode_steps < 0:
+            raise ValueError("max_episode_steps must be >= 0 (0 = no time limit)")
         self.state_dim, self.action_dim = get_env_config(cube_size)
         self.cube_size = cube_size
         self.num_envs = int(num_envs)
@@ -67,12 +82,19 @@ class VecCubeEnv:
         elif obs == "code":
             self._fmt = _lib.FMT_CODE
             self._obs_buf = ops.alloc_code(n, cube_size, dev)
+        if self.auto_reset:
+            # steps taken in the running episode, episodes started by auto-reset so far (it numbers the walks), and the two outputs
+            self.elapsed = torch.zeros(n, dtype=torch.int32, device=dev)
+            self.episode = torch.zeros(n, dtype=torch.int32, device=dev)
+            self.ended = torch.zeros(n, dtype=torch.uint8, device=dev)
+            self.episode_length = torch.zeros(n, dtype=torch.int32, device=dev)
         self.init_state()
 
     # ------------------------------------------------------------------ reference surface
     def init_state(self):
         """All cubes solved (cube_env.py:33-42)."""
         ops.fill_solved(self.stickers, self.num_envs, self.cube_size)
+        self._new_episodes()
         return self._observe()
 
     def reset(self, seeds=None, scramble_count=2, actions=None):
@@ -93,6 +115,7 @@ class VecCubeEnv:
             # the reference returns an unbound `state` here (UnboundLocalError, cube_env.py:69)
             raise UnboundLocalError("reset(scramble_count=0): the reference has no state to return")
         ops.fill_solved(self.stickers, n, self.cube_size)
+        self._new_episodes()
         if actions is None and seeds is not None:
             if len(seeds) != n:
                 raise ValueError("need one seed per env")
@@ -131,13 +154,31 @@ class VecCubeEnv:
         The three returned tensors are the env's OWN buffers, overwritten by the next step / reset: clone what
         must outlive it.  A uint8 device tensor is not range-checked on the host (that would synchronise): an
         action > action_dim leaves that cube unspecified and raises IndexError at the next check_actions()
-        (`debug_check_every=K` in the constructor runs that check every K steps)."""
+        (`debug_check_every=K` in the constructor runs that check every K steps).
+
+        auto_reset=True: three launches -- the move in place (reward, done), rcx_episode_end (include/rubikepisode.h), the
+        observation.  Returns (obs of the states AFTER any reset, reward and done of the step taken, {"ended": uint8 [N]: 0 | 1
+        terminated | 2 truncated, "episode_length": int32 [N]: the steps of the episode that ended, else 0}).  A cube that ended
+        already holds the first state of its next episode; the TERMINAL observation of a truncated episode is not returned (for a
+        terminated one it is the solved cube).  Fresh scrambles draw from `seed`, stream `stream_id + 2**32` -- never a stream
+        reset() uses -- walk `episode * num_envs + i`, where `episode` counts the auto-resets of cube i; reset() and init_state()
+        start new episodes (elapsed = 0) and leave that count running.  `active` contradicts auto-reset: ValueError.  Everything
+        stays on the device, so a step can be captured as a hipGraph and replayed; the counters advance on replay."""
+        if self.auto_reset and active is not None:
+            raise ValueError("step(active=...) parks cubes; an auto_reset env restarts them instead")
         a = self._actions(actions)
         self._steps += 1
         if self.debug_check_every and self._steps % self.debug_check_every == 0:
             self.check_actions()
         if active is not None:
             a = torch.where(active.to(self.device), a, torch.full_like(a, self.action_dim))
+        if self.auto_reset:
+            n, lo_hi = self.num_envs, self._reset_depth
+            ops.apply_moves(self.stickers, self.stickers, a, n, self.cube_size, self.reward, self.done, None, _lib.FMT_NONE)
+            ops.episode_end(self.stickers, n, self.cube_size, self.done, self.elapsed, self.episode, self.ended, self.episode_length,
+                            max_steps=self.max_episode_steps, depth=lo_hi, seed=self.seed, stream_id=self.stream_id + 2 ** 32,
+                            walk_offset=0, walk_stride=n)
+            return self._observe(), self.reward, self.done, {"ended": self.ended, "episode_length": self.episode_length}
         ops.apply_moves(self.stickers, self.stickers, a, self.num_envs, self.cube_size, self.reward, self.done,
                         self._obs_buf, self._fmt)
         return self._obs_buf, self.reward, self.done, {}
@@ -190,6 +231,9 @@ class VecCubeEnv:
         for k in ("reward", "done", "_obs_buf"):
             v = getattr(self, k)
             setattr(other, k, None if v is None else (torch.empty_like(v) if lean else v.clone()))
+        if self.auto_reset:
+            other.elapsed, other.episode = self.elapsed.clone(), self.episode.clone()         # state, like the stickers
+            other.ended, other.episode_length = (torch.empty_like(v) if lean else v.clone() for v in (self.ended, self.episode_length))
         return other
 
     __copy__ = clone
@@ -210,6 +254,11 @@ class VecCubeEnv:
                 raise IndexError("action out of range")
             a = a.to(device=self.device, dtype=torch.uint8)
         return a.contiguous().reshape(-1)
+
+    def _new_episodes(self):
+        """reset() / init_state(): every cube starts an episode; the auto-reset count (the walk numbering) keeps running."""
+        if self.auto_reset:
+            self.elapsed.zero_()
 
     def _observe(self):
         if self._obs_buf is not None:
