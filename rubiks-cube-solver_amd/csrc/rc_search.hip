@@ -603,3 +603,6 @@ int rc_search_backtrack(const uint16_t *hist_parent, const uint8_t *hist_action,
         return 0;
     });
 }
+
+// the cube symmetries (include/rubiksym.h): the rcs_* entry points of this library
+#include "rc_sym.h"

@@ -258,6 +258,62 @@ def episode_end(st, n, cube_size, done, elapsed, episode, ended, length, *, max_
                                         walk_offset, walk_stride, ptr(ended), ptr(length), stream_ptr(st.device)))
 
 
+def _state_arg(t, rows, n, pitch, what):
+    """A state operand of the symmetry kernels: a tiled tensor ([tiles, rows, pitch] or [rows, pitch]; pitch None or its last
+    dimension), or ANY contiguous uint8 HIP tensor that holds the tiles of an explicit `pitch` (a buffer carved out of a larger
+    allocation).  Returns the pitch."""
+    if t.dim() in (2, 3) and pitch in (None, t.shape[-1]):
+        return _tiled(t, rows, n, what)
+    if pitch is None or t.dtype != torch.uint8 or not t.is_cuda or not t.is_contiguous():
+        raise RubikHipError(f"{what}: need a tiled uint8 HIP tensor, or a contiguous one with an explicit pitch")
+    if t.numel() < _tiles_of(n, pitch) * rows * pitch:
+        raise RubikHipError(f"{what}: {t.numel()} bytes cannot hold {n} cubes at pitch {pitch}")
+    return pitch
+
+
+def apply_symmetry(st, n, pitch, cube_size, sym, out=None, pitch_out=None, bad=None):
+    """The images of n cubes under whole-cube symmetries (rcs_sym_apply, include/rubiksym.h): image[i] = relabel[s][st[perm[s][i]]],
+    tables.get_symmetries.  st / out: state buffers with pitches of their own (pitch None: the tensor's last dimension) that share no
+    memory; out defaults to a fresh buffer shaped like st, and its pad columns keep their bytes.  sym: an int -- one symmetry for
+    every cube, a row permutation of the tile -- or a uint8 device tensor [n], one per cube.  A sym[i] >= K cannot raise on the
+    device: cube i gets the identity image and a flag is set.  bad: that flag, a uint8 device tensor [1] the caller zeroes and reads
+    (nothing synchronises); None: a flag of the call's own, read back at once (a synchronisation) and raised as IndexError.
+    Returns out."""
+    from . import _search_lib, _sym_lib
+    S, _, _ = _size(cube_size)
+    if out is None:
+        out, pitch_out = torch.empty_like(st), pitch
+    p_in, p_out = _state_arg(st, S, n, pitch, "apply_symmetry st"), _state_arg(out, S, n, pitch_out, "apply_symmetry out")
+    L = _sym_lib.sym_lib()
+    if not isinstance(sym, torch.Tensor):
+        K = _sym_lib.count(cube_size)
+        if not 0 <= int(sym) < K:
+            raise IndexError(f"symmetry index {sym} out of range 0..{K - 1}")
+        _search_lib.check(L.rcs_sym_apply(ptr(st), ptr(out), n, p_in, p_out, cube_size, None, int(sym), None, stream_ptr(st.device)))
+        return out
+    _vec(sym, n, torch.uint8, "sym", out=True)                    # read in packs: the same 16-byte rule as the outputs
+    flag = torch.zeros(1, dtype=torch.uint8, device=st.device) if bad is None else _vec(bad, 1, torch.uint8, "bad")
+    _search_lib.check(L.rcs_sym_apply(ptr(st), ptr(out), n, p_in, p_out, cube_size, ptr(sym), 0, ptr(flag), stream_ptr(st.device)))
+    if bad is None and int(flag):
+        raise IndexError("symmetry index out of range")
+    return out
+
+
+def canonical_symmetry(st, n, pitch, cube_size, sym_out=None, out=None, pitch_out=None):
+    """The canonical form up to symmetry (rcs_sym_canonical): sym_out[i] = the lowest s whose image of cube i is the smallest of the
+    K images, compared as S-byte strings with sticker 0 first.  sym_out: uint8 device tensor [n] (default: a fresh one).  out: an
+    optional state buffer (pitch_out as in apply_symmetry) that receives the canonical images.  Returns sym_out."""
+    from . import _search_lib, _sym_lib
+    S, _, _ = _size(cube_size)
+    p_in = _state_arg(st, S, n, pitch, "canonical_symmetry st")
+    p_out = _state_arg(out, S, n, pitch_out, "canonical_symmetry out") if out is not None else 0
+    if sym_out is None:
+        sym_out = torch.empty(_lib.pitch_for(n, 16), dtype=torch.uint8, device=st.device)[:n]
+    _vec(sym_out, n, torch.uint8, "sym_out", out=True)
+    _search_lib.check(_sym_lib.sym_lib().rcs_sym_canonical(ptr(st), n, p_in, cube_size, ptr(sym_out), ptr(out), p_out, stream_ptr(st.device)))
+    return sym_out
+
+
 def search_pack(leaf_code, child_code, child_solved, n, cube_size, leaf_out, child_out, solved_out):
     """The results of one expansion launch, laid out per root for the host trees of a lockstep search (rc_search_pack):
     leaf_code [tiles, SLOTS, pitch], child_code [A, tiles, SLOTS, pitch], child_solved [A, tiles * pitch]  ->

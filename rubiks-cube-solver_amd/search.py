@@ -215,6 +215,66 @@ def beam_search(model, env, width, max_depth, *, dense_budget_bytes=1 << 30, syn
     return {"solved": plan.length >= 0, "length": plan.length, "actions": actions}
 
 
+def symmetry_indices(symmetries, cube_size):
+    """beam_search_symmetric's `symmetries` -> list of indices into tables.get_symmetries(cube_size)."""
+    from .tables import get_symmetries
+    K = get_symmetries(cube_size).count
+    if isinstance(symmetries, str):
+        if symmetries not in ("rotations", "all"):
+            raise ValueError(f"symmetries must be 'rotations', 'all' or a sequence of indices, got {symmetries!r}")
+        return list(range(K // 2 if symmetries == "rotations" else K))
+    idx = [int(s) for s in symmetries]
+    if not idx or any(not 0 <= s < K for s in idx):
+        raise IndexError(f"symmetries must be a non-empty sequence of indices in 0..{K - 1}")
+    return idx
+
+
+@torch.no_grad()
+def beam_search_symmetric(model, env, width, max_depth, symmetries="rotations", return_all=False, **beam_kwargs):
+    """beam_search from several orientations of every cube of `env`, keeping the shortest answer (`env` is left as it is).
+
+    A symmetry maps a cube at distance d to a cube at distance d and a solution to a solution, but the net is not symmetry-invariant:
+    the images of one cube get different beams.  symmetries: "rotations" (the first half of tables.get_symmetries), "all", or a
+    sequence of indices.  ONE VecCubeEnv of k * P cubes is built, image-major -- cube j * P + p is image symmetries[j] of cube p (one
+    rcs_sym_apply launch) -- and beam_search(model, that env, width, max_depth, **beam_kwargs) runs once.  Every action list is
+    mapped back to the original cube with amap[inverse[s]]; per cube the shortest solved image wins, ties to the lowest j.
+
+    Returns beam_search's dict (solved bool [P], length int32 [P], actions uint8 [max_depth, P]) plus symmetry int32 [P]: the chosen
+    index, -1 where no image was solved.  return_all=True adds all_length int32 [k, P] and all_actions uint8 [k, max_depth, P], the
+    latter mapped back as well."""
+    from .tables import get_symmetries
+    from .vec_env import VecCubeEnv
+    P, cs, dev = env.num_envs, env.cube_size, env.device
+    y = get_symmetries(cs)
+    idx = symmetry_indices(symmetries, cs)
+    k, A = len(idx), env.action_dim
+    big = VecCubeEnv(k * P, dev, cs, obs=None)
+    tiles, S, pitch = big.stickers.shape
+    rows = torch.zeros((tiles * pitch, S), dtype=torch.uint8, device=dev)
+    rows[:k * P] = ops.to_aos(env.stickers, P).repeat(k, 1)
+    src = rows.view(tiles, pitch, S).permute(0, 2, 1).contiguous()
+    sym = torch.tensor(idx, dtype=torch.uint8).repeat_interleave(P).to(dev)
+    ops.apply_symmetry(src, k * P, None, cs, sym, out=big.stickers, bad=torch.zeros(1, dtype=torch.uint8, device=dev))   # indices checked above
+    res = beam_search(model, big, width, max_depth, **beam_kwargs)
+    D = res["actions"].shape[0]
+    back = torch.from_numpy(y.amap[y.inverse[idx]].astype("int64")).to(dev)              # [k, A + 1]: image j's action -> the cube's own
+    all_actions = back[torch.arange(k, device=dev)[None, :, None], res["actions"].view(D, k, P).long()].to(torch.uint8)
+    all_length = res["length"].view(k, P)
+    # the shortest solved image, ties to the lowest j: one key per (length, j), unsolved images last
+    key = torch.where(all_length >= 0, all_length.long(), torch.full_like(all_length, max_depth + 1, dtype=torch.long)) * k + \
+        torch.arange(k, device=dev)[:, None]
+    j = key.argmin(0)
+    solved = (all_length >= 0).any(0)
+    length = torch.where(solved, all_length.gather(0, j[None])[0], torch.full_like(all_length[0], -1))
+    actions = all_actions.gather(1, j[None, None, :].expand(D, 1, P))[:, 0]
+    actions = torch.where(solved[None], actions, torch.full_like(actions, A))
+    symmetry = torch.where(solved, torch.tensor(idx, dtype=torch.int32, device=dev)[j], torch.full((P,), -1, dtype=torch.int32, device=dev))
+    out = {"solved": solved, "length": length, "actions": actions, "symmetry": symmetry}
+    if return_all:
+        out["all_length"], out["all_actions"] = all_length, all_actions.permute(1, 0, 2).contiguous()
+    return out
+
+
 @torch.no_grad()
 def beam_solve_percentage(model, cube_size, sample_scramble_count, sample_cube_count, width, max_depth, device="cuda", seeds=None,
                           graph=False, front="dense"):

@@ -26,6 +26,7 @@ the 3x3x3 ones (asserted in tests).
 from __future__ import annotations
 
 import functools
+import itertools
 from dataclasses import dataclass
 
 import numpy as np
@@ -287,6 +288,74 @@ def pair_tables(cube_size: int):
             for c0 in range(6):
                 epair[c1][c0] = t.edge_code[c0 + 10 * c1]
     return epair, np.stack(tables), index
+
+
+# ------------------------------------------------------------------------------------------- symmetries
+@dataclass(frozen=True)
+class CubeSymmetries:
+    """The whole-cube symmetries of one cube size (get_symmetries).  image[i] = relabel[s][state[perm[s][i]]]."""
+    cube_size: int
+    count: int  # K: 48 (3x3x3), 6 (2x2x2: the symmetries that fix the DLB cubie)
+    matrix: np.ndarray  # int8 [K][3][3]  signed permutation matrices M
+    perm: np.ndarray  # uint8 [K][S]   the sticker j whose (position, normal) M maps onto those of sticker i (a gather, like the moves)
+    relabel: np.ndarray  # uint8 [K][6]   the face whose normal is M times the normal of face c
+    amap: np.ndarray  # uint8 [K][A+1] T_s(move_a(x)) == move_{amap[s][a]}(T_s(x)); amap[s][A] = A (the no-op)
+    det: np.ndarray  # int8 [K]  +1 rotations (first), -1 reflections
+    inverse: np.ndarray  # uint8 [K]
+    compose: np.ndarray  # uint8 [K][K]  compose[s][u] = apply s, then u
+
+    def apply(self, states, s):
+        """[n, S] sticker rows -> their images under symmetry s (an int, or one index per row).  The rule in numpy."""
+        st = np.asarray(states, np.uint8)
+        s = np.broadcast_to(np.asarray(s, np.int64), (len(st),))
+        return self.relabel[s[:, None], np.take_along_axis(st, self.perm[s].astype(np.int64), axis=1)]
+
+
+@functools.lru_cache(maxsize=None)
+def get_symmetries(cube_size: int) -> CubeSymmetries:
+    """The symmetries of the cube as a rigid body: every signed permutation matrix M (rotations and reflections of the coordinate
+    axes), followed by the recolouring that turns the solved cube's image back into the solved cube.  The 2x2x2 env never moves the
+    DLB cubie, so it keeps the M that fix that cubie's position (-1, -1, -1).  Order: permutations of the axes in
+    itertools.permutations order, signs in itertools.product((1, -1)) order, M[r][p[r]] = sg[r]; then stably det = +1 first, so the
+    identity is index 0 and the first half are the rotations."""
+    if cube_size not in (2, 3):
+        raise NotImplementedError(f"cube_size {cube_size}")
+    n = cube_size
+    mats = []
+    for p in itertools.permutations(range(3)):
+        for sg in itertools.product((1, -1), repeat=3):
+            M = np.zeros((3, 3), np.int64)
+            for r in range(3):
+                M[r, p[r]] = sg[r]
+            if n == 2 and tuple(M @ np.array([-1, -1, -1])) != (-1, -1, -1):
+                continue
+            mats.append(M)
+    dets = [int(round(np.linalg.det(M))) for M in mats]
+    order = sorted(range(len(mats)), key=lambda k: dets[k] != 1)  # sorted() is stable
+    mats, dets = [mats[k] for k in order], [dets[k] for k in order]
+    geo = _sticker_geometry(n)
+    where = {g: i for i, g in enumerate(geo)}
+    face_of = {v: k for k, v in enumerate(_NORMAL[f] for f in FACES)}
+    names = ACTION_NAMES[n]
+    A = len(names)
+    mv = lambda M, v: tuple(int(x) for x in M @ np.array(v))
+    perm = np.zeros((len(mats), len(geo)), np.uint8)
+    relabel = np.zeros((len(mats), 6), np.uint8)
+    amap = np.full((len(mats), A + 1), A, np.uint8)
+    for s, M in enumerate(mats):
+        for j, (pos, nm) in enumerate(geo):
+            perm[s, where[(mv(M, pos), mv(M, nm))]] = j
+        for c, f in enumerate(FACES):
+            relabel[s, c] = face_of[mv(M, _NORMAL[f])]
+        for a, nm in enumerate(names):
+            face = FACES[face_of[mv(M, _NORMAL[nm[0]])]]
+            prime = nm.endswith("'") != (dets[s] < 0)  # a reflection turns clockwise into counter-clockwise
+            amap[s, a] = names.index(face + ("'" if prime else ""))
+    index = {M.tobytes(): s for s, M in enumerate(mats)}
+    compose = np.array([[index[(Mu @ Ms).tobytes()] for Mu in mats] for Ms in mats], np.uint8)
+    inverse = np.array([index[np.ascontiguousarray(M.T).tobytes()] for M in mats], np.uint8)  # orthogonal: the inverse is the transpose
+    return CubeSymmetries(cube_size=n, count=len(mats), matrix=np.array(mats, np.int8), perm=perm, relabel=relabel, amap=amap,
+                          det=np.array(dets, np.int8), inverse=inverse, compose=compose)
 
 
 def get_env_config(cube_size: int = 3):

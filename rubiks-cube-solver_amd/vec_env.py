@@ -88,6 +88,7 @@ class VecCubeEnv:
             self.episode = torch.zeros(n, dtype=torch.int32, device=dev)
             self.ended = torch.zeros(n, dtype=torch.uint8, device=dev)
             self.episode_length = torch.zeros(n, dtype=torch.int32, device=dev)
+        self._sym_buf = self._sym_bad = None         # apply_symmetry's scratch state buffer and bad-index flag, made on first use
         self.init_state()
 
     # ------------------------------------------------------------------ reference surface
@@ -217,9 +218,41 @@ class VecCubeEnv:
         return out
 
     def check_actions(self):
-        """Raise IndexError if any kernel since the last check saw an out-of-range action (synchronises)."""
+        """Raise IndexError if any kernel since the last check saw an out-of-range action, or apply_symmetry an out-of-range
+        symmetry index (synchronises)."""
         if _lib.read_status(self.device) & _lib.STATUS_BAD_ACTION:
             raise IndexError("action out of range")  # cube_env.py:86,96
+        if self._sym_bad is not None and int(self._sym_bad):
+            self._sym_bad.zero_()
+            raise IndexError("symmetry index out of range")
+
+    def apply_symmetry(self, sym):
+        """Every cube becomes its image under a whole-cube symmetry (tables.get_symmetries; include/rubiksym.h).  sym: an int (one
+        symmetry for all cubes) or a uint8 tensor [N] on the env's device (one per cube).  The image is written into a scratch
+        buffer the env keeps, which then becomes `stickers` (the old buffer is the next scratch: `stickers` is REBOUND, hold no
+        reference to it across this call).  The observation is refreshed and returned; reward, done and the episode counters are
+        untouched (a symmetry keeps solved cubes solved and every distance).  A following step(amap[s][a]) gives the image of
+        step(a).  An int out of range raises IndexError at once; an index tensor is not checked on the host: an entry >= K leaves that
+        cube as it is and raises IndexError at the next check_actions()."""
+        if isinstance(sym, torch.Tensor):
+            if sym.dtype != torch.uint8 or sym.device != self.device or sym.numel() != self.num_envs:
+                raise ValueError(f"sym must be an int or a uint8 tensor [{self.num_envs}] on {self.device}")
+            sym = sym.contiguous().reshape(-1)
+            if sym.data_ptr() % 16:
+                sym = sym.clone()
+            if self._sym_bad is None:
+                self._sym_bad = torch.zeros(1, dtype=torch.uint8, device=self.device)
+        if self._sym_buf is None:
+            self._sym_buf = torch.empty_like(self.stickers)
+        ops.apply_symmetry(self.stickers, self.num_envs, None, self.cube_size, sym, out=self._sym_buf, bad=self._sym_bad)
+        self.stickers, self._sym_buf = self._sym_buf, self.stickers
+        return self._observe()
+
+    def canonical(self):
+        """uint8 [N]: per cube the lowest symmetry index whose image is the lexicographically smallest of the K images (the
+        canonical form up to symmetry, rcs_sym_canonical).  The cubes stay as they are; apply_symmetry(env.canonical()) makes
+        every cube its canonical image."""
+        return ops.canonical_symmetry(self.stickers, self.num_envs, None, self.cube_size)
 
     def clone(self, lean=False):
         """Independent copy of the cubes.  lean: copy only the sticker buffer (the state); reward / done / observation
@@ -228,6 +261,7 @@ class VecCubeEnv:
         other = object.__new__(VecCubeEnv)
         other.__dict__.update(self.__dict__)
         other.stickers = self.stickers.clone()
+        other._sym_buf = other._sym_bad = None
         for k in ("reward", "done", "_obs_buf"):
             v = getattr(self, k)
             setattr(other, k, None if v is None else (torch.empty_like(v) if lean else v.clone()))
