@@ -84,6 +84,87 @@ int rc_search_advance(const uint8_t *beam_in, uint8_t *beam_out, int64_t n_probl
 int rc_search_backtrack(const uint16_t *hist_parent, const uint8_t *hist_action, int64_t n_problems, int width, int64_t pitch,
                         int cube_size, int max_depth, const int32_t *length, const int32_t *solution, uint8_t *actions, void *stream);
 
+/* ======================================================================================================================
+ * Batch-weighted A* (DESIGN.md "A* search"): the rca_* entry points.  Same conventions as above; the expansion and the net are the
+ * beam's (rc_search_expand on a beam of width W = B, scores written by the caller).
+ *
+ * THE RULE.  Per problem p there is a pool of capacity C.  Nodes are numbered 0 .. count[p] - 1 in order of creation; node n of
+ * problem p is element gid = p * C + n of every pool array:
+ *     pool_stickers  TILED state buffer [ptiles][S][pool_pitch] of P * C cubes, pool_pitch a power of two >= 512
+ *                    (S * pool_pitch < 2^32), ptiles = ceil(P * C / pool_pitch): cube gid
+ *     pool_keys      uint64 [KW][P * C]   the exact key, the words rc_search_expand writes
+ *     pool_parent    int32  [P * C]       node index of the parent, -1 for the root
+ *     pool_action    uint8  [P * C]       the move that made the node; the root holds the no-op A
+ *     pool_g         int32  [P * C]       moves from the root
+ *     pool_score     float  [P * C]       the net's value for the node (0 for the root, which is never scored)
+ *     pool_prio      float  [P * C]       score - weight * g in float32, TWO separately rounded operations (multiply, then subtract;
+ *                                         never an fma), so numpy's float32 gives the same bits; +inf for the root
+ *     pool_state     uint8  [P * C]       RCA_OPEN | RCA_CLOSED
+ *     count int32 [P], overflow uint8 [P]
+ *   Elements past count[p] of a problem's region are never written.
+ *   Order: higher prio is better, NaN lowest, -0 == +0 (rc_search_select's order); on equal prio the HIGHER node index wins (newer
+ *   is deeper: under an exact heuristic the search walks one geodesic instead of flooding all of them).
+ *   One iteration = rca_pop, rc_search_expand, the caller's scores, rca_merge; `iteration` points at ONE device int32, the 1-based
+ *   iteration, read by the kernels and advanced by the caller (as `depth` above).  All stream-ordered, no host synchronisation.
+ *   pop     per active problem the min(B, open nodes) best open nodes become closed and are gathered in ascending node index into
+ *           slots 0 .. of the beam: stickers, last_action = pool_action, pop_node[p * B + i] = the node of slot i,
+ *           live[p] = their number.  Beam slots, last_action and pop_node entries past live[p] are not written.  A problem with no
+ *           open node is exhausted: active = 0, live = 0, ended = *iteration, length stays -1.
+ *   merge   per active problem, candidate c = i * A + a of the expanded beam:
+ *           solved check  a VALID and SOLVED candidate exists: length = g(parent) + 1 of the candidate with the smallest such value,
+ *                         ties to the lowest c; solution[2p] = its parent node, solution[2p + 1] = its action; active = 0,
+ *                         ended = *iteration; nothing is appended.
+ *           otherwise     a candidate is NEW (flag RCA_NEW is set on it) iff it is VALID, no node of the problem's pool, open or
+ *                         closed, has its key, and it is the lowest c among the iteration's candidates with that key.  The new
+ *                         candidates become nodes in ascending c: node count + r = the r-th, stickers = the parent's moved by a,
+ *                         parent = pop_node[p * B + i], action = a, g = g(parent) + 1, score = scores[candidate], prio, open.
+ *                         Only the first C - count of them fit; the rest are dropped and overflow[p] is set and stays set; the
+ *                         problem goes on with the open nodes it has.
+ *           A known state is never re-opened and its g never lowered: DeepCubeA's re-opening rule is deliberately left out.  With
+ *           B = 1, weight = 1 and a consistent heuristic the result is still optimal; beyond that no optimality is claimed.
+ *   Every result follows from this rule and never from timing: equal keys within an iteration resolve to the lowest c
+ *   (atomicCAS + atomicMin in the scratch table), and the persistent table only ever receives keys it does not hold.
+ */
+#define RCA_OPEN 1u
+#define RCA_CLOSED 2u
+#define RCA_NEW 8u             /* candidate flag written by rca_merge */
+
+/* Limits of every call below: cube_size 2 | 3, n_problems >= 1, 1 <= batch <= 65536, capacity >= 1, n_problems * capacity < 2^31,
+ * pitches powers of two >= 512.  A violated limit, a null pointer or a device pointer that is not 16-byte aligned is -1 before
+ * anything is launched or written. */
+
+/* Bytes of the persistent hash table of a search: a power of two of 64-bit slots, at least 2 * P * C of them; -1 for bad arguments.
+ * Host only.  The per-iteration scratch of rca_merge is rc_search_workspace_bytes(cube_size, P, B) bytes. */
+int64_t rca_workspace_bytes(int cube_size, int64_t n_problems, int64_t capacity);
+
+/* Pool and root.  Cube p of `roots` (as in rc_search_init; only read) becomes node 0 of problem p: open, g = 0, prio = +inf,
+ * parent = -1, action = A, count = 1, overflow = 0; its key enters `table`, which is cleared first.  live = 0, ended = 0,
+ * solution = (-1, A).  A solved root gets length = 0 and active = 0, any other length = -1 and active = 1. */
+int rca_init(const uint8_t *roots, int64_t n_problems, int64_t root_pitch, int cube_size, int64_t capacity, int64_t pool_pitch,
+             uint8_t *pool_stickers, uint64_t *pool_keys, int32_t *pool_parent, uint8_t *pool_action, int32_t *pool_g, float *pool_score,
+             float *pool_prio, uint8_t *pool_state, int32_t *count, uint8_t *overflow, int32_t *live, uint8_t *active, int32_t *length,
+             int32_t *solution, int32_t *ended, void *table, int64_t table_bytes, void *stream);
+
+/* Pop (the rule above).  beam: a tiled state buffer of P * batch slots at `pitch`, last_action [NBp], pop_node int32 [P * batch]. */
+int rca_pop(int64_t n_problems, int cube_size, int batch, int64_t capacity, int64_t pool_pitch, const uint8_t *pool_stickers,
+            const uint8_t *pool_action, const float *pool_prio, uint8_t *pool_state, const int32_t *count, const int32_t *iteration,
+            uint8_t *beam, int64_t pitch, uint8_t *last_action, int32_t *live, uint8_t *active, int32_t *ended, int32_t *pop_node,
+            void *stream);
+
+/* Merge (the rule above; three launches: clear `scratch`, the beam's insert of every valid candidate into it, one workgroup per
+ * problem).  flags / keys / scores: the candidate arrays of rc_search_expand at (batch, pitch).  weight: finite and >= 0. */
+int rca_merge(int64_t n_problems, int cube_size, int batch, int64_t pitch, int64_t capacity, int64_t pool_pitch, float weight,
+              uint8_t *flags, const uint64_t *keys, const float *scores, const int32_t *live, uint8_t *active, int32_t *length,
+              int32_t *solution, int32_t *ended, const int32_t *iteration, const int32_t *pop_node, uint8_t *pool_stickers,
+              uint64_t *pool_keys, int32_t *pool_parent, uint8_t *pool_action, int32_t *pool_g, float *pool_score, float *pool_prio,
+              uint8_t *pool_state, int32_t *count, uint8_t *overflow, void *table, int64_t table_bytes, void *scratch,
+              int64_t scratch_bytes, void *stream);
+
+/* Backtrack: actions[d * n_problems + p] (uint8 [max_length][P]) = the moves of problem p's solution in order, then the no-op A;
+ * all no-ops where length <= 0 or length > max_length.  Follows pool_parent from solution. */
+int rca_backtrack(int64_t n_problems, int cube_size, int64_t capacity, const int32_t *pool_parent, const uint8_t *pool_action,
+                  const int32_t *length, const int32_t *solution, uint8_t *actions, int max_length, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -237,14 +237,49 @@ __device__ __forceinline__ uint32_t block_sum(uint32_t v, uint32_t *red) {
     return r;
 }
 
+// The `need`-th best of the distinct 64-bit ranks of the eligible elements i < n (the caller has counted more than `need` of them):
+// MSB-first radix select, 8 bits per pass, one 256-thread workgroup; rank(i, r) says whether i is eligible and gives its rank.
+// Returns the threshold: the elements with rank >= it are exactly the `need` best.  Every thread of the workgroup calls it.
+template <class F>
+__device__ __forceinline__ uint64_t radix_kth(uint32_t n, uint32_t need_, F &&rank) {
+    __shared__ uint32_t hist[256];
+    __shared__ uint64_t s_prefix, s_mask;
+    __shared__ uint32_t s_need, s_done;
+    const int tid = threadIdx.x;
+    if (tid == 0) { s_prefix = 0; s_mask = 0; s_need = need_; s_done = 0; }
+    for (int shift = 56; shift >= 0; shift -= 8) {
+        hist[tid] = 0;
+        __syncthreads();
+        const uint64_t prefix = s_prefix, mask = s_mask;
+        for (uint32_t i = tid; i < n; i += kSelThreads) {
+            uint64_t r;
+            if (!rank(i, r)) continue;
+            if ((r & mask) == prefix) atomicAdd(&hist[(r >> shift) & 255u], 1u);
+        }
+        __syncthreads();
+        if (tid == 0) {
+            const uint32_t need = s_need;
+            uint32_t cum = 0;
+            int bin = 255;
+            for (; bin > 0 && cum + hist[bin] < need; --bin) cum += hist[bin];
+            s_prefix = prefix | ((uint64_t)bin << shift);
+            s_mask = mask | (255ull << shift);
+            s_need = need - cum;
+            s_done = hist[bin] == need - cum;                  // the whole bin is kept: ranks >= the prefix are exactly the best `need`
+        }
+        __syncthreads();
+        if (s_done) break;
+    }
+    const uint64_t thr = s_prefix;
+    __syncthreads();                                           // the shared words may be reused by the next call
+    return thr;
+}
+
 // One workgroup per problem.  Every phase walks the candidates in c order with c = tid + 256 k, so a thread only ever re-reads
 // the survivor flags it wrote itself.
 template <class T>
 __global__ void __launch_bounds__(kSelThreads) k_select(SelectArgs a) {
     __shared__ uint32_t red[4];
-    __shared__ uint32_t hist[256];
-    __shared__ uint64_t s_prefix, s_mask;
-    __shared__ uint32_t s_need, s_done;
     const int64_t p = blockIdx.x;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     if (!a.active[p]) {
@@ -293,36 +328,15 @@ __global__ void __launch_bounds__(kSelThreads) k_select(SelectArgs a) {
         }
     }
     const uint32_t nsurv = block_sum(cnt, red);
-    // 3. the W-th best rank among the survivors (MSB-first radix select, 8 bits per pass; ranks are distinct)
+    // 3. the W-th best rank among the survivors (ranks are distinct)
     uint64_t thr = 0;
-    if (nsurv > W) {
-        if (tid == 0) { s_prefix = 0; s_mask = 0; s_need = W; s_done = 0; }
-        for (int shift = 56; shift >= 0; shift -= 8) {
-            hist[tid] = 0;
-            __syncthreads();
-            const uint64_t prefix = s_prefix, mask = s_mask;
-            for (uint32_t c = tid; c < M; c += kSelThreads) {
-                const int64_t j = cand_j<T>(a, p, c);
-                if (!(a.flags[j] & RC_SEARCH_SURVIVOR)) continue;
-                const uint64_t r = rank_of(a.scores[j], c);
-                if ((r & mask) == prefix) atomicAdd(&hist[(r >> shift) & 255u], 1u);
-            }
-            __syncthreads();
-            if (tid == 0) {
-                const uint32_t need = s_need;
-                uint32_t cum = 0;
-                int bin = 255;
-                for (; bin > 0 && cum + hist[bin] < need; --bin) cum += hist[bin];
-                s_prefix = prefix | ((uint64_t)bin << shift);
-                s_mask = mask | (255ull << shift);
-                s_need = need - cum;
-                s_done = hist[bin] == need - cum;              // the whole bin is kept: ranks >= the prefix are exactly the W best
-            }
-            __syncthreads();
-            if (s_done) break;
-        }
-        thr = s_prefix;
-    }
+    if (nsurv > W)
+        thr = radix_kth(M, W, [&](uint32_t c, uint64_t &r) {
+            const int64_t j = cand_j<T>(a, p, c);
+            if (!(a.flags[j] & RC_SEARCH_SURVIVOR)) return false;
+            r = rank_of(a.scores[j], c);
+            return true;
+        });
     // 4. the kept candidates in ascending c
     uint32_t base = 0;
     for (uint32_t c0 = 0; c0 < M; c0 += kSelThreads) {
@@ -599,6 +613,479 @@ int rc_search_backtrack(const uint16_t *hist_parent, const uint8_t *hist_action,
         if (max_depth < 1) return fail("rc_search_backtrack: max_depth must be >= 1");
         hipLaunchKernelGGL(k_backtrack, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, S(stream), hist_parent, hist_action, n, width, g.nbp,
                            T::A, max_depth, length, solution, actions);
+        RCS_HIP(hipGetLastError());
+        return 0;
+    });
+}
+
+// =========================================================================================== batch-weighted A*
+// The rca_* entry points (include/rubiksearch.h "Batch-weighted A*", DESIGN.md "A* search"): a persistent node pool per problem
+// around the beam's expand and the caller's net.
+//
+//   k_astar_init       root -> node 0 of every problem's pool (open, prio +inf), its key into the persistent table
+//   k_astar_pop        one workgroup per problem: radix select of the B best open nodes (prio desc, node index desc), closed and
+//                      gathered in ascending node index into the beam
+//   k_insert           (the beam's, unchanged) the iteration's valid candidates into the scratch table: equal keys keep the lowest c
+//   k_astar_merge      one workgroup per problem: solved check, new = owner of its scratch slot and key absent from the persistent
+//                      table, the new candidates appended in ascending c, their keys into the persistent table
+//   k_astar_backtrack  parent links -> actions [D][P]
+namespace {
+
+constexpr uint8_t kOpen = RCA_OPEN, kClosed = RCA_CLOSED;
+
+struct Pool {
+    uint8_t *stickers;            // tiled [ptiles][S][ppitch], node gid = p * cap + n
+    uint64_t *keys;               // [KW][np]
+    int32_t *parent;
+    uint8_t *action;
+    int32_t *g;
+    float *score, *prio;
+    uint8_t *state;
+    int32_t *count;
+    uint8_t *overflow;
+    unsigned long long *table;    // persistent: node gids, kEmpty elsewhere
+    uint64_t tmask;
+    int64_t np, ppitch;           // np = P * cap
+    int pshift;
+    int32_t cap;
+};
+
+__device__ __forceinline__ uint64_t block_min64(uint64_t v, uint64_t *red) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const uint64_t w = ((uint64_t)(uint32_t)__shfl_xor((int)(v >> 32), o) << 32) | (uint32_t)__shfl_xor((int)(uint32_t)v, o);
+        v = w < v ? w : v;
+    }
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    uint64_t r = red[0];
+#pragma unroll
+    for (int q = 1; q < 4; ++q) r = red[q] < r ? red[q] : r;
+    __syncthreads();
+    return r;
+}
+
+// node `gid` of the pool holds key k
+template <class T>
+__device__ __forceinline__ bool node_has_key(const Pool &o, int64_t gid, const uint64_t (&k)[Key<T>::KW]) {
+    bool eq = true;
+#pragma unroll
+    for (int x = 0; x < Key<T>::KW; ++x) eq = eq && o.keys[(int64_t)x * o.np + gid] == k[x];
+    return eq;
+}
+
+// Insert node gid under a key no node of the table holds (merge has checked, init's table is empty): the first empty slot of the
+// probe sequence.  Distinct keys only ever compete for a slot, never for an owner, so where the entries land does not matter.
+__device__ __forceinline__ void table_put(const Pool &o, uint64_t h, int64_t gid) {
+    while (atomicCAS(&o.table[h], (unsigned long long)kEmpty, (unsigned long long)gid) != kEmpty) h = (h + 1) & o.tmask;
+}
+
+template <class T>
+__global__ void __launch_bounds__(256) k_astar_init(const uint8_t *roots, int64_t n, int64_t rpitch, int rshift, Pool o, int32_t *live,
+                                                    uint8_t *active, int32_t *length, int32_t *solution, int32_t *ended) {
+    using K = Key<T>;
+    const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (p >= n) return;
+    const int64_t gid = p * o.cap;
+    const uint8_t *src = roots + (rshift >= 63 ? p : tiled(p, rpitch, rshift, T::S));
+    uint8_t *dst = o.stickers + tiled(gid, o.ppitch, o.pshift, T::S);
+    bool solved = true;
+    uint8_t first = 0;
+    uint64_t k[K::KW] = {};
+    int kk = 0;
+    for (int i = 0; i < T::S; ++i) {
+        const uint8_t v = src[(int64_t)i * rpitch];
+        dst[(int64_t)i * o.ppitch] = v;
+        if (i % T::FACE == 0) first = v;
+        else solved = solved && v == first;
+        if (!(T::SIZE == 3 && i % 9 == 4)) {                   // Key<T>::sticker enumerates the non-centre stickers in ascending order
+            k[kk / 16] |= (uint64_t)(v & 7u) << (3 * (kk % 16));
+            ++kk;
+        }
+    }
+#pragma unroll
+    for (int x = 0; x < K::KW; ++x) o.keys[(int64_t)x * o.np + gid] = k[x];
+    o.parent[gid] = -1;
+    o.action[gid] = (uint8_t)T::A;
+    o.g[gid] = 0;
+    o.score[gid] = 0.0f;
+    o.prio[gid] = __uint_as_float(0x7F800000u);                // +inf: popped first whatever the net says
+    o.state[gid] = kOpen;
+    o.count[p] = 1;
+    o.overflow[p] = 0;
+    table_put(o, slot_of<T>(k, p, o.tmask), gid);
+    live[p] = 0;
+    active[p] = solved ? 0 : 1;
+    length[p] = solved ? 0 : -1;
+    solution[2 * p] = -1;
+    solution[2 * p + 1] = T::A;
+    ended[p] = 0;
+}
+
+struct PopArgs {
+    const uint8_t *stickers, *action;                          // the pool: only `state` is written
+    const float *prio;
+    uint8_t *state;
+    const int32_t *count;
+    int64_t ppitch;
+    int pshift;
+    int32_t cap;
+    const int32_t *iteration;
+    uint8_t *beam, *last_action;
+    int32_t *live;
+    uint8_t *active;
+    int32_t *ended, *pop_node;
+    int64_t pitch;
+    int shift, batch;
+};
+
+// One workgroup per problem.  Ranks are distinct (the node index is their low word), so the radix select keeps exactly B nodes.
+template <class T>
+__global__ void __launch_bounds__(kSelThreads) k_astar_pop(PopArgs a) {
+    __shared__ uint32_t red[4];
+    const PopArgs &o = a;
+    const int64_t p = blockIdx.x;
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    if (!a.active[p]) return;
+    const int64_t g0 = p * o.cap;
+    const uint32_t n = (uint32_t)min(max(o.count[p], 0), o.cap), B = (uint32_t)a.batch;
+    uint32_t cnt = 0;
+    for (uint32_t i = tid; i < n; i += kSelThreads) cnt += o.state[g0 + i] == kOpen;
+    const uint32_t nopen = block_sum(cnt, red);
+    if (nopen == 0) {                                          // exhausted: length stays -1
+        if (tid == 0) {
+            a.active[p] = 0;
+            a.live[p] = 0;
+            a.ended[p] = *a.iteration;
+        }
+        return;
+    }
+    uint64_t thr = 0;
+    if (nopen > B)                                             // the B-th best rank; the node index is the low word: the higher one wins a tie
+        thr = radix_kth(n, B, [&](uint32_t i, uint64_t &r) {
+            if (o.state[g0 + i] != kOpen) return false;
+            r = rank_of(o.prio[g0 + i], 0xFFFFFFFFu - i);
+            return true;
+        });
+    uint32_t base = 0;
+    for (uint32_t i0 = 0; i0 < n; i0 += kSelThreads) {         // the popped nodes in ascending node index
+        const uint32_t i = i0 + tid;
+        const bool keep = i < n && o.state[g0 + i] == kOpen && (nopen <= B || rank_of(o.prio[g0 + i], 0xFFFFFFFFu - i) >= thr);
+        const unsigned long long bal = __ballot(keep);
+        if (lane == 0) red[wv] = (uint32_t)__popcll(bal);
+        __syncthreads();
+        uint32_t off = base;
+        for (int q = 0; q < wv; ++q) off += red[q];
+        const uint32_t tot = red[0] + red[1] + red[2] + red[3];
+        if (keep) {
+            const uint32_t slot = off + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
+            if (slot < B) {
+                const int64_t b = p * a.batch + slot;
+                o.state[g0 + i] = kClosed;
+                a.pop_node[b] = (int32_t)i;
+                a.last_action[b] = o.action[g0 + i];
+                const uint8_t *src = o.stickers + tiled(g0 + i, o.ppitch, o.pshift, T::S);
+                uint8_t *dst = a.beam + tiled(b, a.pitch, a.shift, T::S);
+#pragma unroll
+                for (int s = 0; s < T::S; ++s) dst[(int64_t)s * a.pitch] = src[(int64_t)s * o.ppitch];
+            }
+        }
+        base += tot;
+        __syncthreads();
+    }
+    if (tid == 0) a.live[p] = (int32_t)min(base, B);
+}
+
+struct MergeArgs {
+    SelectArgs s;                 // the iteration's candidates and the scratch table k_insert filled
+    Pool o;
+    const int32_t *iteration, *pop_node;
+    int32_t *ended;
+    float weight;
+};
+
+// the node beam slot i of problem p was popped from (a node of the pool by construction; clamped like k_advance's parents)
+__device__ __forceinline__ int32_t popped(const MergeArgs &a, int64_t p, uint32_t i, int32_t count) {
+    return min(max(a.pop_node[p * a.s.width + i], 0), count - 1);
+}
+
+template <class T>
+__global__ void __launch_bounds__(kSelThreads) k_astar_merge(MergeArgs a) {
+    using K = Key<T>;
+    __shared__ uint32_t red[4];
+    __shared__ uint64_t red64[4];
+    const SelectArgs &s = a.s;
+    const Pool &o = a.o;
+    const int64_t p = blockIdx.x;
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    if (!s.active[p]) return;
+    const int64_t g0 = p * o.cap;
+    const uint32_t M = (uint32_t)min(max(s.live[p], 0), s.width) * T::A;
+    const int32_t count = min(max(o.count[p], 1), o.cap);      // >= 1: the root; read by every thread before thread 0 writes it
+    // 1. solved check: the smallest g(parent) + 1, then the lowest c
+    uint64_t best = ~0ull;
+    for (uint32_t c = tid; c < M; c += kSelThreads) {
+        const uint8_t f = s.flags[cand_j<T>(s, p, c)];
+        if ((f & RC_SEARCH_VALID) && (f & RC_SEARCH_SOLVED)) {
+            const uint64_t v = ((uint64_t)(uint32_t)(o.g[g0 + popped(a, p, c / T::A, count)] + 1) << 32) | c;
+            best = v < best ? v : best;
+        }
+    }
+    best = block_min64(best, red64);
+    if (best != ~0ull) {
+        if (tid == 0) {
+            const uint32_t c = (uint32_t)best;
+            s.length[p] = (int32_t)(best >> 32);
+            s.solution[2 * p] = popped(a, p, c / T::A, count);
+            s.solution[2 * p + 1] = (int32_t)(c % T::A);
+            s.active[p] = 0;
+            a.ended[p] = *a.iteration;
+        }
+        return;
+    }
+    // 2. new candidates: the owner of its key's scratch slot (the lowest c with that key), and no node of this problem holds the key.
+    //    Read-only on the persistent table; other problems' workgroups may be inserting (phase 3) meanwhile, which only turns empty
+    //    slots into entries of THEIR nodes: skipped by the problem test before any key is loaded.  Nodes of p enter after the barrier.
+    for (uint32_t c = tid; c < M; c += kSelThreads) {
+        const int64_t j = cand_j<T>(s, p, c);
+        const uint8_t f = s.flags[j];
+        if (!(f & RC_SEARCH_VALID)) continue;
+        uint64_t k[K::KW];
+        load_key<T>(s, j, k);
+        const uint64_t id = ((uint64_t)p << 32) | c;
+        const uint64_t h0 = slot_of<T>(k, p, s.tmask);
+        bool owner = false;
+        for (uint64_t h = h0;; h = (h + 1) & s.tmask) {
+            const uint64_t v = s.table[h];
+            if (v == kEmpty) break;                            // cannot happen: every valid candidate was inserted
+            if (same_key<T>(s, v, k, p)) {
+                owner = v == id;
+                break;
+            }
+        }
+        if (!owner) continue;
+        bool known = false;
+        for (uint64_t h = slot_of<T>(k, p, o.tmask);; h = (h + 1) & o.tmask) {
+            const uint64_t v = o.table[h];
+            if (v == kEmpty) break;
+            if ((int64_t)v >= g0 && (int64_t)v < g0 + count && node_has_key<T>(o, (int64_t)v, k)) {
+                known = true;
+                break;
+            }
+        }
+        if (!known) s.flags[j] = f | RCA_NEW;
+    }
+    __syncthreads();
+    // 3. append in ascending c: node count + r = the r-th new candidate, while the pool has room
+    const uint32_t room = (uint32_t)(o.cap - count);
+    uint32_t base = 0;
+    for (uint32_t c0 = 0; c0 < M; c0 += kSelThreads) {
+        const uint32_t c = c0 + tid;
+        int64_t j = 0;
+        bool isnew = false;
+        if (c < M) {
+            j = cand_j<T>(s, p, c);
+            isnew = (s.flags[j] & RCA_NEW) != 0;
+        }
+        const unsigned long long bal = __ballot(isnew);
+        if (lane == 0) red[wv] = (uint32_t)__popcll(bal);
+        __syncthreads();
+        uint32_t off = base;
+        for (int q = 0; q < wv; ++q) off += red[q];
+        const uint32_t tot = red[0] + red[1] + red[2] + red[3];
+        if (isnew) {
+            const uint32_t r = off + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
+            if (r < room) {
+                const int64_t gid = g0 + count + r;
+                const int32_t par = popped(a, p, c / T::A, count);
+                uint64_t k[K::KW];
+                load_key<T>(s, j, k);
+                // the child's stickers are its key's 3-bit fields; a centre (3x3x3) never moves: the parent's
+                const uint8_t *src = o.stickers + tiled(g0 + par, o.ppitch, o.pshift, T::S);
+                uint8_t *dst = o.stickers + tiled(gid, o.ppitch, o.pshift, T::S);
+                sfor<T::S>([&](auto ic) {
+                    constexpr int i = decltype(ic)::value;
+                    if constexpr (T::SIZE == 3 && i % 9 == 4) dst[(int64_t)i * o.ppitch] = src[(int64_t)i * o.ppitch];
+                    else {
+                        constexpr int kk = T::SIZE == 3 ? (i / 9) * 8 + (i % 9 < 4 ? i % 9 : i % 9 - 1) : i;
+                        static_assert(K::sticker(kk) == i);
+                        dst[(int64_t)i * o.ppitch] = (uint8_t)((k[kk / 16] >> (3 * (kk % 16))) & 7u);
+                    }
+                });
+#pragma unroll
+                for (int x = 0; x < K::KW; ++x) o.keys[(int64_t)x * o.np + gid] = k[x];
+                const int32_t g = o.g[g0 + par] + 1;
+                const float sc = s.scores[j];
+                o.parent[gid] = par;
+                o.action[gid] = (uint8_t)(c % T::A);
+                o.g[gid] = g;
+                o.score[gid] = sc;
+                o.prio[gid] = __fsub_rn(sc, __fmul_rn(a.weight, (float)g));   // two roundings, never an fma: numpy float32 bit for bit
+                o.state[gid] = kOpen;
+                table_put(o, slot_of<T>(k, p, o.tmask), gid);
+            }
+        }
+        base += tot;
+        __syncthreads();
+    }
+    if (tid == 0) {
+        o.count[p] = count + (int32_t)min(base, room);
+        if (base > room) o.overflow[p] = 1;
+    }
+}
+
+__global__ void __launch_bounds__(256) k_astar_backtrack(const int32_t *parent, const uint8_t *action, int64_t n, int32_t cap, int A, int D,
+                                                         const int32_t *length, const int32_t *solution, uint8_t *actions) {
+    const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (p >= n) return;
+    for (int d = 0; d < D; ++d) actions[(int64_t)d * n + p] = (uint8_t)A;
+    const int L = length[p];
+    int32_t node = solution[2 * p];
+    const int32_t act = solution[2 * p + 1];
+    if (L < 1 || L > D || node < 0 || node >= cap || act < 0 || act >= A) return;
+    actions[(int64_t)(L - 1) * n + p] = (uint8_t)act;
+    for (int t = L - 1; t >= 1; --t) {                         // node has g = t: the move that made it is the solution's t-th
+        actions[(int64_t)(t - 1) * n + p] = action[p * cap + node];
+        node = parent[p * cap + node];
+        if (node < 0 || node >= cap) return;
+    }
+}
+
+int64_t astar_slots(int64_t n_problems, int64_t capacity) {
+    const int64_t need = 2 * n_problems * capacity;
+    int64_t s = 1024;
+    while (s < need) s <<= 1;
+    return s;
+}
+
+struct PoolGeo {
+    int pshift;
+    int64_t slots;
+};
+// the pool of P problems x C nodes at pool_pitch, and its table
+template <class T>
+int pool_geometry(int64_t n, int64_t capacity, int64_t pool_pitch, PoolGeo &g) {
+    if (n < 1 || capacity < 1 || capacity >= ((int64_t)1 << 31) || n >= ((int64_t)1 << 31) || n * capacity >= ((int64_t)1 << 31))
+        return fail("need n_problems >= 1, capacity >= 1 and n_problems * capacity < 2^31");
+    if (pool_pitch < 512 || (pool_pitch & (pool_pitch - 1)) != 0 || pool_pitch * T::S >= ((int64_t)1 << 32))
+        return fail("pool_pitch must be a power of two >= 512 with S * pool_pitch < 2^32");
+    g.pshift = log2_exact(pool_pitch);
+    g.slots = astar_slots(n, capacity);
+    return 0;
+}
+
+template <class... P>
+bool any_null(P... p) { return (... || (p == nullptr)); }
+template <class... P>
+bool all_aligned16(P... p) { return (... && aligned16(p)); }
+
+}  // namespace
+
+int64_t rca_workspace_bytes(int cube_size, int64_t n_problems, int64_t capacity) {
+    if ((cube_size != 2 && cube_size != 3) || n_problems < 1 || capacity < 1 || n_problems >= ((int64_t)1 << 31) ||
+        capacity >= ((int64_t)1 << 31) || n_problems * capacity >= ((int64_t)1 << 31))
+        return -1;
+    return astar_slots(n_problems, capacity) * 8;
+}
+
+int rca_init(const uint8_t *roots, int64_t n, int64_t root_pitch, int cube_size, int64_t capacity, int64_t pool_pitch, uint8_t *pool_stickers,
+             uint64_t *pool_keys, int32_t *pool_parent, uint8_t *pool_action, int32_t *pool_g, float *pool_score, float *pool_prio,
+             uint8_t *pool_state, int32_t *count, uint8_t *overflow, int32_t *live, uint8_t *active, int32_t *length, int32_t *solution,
+             int32_t *ended, void *table, int64_t table_bytes, void *stream) {
+    return by_size(cube_size, [&](auto t) {
+        using T = decltype(t);
+        PoolGeo pg;
+        if (int rc = pool_geometry<T>(n, capacity, pool_pitch, pg)) return rc;
+        if (any_null(roots, pool_stickers, pool_keys, pool_parent, pool_action, pool_g, pool_score, pool_prio, pool_state, count, overflow, live,
+                     active, length, solution, ended, table))
+            return fail("rca_init: null buffer");
+        if (!all_aligned16(roots, pool_stickers, pool_keys, pool_parent, pool_action, pool_g, pool_score, pool_prio, pool_state, count, overflow,
+                           live, active, length, solution, ended, table))
+            return fail("rca_init: buffers must be 16-byte aligned");
+        if (table_bytes < pg.slots * 8) return fail("rca_init: table smaller than rca_workspace_bytes()");
+        int rshift = 63;                                       // roots: as rc_search_init
+        if (root_pitch <= 0 || (root_pitch & 15) != 0 || root_pitch * T::S >= ((int64_t)1 << 32)) return fail("rca_init: bad root_pitch");
+        if (n > root_pitch) {
+            if (root_pitch < 512 || (root_pitch & (root_pitch - 1)) != 0) return fail("rca_init: several root tiles need a power-of-two pitch >= 512");
+            rshift = log2_exact(root_pitch);
+        }
+        const Pool o{pool_stickers, pool_keys, pool_parent, pool_action, pool_g, pool_score, pool_prio, pool_state, count, overflow,
+                     static_cast<unsigned long long *>(table), (uint64_t)(pg.slots - 1), n * capacity, pool_pitch, pg.pshift, (int32_t)capacity};
+        RCS_HIP(hipMemsetAsync(table, 0xFF, (size_t)pg.slots * 8, S(stream)));           // every slot kEmpty, once per search
+        hipLaunchKernelGGL((k_astar_init<T>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, S(stream), roots, n, root_pitch, rshift, o, live,
+                           active, length, solution, ended);
+        RCS_HIP(hipGetLastError());
+        return 0;
+    });
+}
+
+int rca_pop(int64_t n, int cube_size, int batch, int64_t capacity, int64_t pool_pitch, const uint8_t *pool_stickers, const uint8_t *pool_action,
+            const float *pool_prio, uint8_t *pool_state, const int32_t *count, const int32_t *iteration, uint8_t *beam, int64_t pitch,
+            uint8_t *last_action, int32_t *live, uint8_t *active, int32_t *ended, int32_t *pop_node, void *stream) {
+    return by_size(cube_size, [&](auto t) {
+        using T = decltype(t);
+        Geo g;
+        PoolGeo pg;
+        if (int rc = geometry<T>(n, batch, pitch, g)) return rc;
+        if (int rc = pool_geometry<T>(n, capacity, pool_pitch, pg)) return rc;
+        if (any_null(pool_stickers, pool_action, pool_prio, pool_state, count, iteration, beam, last_action, live, active, ended, pop_node))
+            return fail("rca_pop: null buffer");
+        if (!all_aligned16(pool_stickers, pool_action, pool_prio, pool_state, count, iteration, beam, last_action, live, active, ended, pop_node))
+            return fail("rca_pop: buffers must be 16-byte aligned");
+        const PopArgs a{pool_stickers, pool_action, pool_prio, pool_state, count, pool_pitch, pg.pshift, (int32_t)capacity,
+                        iteration, beam, last_action, live, active, ended, pop_node, pitch, g.shift, batch};
+        hipLaunchKernelGGL((k_astar_pop<T>), dim3((unsigned)n), dim3(kSelThreads), 0, S(stream), a);
+        RCS_HIP(hipGetLastError());
+        return 0;
+    });
+}
+
+int rca_merge(int64_t n, int cube_size, int batch, int64_t pitch, int64_t capacity, int64_t pool_pitch, float weight, uint8_t *flags,
+              const uint64_t *keys, const float *scores, const int32_t *live, uint8_t *active, int32_t *length, int32_t *solution,
+              int32_t *ended, const int32_t *iteration, const int32_t *pop_node, uint8_t *pool_stickers, uint64_t *pool_keys,
+              int32_t *pool_parent, uint8_t *pool_action, int32_t *pool_g, float *pool_score, float *pool_prio, uint8_t *pool_state,
+              int32_t *count, uint8_t *overflow, void *table, int64_t table_bytes, void *scratch, int64_t scratch_bytes, void *stream) {
+    return by_size(cube_size, [&](auto t) {
+        using T = decltype(t);
+        Geo g;
+        PoolGeo pg;
+        if (int rc = geometry<T>(n, batch, pitch, g)) return rc;
+        if (int rc = pool_geometry<T>(n, capacity, pool_pitch, pg)) return rc;
+        if (!(weight >= 0.0f) || weight > 3.0e38f) return fail("rca_merge: weight must be finite and >= 0");
+        if (any_null(flags, keys, scores, live, active, length, solution, ended, iteration, pop_node, pool_stickers, pool_keys, pool_parent,
+                     pool_action, pool_g, pool_score, pool_prio, pool_state, count, overflow, table, scratch))
+            return fail("rca_merge: null buffer");
+        if (!all_aligned16(flags, keys, scores, live, active, length, solution, ended, iteration, pop_node, pool_stickers, pool_keys, pool_parent,
+                           pool_action, pool_g, pool_score, pool_prio, pool_state, count, overflow, table, scratch))
+            return fail("rca_merge: buffers must be 16-byte aligned");
+        const int64_t sslots = table_slots(T::A, n, batch);
+        if (table_bytes < pg.slots * 8) return fail("rca_merge: table smaller than rca_workspace_bytes()");
+        if (scratch_bytes < sslots * 8) return fail("rca_merge: scratch smaller than rc_search_workspace_bytes()");
+        const SelectArgs s{flags, keys, scores, live, active, length, solution, nullptr, nullptr, nullptr, nullptr,
+                           static_cast<unsigned long long *>(scratch), (uint64_t)(sslots - 1), g.nbp, batch};
+        const Pool o{pool_stickers, pool_keys, pool_parent, pool_action, pool_g, pool_score, pool_prio, pool_state, count, overflow,
+                     static_cast<unsigned long long *>(table), (uint64_t)(pg.slots - 1), n * capacity, pool_pitch, pg.pshift, (int32_t)capacity};
+        const MergeArgs a{s, o, iteration, pop_node, ended, weight};
+        RCS_HIP(hipMemsetAsync(scratch, 0xFF, (size_t)sslots * 8, S(stream)));
+        hipLaunchKernelGGL((k_insert<T>), dim3((unsigned)((T::A * g.nbp + 255) / 256)), dim3(256), 0, S(stream), s);
+        RCS_HIP(hipGetLastError());
+        hipLaunchKernelGGL((k_astar_merge<T>), dim3((unsigned)n), dim3(kSelThreads), 0, S(stream), a);
+        RCS_HIP(hipGetLastError());
+        return 0;
+    });
+}
+
+int rca_backtrack(int64_t n, int cube_size, int64_t capacity, const int32_t *pool_parent, const uint8_t *pool_action, const int32_t *length,
+                  const int32_t *solution, uint8_t *actions, int max_length, void *stream) {
+    return by_size(cube_size, [&](auto t) {
+        using T = decltype(t);
+        if (n < 1 || capacity < 1 || n >= ((int64_t)1 << 31) || capacity >= ((int64_t)1 << 31) || n * capacity >= ((int64_t)1 << 31))
+            return fail("need n_problems >= 1, capacity >= 1 and n_problems * capacity < 2^31");
+        if (max_length < 1) return fail("rca_backtrack: max_length must be >= 1");
+        if (any_null(pool_parent, pool_action, length, solution, actions)) return fail("rca_backtrack: null buffer");
+        if (!all_aligned16(pool_parent, pool_action, length, solution, actions)) return fail("rca_backtrack: buffers must be 16-byte aligned");
+        hipLaunchKernelGGL(k_astar_backtrack, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, S(stream), pool_parent, pool_action, n,
+                           (int32_t)capacity, T::A, max_length, length, solution, actions);
         RCS_HIP(hipGetLastError());
         return 0;
     });

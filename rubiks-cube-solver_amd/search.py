@@ -10,6 +10,10 @@ The solutions are read back from the history by rc_search_backtrack at the end.
 
 front="codes" (opt-in; DESIGN.md "Net front") replaces the second line: rc_net_first_layer sums the first layer's rows straight from
 the candidate codes into a [chunk, H1] buffer, and the rest of the encoder and the value head run on that; no dense one-hot exists.
+
+astar_search / AStarPlan (DESIGN.md "A* search"): batch-weighted A* around the same expand and score.  Per cube a persistent node pool
+with an exact hash set; an iteration is rca_pop (the B best open nodes -> the beam), rc_search_expand, the score above, rca_merge (the
+states the pool has not seen become nodes); rca_backtrack follows the parent links.  The rule: include/rubiksearch.h.
 """
 from __future__ import annotations
 
@@ -215,6 +219,184 @@ def beam_search(model, env, width, max_depth, *, dense_budget_bytes=1 << 30, syn
     return {"solved": plan.length >= 0, "length": plan.length, "actions": actions}
 
 
+POOL_BUDGET_BYTES = 8 << 30           # astar_search's default capacity keeps pool + table under this many bytes
+
+
+def pool_node_bytes(cube_size):
+    """Bytes one pool node costs: stickers, key words, parent, action, g, score, prio, state, and its share of the persistent table
+    (2 to 4 slots of 8 bytes: a power of two >= 2 * P * C; 4 is counted)."""
+    S = ops._size(cube_size)[0]
+    return S + 8 * KEY_WORDS[cube_size] + 4 + 1 + 4 + 4 + 4 + 1 + 32
+
+
+class AStarPlan:
+    """Device buffers of one batch-weighted A* shape (P problems, B nodes popped per iteration, pool capacity C) and the launches of one
+    iteration.  Layouts and THE RULE: include/rubiksearch.h "Batch-weighted A*".  It owns a BeamPlan of width B (self.beam: expand,
+    score, the candidate arrays) plus the node pool.  One method per entry point; tests drive them one by one."""
+
+    def __init__(self, n_problems, cube_size, batch, capacity, device, dtype=torch.float32, dense_budget_bytes=1 << 30, front="dense",
+                 hidden=None, weight=1.0):
+        import math
+        if not 1 <= int(batch) <= MAX_WIDTH:
+            raise ValueError(f"batch must be in 1..{MAX_WIDTH}")
+        if int(n_problems) < 1 or int(capacity) < 1 or int(n_problems) * int(capacity) >= 1 << 31:
+            raise ValueError("need n_problems >= 1, capacity >= 1 and n_problems * capacity < 2^31")
+        if not (math.isfinite(float(weight)) and float(weight) >= 0.0):
+            raise ValueError(f"weight must be finite and >= 0, got {weight!r}")
+        if cube_size not in KEY_WORDS:
+            raise ValueError(f"cube_size must be 2 or 3, got {cube_size!r}")
+        self.beam = BeamPlan(n_problems, cube_size, batch, 0, device, dtype, dense_budget_bytes, front, hidden)   # its ValueErrors too
+        b = self.beam
+        self.P, self.B, self.C, self.cs, self.weight = b.P, b.W, int(capacity), b.cs, float(weight)
+        self.S, self.A, self.dev = b.S, b.A, b.dev
+        self.np = n = self.P * self.C
+        self.ppitch = beam_pitch(n)
+        self.ptiles = -(-n // self.ppitch)
+        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=self.dev)
+        self.stickers = z((self.ptiles, self.S, self.ppitch), torch.uint8)
+        self.keys = z((KEY_WORDS[self.cs], n), torch.int64)                     # uint64 words
+        self.parent, self.g = z(n, torch.int32), z(n, torch.int32)
+        self.action, self.state = z(n, torch.uint8), z(n, torch.uint8)
+        self.node_score, self.prio = z(n, torch.float32), z(n, torch.float32)   # node_score: the rule's `score` (score() is the net)
+        self.count, self.overflow = z(self.P, torch.int32), z(self.P, torch.uint8)
+        self.ended = z(self.P, torch.int32)
+        self.solution = z((self.P, 2), torch.int32)                             # (parent node, action)
+        self.pop_node = z(self.P * self.B, torch.int32)
+        self.iteration = z(1, torch.int32)
+        self.actions = None
+        from . import _astar_lib
+        self.table = torch.empty(_astar_lib.workspace_bytes(self.cs, self.P, self.C), dtype=torch.uint8, device=self.dev)
+
+    # ------------------------------------------------------------------ one entry point each
+    def _pool(self):
+        return (ptr(self.stickers), ptr(self.keys), ptr(self.parent), ptr(self.action), ptr(self.g), ptr(self.node_score), ptr(self.prio),
+                ptr(self.state))
+
+    def init(self, roots, root_pitch):
+        from ._astar_lib import astar_lib
+        _lib.init(self.dev)
+        b = self.beam
+        check(astar_lib().rca_init(ptr(roots), self.P, root_pitch, self.cs, self.C, self.ppitch, *self._pool(), ptr(self.count),
+                                   ptr(self.overflow), ptr(b.live), ptr(b.active), ptr(b.length), ptr(self.solution), ptr(self.ended),
+                                   ptr(self.table), self.table.numel(), stream_ptr(self.dev)))
+        self.iteration.fill_(1)
+
+    def pop(self):
+        from ._astar_lib import astar_lib
+        b = self.beam
+        check(astar_lib().rca_pop(self.P, self.cs, self.B, self.C, self.ppitch, ptr(self.stickers), ptr(self.action), ptr(self.prio),
+                                  ptr(self.state), ptr(self.count), ptr(self.iteration), ptr(b.beams[0]), b.pitch, ptr(b.last_action),
+                                  ptr(b.live), ptr(b.active), ptr(self.ended), ptr(self.pop_node), stream_ptr(self.dev)))
+
+    def expand(self):
+        self.beam.expand(0)
+
+    def score(self, model):
+        self.beam.score(model)
+
+    def merge(self):
+        from ._astar_lib import astar_lib
+        b = self.beam
+        check(astar_lib().rca_merge(self.P, self.cs, self.B, b.pitch, self.C, self.ppitch, self.weight, ptr(b.flags), ptr(b.keys),
+                                    ptr(b.scores), ptr(b.live), ptr(b.active), ptr(b.length), ptr(self.solution), ptr(self.ended),
+                                    ptr(self.iteration), ptr(self.pop_node), *self._pool(), ptr(self.count), ptr(self.overflow),
+                                    ptr(self.table), self.table.numel(), ptr(b.workspace), b.workspace.numel(), stream_ptr(self.dev)))
+
+    def backtrack(self, max_length):
+        """actions uint8 [max_length, P] (kept as self.actions): the solutions' moves, then the no-op."""
+        from ._astar_lib import astar_lib
+        b = self.beam
+        self.actions = torch.zeros((max(int(max_length), 1), self.P), dtype=torch.uint8, device=self.dev)
+        check(astar_lib().rca_backtrack(self.P, self.cs, self.C, ptr(self.parent), ptr(self.action), ptr(b.length), ptr(self.solution),
+                                        ptr(self.actions), self.actions.shape[0], stream_ptr(self.dev)))
+        return self.actions
+
+    def step(self, model):
+        """One iteration.  Stream-ordered, no host synchronisation (capturable as a linear hipGraph; there is no ping-pong)."""
+        self.pop()
+        self.expand()
+        self.score(model)
+        self.merge()
+        self.iteration.add_(1)
+
+
+def astar_capacity(n_problems, cube_size, batch, max_iterations, budget_bytes=POOL_BUDGET_BYTES):
+    """astar_search's default pool capacity: 1 + batch * (A - 1) * max_iterations nodes per problem (the root, and at most A - 1 new
+    states per popped node: one child undoes the parent's move), capped so that P * C * pool_node_bytes stays under budget_bytes and
+    P * C under 2^31; never below 1."""
+    A = ops._size(cube_size)[1]
+    want = 1 + int(batch) * (A - 1) * int(max_iterations)
+    cap = min(int(budget_bytes) // (pool_node_bytes(cube_size) * int(n_problems)), ((1 << 31) - 1) // int(n_problems))
+    return max(1, min(want, cap))
+
+
+@torch.no_grad()
+def astar_search(model, env, batch, max_iterations, *, weight=1.0, capacity=None, front="dense", dense_budget_bytes=1 << 30, sync_every=4,
+                 graph=False):
+    """Batch-weighted A* (DeepCubeA's search without its re-opening rule; include/rubiksearch.h has THE RULE) from every cube of `env`
+    (a VecCubeEnv, any observation mode; its state is left unchanged).
+
+    Per cube a pool holds every state ever generated.  Each iteration pops the `batch` open nodes with the best value - weight * g
+    (ties: the newer node), expands them, scores the children with the value head as beam_search does (front as there) and appends the
+    states the pool has not seen; a cube is solved at the first iteration a child is solved.  capacity: nodes per cube, default
+    astar_capacity(...) (pool and table under POOL_BUDGET_BYTES); a full pool drops new states and sets overflow.  "All cubes done"
+    is checked on the host every `sync_every` iterations.  graph=True replays one iteration as a hipGraph (one capture, after a warm-up
+    iteration on a side stream); the results equal the eager run's.
+
+    Returns dict(solved bool [P], length int32 [P] (0: the root was solved, -1: not solved), actions uint8 [L, P] with
+    L = max(1, length.max()): the solution's moves, then the no-op action_dim, iterations int32 [P]: the iteration at which the cube
+    was solved or found exhausted (0: solved root; the number of iterations run for a cube still active at the end), nodes int32 [P],
+    overflow bool [P], capacity int)."""
+    import math
+    from .adi import _module_dtype
+    P, cs = env.num_envs, env.cube_size
+    if not 1 <= int(batch) <= MAX_WIDTH:
+        raise ValueError(f"batch must be in 1..{MAX_WIDTH}")
+    if int(max_iterations) < 0 or int(sync_every) < 1:
+        raise ValueError("need max_iterations >= 0 and sync_every >= 1")
+    if not (math.isfinite(float(weight)) and float(weight) >= 0.0):
+        raise ValueError(f"weight must be finite and >= 0, got {weight!r}")
+    if front not in ("dense", "codes"):
+        raise ValueError(f"front must be 'dense' or 'codes', got {front!r}")
+    if capacity is None:
+        capacity = astar_capacity(P, cs, batch, max_iterations)
+    if int(capacity) < 1 or P * int(capacity) >= 1 << 31:
+        raise ValueError("need capacity >= 1 and n_problems * capacity < 2^31")
+    dtype, hidden = _module_dtype(model), None
+    if front == "codes":
+        from .codenet import CodeNet
+        model = model if isinstance(model, CodeNet) else CodeNet(model, cs)      # ValueError for a float16 model
+        dtype, hidden = model.dtype, model.hidden
+        if model.device != env.stickers.device:
+            raise ValueError(f"front='codes': the model is on {model.device}, the cubes on {env.stickers.device}")
+    plan = AStarPlan(P, cs, batch, capacity, env.device, dtype, dense_budget_bytes, front, hidden, weight)
+    plan.init(env.stickers, env.stickers.shape[-1])
+    g, ran = None, 0
+    for t in range(1, int(max_iterations) + 1):
+        if not graph:
+            plan.step(model)
+        elif t == 1:                                           # warm-up outside capture (libraries pick their kernels here)
+            s = torch.cuda.Stream(plan.dev)
+            s.wait_stream(torch.cuda.current_stream(plan.dev))
+            with torch.cuda.stream(s):
+                plan.step(model)
+            torch.cuda.current_stream(plan.dev).wait_stream(s)
+        else:
+            if g is None:
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g):                      # capture does not execute
+                    plan.step(model)
+            g.replay()
+        ran = t
+        if t % sync_every == 0 and not bool(plan.beam.active.any()):
+            break
+    length = plan.beam.length
+    actions = plan.backtrack(max(1, int(length.max())))
+    iterations = torch.where(plan.beam.active != 0, torch.full_like(plan.ended, ran), plan.ended)
+    return {"solved": length >= 0, "length": length, "actions": actions, "iterations": iterations, "nodes": plan.count,
+            "overflow": plan.overflow != 0, "capacity": int(capacity)}
+
+
 def symmetry_indices(symmetries, cube_size):
     """beam_search_symmetric's `symmetries` -> list of indices into tables.get_symmetries(cube_size)."""
     from .tables import get_symmetries
@@ -286,5 +468,20 @@ def beam_solve_percentage(model, cube_size, sample_scramble_count, sample_cube_c
     env = VecCubeEnv(len(ks), device, cube_size, obs=None)
     env.reset(seeds=seeds * sample_scramble_count, scramble_count=ks)
     res = beam_search(model, env, width, max_depth, graph=graph, front=front)
+    solved = res["solved"].view(sample_scramble_count, len(seeds)).float().mean(1) * 100.0
+    return [float(x) for x in solved.cpu()]
+
+
+@torch.no_grad()
+def astar_solve_percentage(model, cube_size, sample_scramble_count, sample_cube_count, batch, max_iterations, device="cuda", seeds=None,
+                           weight=1.0, capacity=None, graph=False, front="dense"):
+    """beam_solve_percentage with astar_search as the solver: for scramble_count = 1..sample_scramble_count, the percentage of the
+    sample_cube_count cubes (seeds i * 10, train.py:180) solved within max_iterations.  All (k, seed) pairs run as ONE batch."""
+    from .vec_env import VecCubeEnv
+    seeds = list(seeds) if seeds is not None else [i * 10 for i in range(sample_cube_count)]
+    ks = [k for k in range(1, sample_scramble_count + 1) for _ in seeds]
+    env = VecCubeEnv(len(ks), device, cube_size, obs=None)
+    env.reset(seeds=seeds * sample_scramble_count, scramble_count=ks)
+    res = astar_search(model, env, batch, max_iterations, weight=weight, capacity=capacity, graph=graph, front=front)
     solved = res["solved"].view(sample_scramble_count, len(seeds)).float().mean(1) * 100.0
     return [float(x) for x in solved.cpu()]
