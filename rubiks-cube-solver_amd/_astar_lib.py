@@ -6,11 +6,9 @@ _search_lib.search_lib() has loaded (build-id check included) and gives the rca_
 for rcs_*.  A library without them is an error, as everywhere else."""
 from __future__ import annotations
 
-import threading
 from ctypes import c_float as f32, c_int as i32, c_int64 as i64, c_void_p as vp
 
 from . import _native, _search_lib
-from ._native import RubikHipError
 
 OPEN, CLOSED, NEW = 1, 2, 8
 # every rca_* function of include/rubiksearch.h, once (the format of _search_lib.SIGNATURES)
@@ -23,23 +21,8 @@ ASTAR_SIGNATURES = {
     "rca_backtrack": [i64, i32, i64, vp, vp, vp, vp, vp, i32, vp],
 }
 
-_lock = threading.Lock()
-_declared = None
-
-
-def astar_lib():
-    """librubiksearch.so with the rca_* signatures applied (once)."""
-    global _declared
-    if _declared is None:
-        with _lock:
-            if _declared is None:
-                L = _search_lib.search_lib()
-                missing = [fn for fn in ASTAR_SIGNATURES if not hasattr(L, fn)]
-                if missing:
-                    raise RubikHipError(f"{_search_lib.LIB_PATH} has no {', '.join(missing)}: rebuild it with __graft_entry__.build()")
-                _native.declare(L, ASTAR_SIGNATURES)
-                _declared = L
-    return _declared
+# librubiksearch.so with the rca_* signatures applied (once)
+astar_lib = _native.extension(_search_lib.search_lib, ASTAR_SIGNATURES, "search")
 
 
 def workspace_bytes(cube_size, n_problems, capacity) -> int:

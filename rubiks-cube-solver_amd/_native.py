@@ -58,6 +58,26 @@ def load(name, signatures):
     return _loaded[name]
 
 
+def extension(base_loader, signatures, name):
+    """The loader of an extension of library `name`: further entry points of the SAME binary, declared in a header of their own.
+    Calling it takes the library base_loader() has loaded (build-id check included), gives the functions of `signatures` their
+    signatures, once, and returns that one CDLL object every time.  A library without them is an error, as everywhere else."""
+    lock, declared = threading.Lock(), []
+
+    def loader():
+        if not declared:
+            with lock:
+                if not declared:
+                    L = base_loader()
+                    missing = [fn for fn in signatures if not hasattr(L, fn)]
+                    if missing:
+                        raise RubikHipError(f"{path(name)} has no {', '.join(missing)}: rebuild it with __graft_entry__.build()")
+                    declare(L, signatures)
+                    declared.append(L)
+        return declared[0]
+    return loader
+
+
 def build_id(name, L) -> str:
     """The source hash the loaded library L was built from."""
     return getattr(L, _build.LIBRARIES[name].id_symbol)().decode()

@@ -5,13 +5,11 @@ library _search_lib.search_lib() has loaded (build-id check included: csrc/rc_sy
 its hashed sources) and gives the rcs_* entry points their signatures.  A library without them is an error, as everywhere else."""
 from __future__ import annotations
 
-import threading
 from ctypes import c_int as i32, c_int64 as i64, c_void_p as vp
 
 import numpy as np
 
 from . import _native, _search_lib
-from ._native import RubikHipError
 
 # every function of include/rubiksym.h, once (the format of _search_lib.SIGNATURES)
 SYM_SIGNATURES = {
@@ -21,23 +19,8 @@ SYM_SIGNATURES = {
     "rcs_sym_canonical": [vp, i64, i64, i32, vp, vp, i64, vp],
 }
 
-_lock = threading.Lock()
-_declared = None
-
-
-def sym_lib():
-    """librubiksearch.so with the rcs_* signatures applied (once)."""
-    global _declared
-    if _declared is None:
-        with _lock:
-            if _declared is None:
-                L = _search_lib.search_lib()
-                missing = [fn for fn in SYM_SIGNATURES if not hasattr(L, fn)]
-                if missing:
-                    raise RubikHipError(f"{_search_lib.LIB_PATH} has no {', '.join(missing)}: rebuild it with __graft_entry__.build()")
-                _native.declare(L, SYM_SIGNATURES)
-                _declared = L
-    return _declared
+# librubiksearch.so with the rcs_* signatures applied (once)
+sym_lib = _native.extension(_search_lib.search_lib, SYM_SIGNATURES, "search")
 
 
 def count(cube_size) -> int:

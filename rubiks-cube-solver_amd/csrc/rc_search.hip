@@ -10,6 +10,13 @@
 //                candidates listed in ascending c
 //   k_advance    gather + move the kept parents into the other beam buffer, last action, history row
 //   k_backtrack  history -> actions [D][P]
+//
+// The workgroup helpers under k_select and the A* kernels further down (every thread of a 256-thread workgroup calls them):
+//   block_reduce     one value per workgroup from one per thread (min, sum; 32- or 64-bit)
+//   radix_kth        the rank of the k-th best element: the threshold of a top-k
+//   ordered_compact  the kept elements numbered in ascending index: where a top-k or a list of new nodes is written
+//   owns_key         the exact dedup's answer for one candidate: it is the one that holds its key's slot of the scratch table
+//   copy_root        a root's stickers into a beam slot or a pool node, with the solved test
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -40,7 +47,138 @@ __device__ __forceinline__ int64_t tiled(int64_t b, int64_t pitch, int shift, in
     return (b >> shift) * rows * pitch + (b & (pitch - 1));
 }
 
+// ------------------------------------------------------------------------------------- workgroup helpers
+// One word per wave of a 256-thread workgroup: the scratch of block_reduce and ordered_compact, one array per word type.  Both
+// end on a barrier after their last read of it, so calls may follow one another.
+template <class V>
+__device__ __forceinline__ V *wave_words() {
+    __shared__ V w[kSelThreads / kWave];
+    return w;
+}
+
+template <class V>
+__device__ __forceinline__ V lane_xor(V v, int o) {
+    if constexpr (sizeof(V) == 8)                              // the shuffle moves 32 bits
+        return ((uint64_t)(uint32_t)__shfl_xor((int)(v >> 32), o) << 32) | (uint32_t)__shfl_xor((int)(uint32_t)v, o);
+    else return (V)__shfl_xor((int)v, o);
+}
+
+// op over the v of all 256 threads (op associative and commutative; V = uint32_t or uint64_t), returned to every thread
+template <class V, class Op>
+__device__ __forceinline__ V block_reduce(V v, Op op) {
+    V *red = wave_words<V>();
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = op(v, lane_xor(v, o));
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    const V r = op(op(red[0], red[1]), op(red[2], red[3]));
+    __syncthreads();
+    return r;
+}
+struct Min {
+    template <class V>
+    __device__ V operator()(V x, V y) const { return y < x ? y : x; }
+};
+struct Sum {
+    template <class V>
+    __device__ V operator()(V x, V y) const { return x + y; }
+};
+
+// The elements i < n with pred(i), numbered in ascending i: emit(i, slot) runs for each of them with slot = how many kept elements
+// precede it.  Returns their number.  A caller that wants the first k only tests slot < k in emit.  n is the same for the whole
+// workgroup; thread t sees the elements i = t + 256 r and nobody else's, so pred may read what the thread's own earlier emit (or
+// earlier code at the same i) wrote without a barrier.  Barriers: two per round of 256 elements, the second after the round's
+// last read of the shared words -- it is the trailing barrier that lets another call, or a block_reduce, follow at once.  They
+// order the helper's own words only: a caller whose pred reads what OTHER threads wrote puts its own barrier before the call.
+template <class P, class E>
+__device__ __forceinline__ uint32_t ordered_compact(uint32_t n, P &&pred, E &&emit) {
+    uint32_t *red = wave_words<uint32_t>();
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    uint32_t base = 0;
+    for (uint32_t i0 = 0; i0 < n; i0 += kSelThreads) {
+        const uint32_t i = i0 + tid;
+        const bool keep = i < n && pred(i);
+        const unsigned long long bal = __ballot(keep);
+        if (lane == 0) red[wv] = (uint32_t)__popcll(bal);
+        __syncthreads();
+        uint32_t off = base;
+        for (int q = 0; q < wv; ++q) off += red[q];
+        const uint32_t tot = red[0] + red[1] + red[2] + red[3];
+        if (keep) emit(i, off + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull)));
+        base += tot;
+        __syncthreads();
+    }
+    return base;
+}
+
+// rank of a candidate: larger is better.  Score order with NaN lowest and -0 == +0 in the high word, then the lower c.
+__device__ __forceinline__ uint64_t rank_of(float v, uint32_t c) {
+    uint32_t u = __float_as_uint(v);
+    uint32_t o;
+    if (v != v) o = 0u;
+    else {
+        if (u == 0x80000000u) u = 0u;
+        o = (u & 0x80000000u) ? ~u : (u | 0x80000000u);      // never 0: ~u == 0 only for a NaN pattern
+    }
+    return ((uint64_t)o << 32) | (0xFFFFFFFFu - c);
+}
+
+// The `need`-th best of the distinct 64-bit ranks of the eligible elements i < n (the caller has counted more than `need` of them):
+// MSB-first radix select, 8 bits per pass, one 256-thread workgroup; rank(i, r) says whether i is eligible and gives its rank.
+// Returns the threshold: the elements with rank >= it are exactly the `need` best.  Every thread of the workgroup calls it.
+template <class F>
+__device__ __forceinline__ uint64_t radix_kth(uint32_t n, uint32_t need_, F &&rank) {
+    __shared__ uint32_t hist[256];
+    __shared__ uint64_t s_prefix, s_mask;
+    __shared__ uint32_t s_need, s_done;
+    const int tid = threadIdx.x;
+    if (tid == 0) { s_prefix = 0; s_mask = 0; s_need = need_; s_done = 0; }
+    for (int shift = 56; shift >= 0; shift -= 8) {
+        hist[tid] = 0;
+        __syncthreads();
+        const uint64_t prefix = s_prefix, mask = s_mask;
+        for (uint32_t i = tid; i < n; i += kSelThreads) {
+            uint64_t r;
+            if (!rank(i, r)) continue;
+            if ((r & mask) == prefix) atomicAdd(&hist[(r >> shift) & 255u], 1u);
+        }
+        __syncthreads();
+        if (tid == 0) {
+            const uint32_t need = s_need;
+            uint32_t cum = 0;
+            int bin = 255;
+            for (; bin > 0 && cum + hist[bin] < need; --bin) cum += hist[bin];
+            s_prefix = prefix | ((uint64_t)bin << shift);
+            s_mask = mask | (255ull << shift);
+            s_need = need - cum;
+            s_done = hist[bin] == need - cum;                  // the whole bin is kept: ranks >= the prefix are exactly the best `need`
+        }
+        __syncthreads();
+        if (s_done) break;
+    }
+    const uint64_t thr = s_prefix;
+    __syncthreads();                                           // the shared words may be reused by the next call
+    return thr;
+}
+
 // ------------------------------------------------------------------------------------------------- roots
+// Root p of the roots buffer (one tile when rshift >= 63, else tiles of rpitch = 1 << rshift) -> the row at dst, sticker i at
+// dst[i * dpitch]; each(i, v) sees every sticker on its way.  Returns whether the root is solved.
+template <class T, class F>
+__device__ __forceinline__ bool copy_root(const uint8_t *roots, int64_t p, int64_t rpitch, int rshift, uint8_t *dst, int64_t dpitch, F &&each) {
+    const uint8_t *src = roots + (rshift >= 63 ? p : tiled(p, rpitch, rshift, T::S));
+    bool solved = true;
+    uint8_t first = 0;
+    for (int i = 0; i < T::S; ++i) {
+        const uint8_t v = src[(int64_t)i * rpitch];
+        dst[(int64_t)i * dpitch] = v;
+        if (i % T::FACE == 0) first = v;
+        else solved = solved && v == first;                    // py333.py:229-233: every face equals its first sticker
+        each(i, v);
+    }
+    return solved;
+}
+
 template <class T>
 __global__ void __launch_bounds__(256) k_init(const uint8_t *roots, int64_t n, int64_t rpitch, int rshift, uint8_t *beam, int64_t pitch,
                                               int shift, int width, uint8_t *last, int32_t *live, uint8_t *active, int32_t *length,
@@ -48,16 +186,7 @@ __global__ void __launch_bounds__(256) k_init(const uint8_t *roots, int64_t n, i
     const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (p >= n) return;
     const int64_t b = p * width;
-    const uint8_t *src = roots + (rshift >= 63 ? p : tiled(p, rpitch, rshift, T::S));
-    uint8_t *dst = beam + tiled(b, pitch, shift, T::S);
-    bool solved = true;
-    uint8_t first = 0;
-    for (int i = 0; i < T::S; ++i) {
-        const uint8_t v = src[(int64_t)i * rpitch];
-        dst[(int64_t)i * pitch] = v;
-        if (i % T::FACE == 0) first = v;
-        else solved = solved && v == first;                    // py333.py:229-233: every face equals its first sticker
-    }
+    const bool solved = copy_root<T>(roots, p, rpitch, rshift, beam + tiled(b, pitch, shift, T::S), pitch, [](int, uint8_t) {});
     last[b] = (uint8_t)T::A;
     live[p] = solved ? 0 : 1;
     active[p] = solved ? 0 : 1;
@@ -132,21 +261,25 @@ __global__ void __launch_bounds__(kWave) k_expand(ExpandArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------ dedup + select
-struct SelectArgs {
+// the candidates of one step (k_expand's output, scored) with the per-problem state they update and the scratch table of their keys
+struct Cands {
     uint8_t *flags;
     const uint64_t *keys;
     const float *scores;
     const int32_t *live;
     uint8_t *active;
     int32_t *length, *solution;
-    const int32_t *depth;
-    uint16_t *sel_parent;
-    uint8_t *sel_action;
-    int32_t *sel_count;
     unsigned long long *table;
     uint64_t tmask;
     int64_t nbp;
     int width;
+};
+// ... and what the beam's select makes of them
+struct SelectArgs : Cands {
+    const int32_t *depth;
+    uint16_t *sel_parent;
+    uint8_t *sel_action;
+    int32_t *sel_count;
 };
 
 __device__ __forceinline__ uint64_t mix64(uint64_t z) {
@@ -156,12 +289,12 @@ __device__ __forceinline__ uint64_t mix64(uint64_t z) {
 }
 
 template <class T>
-__device__ __forceinline__ int64_t cand_j(const SelectArgs &a, int64_t p, uint32_t c) {
+__device__ __forceinline__ int64_t cand_j(const Cands &a, int64_t p, uint32_t c) {
     return (int64_t)(c % T::A) * a.nbp + p * a.width + c / T::A;
 }
 
 template <class T>
-__device__ __forceinline__ void load_key(const SelectArgs &a, int64_t j, uint64_t (&k)[Key<T>::KW]) {
+__device__ __forceinline__ void load_key(const Cands &a, int64_t j, uint64_t (&k)[Key<T>::KW]) {
 #pragma unroll
     for (int x = 0; x < Key<T>::KW; ++x) k[x] = a.keys[(int64_t)x * T::A * a.nbp + j];
 }
@@ -176,7 +309,7 @@ __device__ __forceinline__ uint64_t slot_of(const uint64_t (&k)[Key<T>::KW], int
 
 // the candidate `id` = (p << 32) | c holds the same key as (k, p)
 template <class T>
-__device__ __forceinline__ bool same_key(const SelectArgs &a, uint64_t id, const uint64_t (&k)[Key<T>::KW], int64_t p) {
+__device__ __forceinline__ bool same_key(const Cands &a, uint64_t id, const uint64_t (&k)[Key<T>::KW], int64_t p) {
     if ((int64_t)(id >> 32) != p) return false;
     uint64_t o[Key<T>::KW];
     load_key<T>(a, cand_j<T>(a, p, (uint32_t)id), o);
@@ -187,7 +320,7 @@ __device__ __forceinline__ bool same_key(const SelectArgs &a, uint64_t id, const
 }
 
 template <class T>
-__global__ void __launch_bounds__(256) k_insert(SelectArgs a) {
+__global__ void __launch_bounds__(256) k_insert(Cands a) {
     const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (j >= T::A * a.nbp || !(a.flags[j] & RC_SEARCH_VALID)) return;        // valid implies a slot of a real problem
     const int64_t ac = j / a.nbp, b = j - ac * a.nbp, p = b / a.width, w = b - p * a.width;
@@ -206,82 +339,25 @@ __global__ void __launch_bounds__(256) k_insert(SelectArgs a) {
     }
 }
 
-// rank of a candidate: larger is better.  Score order with NaN lowest and -0 == +0 in the high word, then the lower c.
-__device__ __forceinline__ uint64_t rank_of(float v, uint32_t c) {
-    uint32_t u = __float_as_uint(v);
-    uint32_t o;
-    if (v != v) o = 0u;
-    else {
-        if (u == 0x80000000u) u = 0u;
-        o = (u & 0x80000000u) ? ~u : (u | 0x80000000u);      // never 0: ~u == 0 only for a NaN pattern
+// Candidate c of problem p (row j = cand_j, valid, so k_insert has put it into the scratch table): its key into k, and whether it
+// is the entry its key's slot holds, i.e. the lowest c of the problem with that key.  Read-only on the table.
+template <class T>
+__device__ __forceinline__ bool owns_key(const Cands &a, int64_t p, uint32_t c, int64_t j, uint64_t (&k)[Key<T>::KW]) {
+    load_key<T>(a, j, k);
+    const uint64_t id = ((uint64_t)p << 32) | c;
+    for (uint64_t h = slot_of<T>(k, p, a.tmask);; h = (h + 1) & a.tmask) {
+        const uint64_t v = a.table[h];
+        if (v == kEmpty) return false;                         // cannot happen: every valid candidate was inserted
+        if (same_key<T>(a, v, k, p)) return v == id;
     }
-    return ((uint64_t)o << 32) | (0xFFFFFFFFu - c);
-}
-
-__device__ __forceinline__ uint32_t block_min(uint32_t v, uint32_t *red) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = min(v, (uint32_t)__shfl_xor((int)v, o));
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    const uint32_t r = min(min(red[0], red[1]), min(red[2], red[3]));
-    __syncthreads();
-    return r;
-}
-__device__ __forceinline__ uint32_t block_sum(uint32_t v, uint32_t *red) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    const uint32_t r = red[0] + red[1] + red[2] + red[3];
-    __syncthreads();
-    return r;
-}
-
-// The `need`-th best of the distinct 64-bit ranks of the eligible elements i < n (the caller has counted more than `need` of them):
-// MSB-first radix select, 8 bits per pass, one 256-thread workgroup; rank(i, r) says whether i is eligible and gives its rank.
-// Returns the threshold: the elements with rank >= it are exactly the `need` best.  Every thread of the workgroup calls it.
-template <class F>
-__device__ __forceinline__ uint64_t radix_kth(uint32_t n, uint32_t need_, F &&rank) {
-    __shared__ uint32_t hist[256];
-    __shared__ uint64_t s_prefix, s_mask;
-    __shared__ uint32_t s_need, s_done;
-    const int tid = threadIdx.x;
-    if (tid == 0) { s_prefix = 0; s_mask = 0; s_need = need_; s_done = 0; }
-    for (int shift = 56; shift >= 0; shift -= 8) {
-        hist[tid] = 0;
-        __syncthreads();
-        const uint64_t prefix = s_prefix, mask = s_mask;
-        for (uint32_t i = tid; i < n; i += kSelThreads) {
-            uint64_t r;
-            if (!rank(i, r)) continue;
-            if ((r & mask) == prefix) atomicAdd(&hist[(r >> shift) & 255u], 1u);
-        }
-        __syncthreads();
-        if (tid == 0) {
-            const uint32_t need = s_need;
-            uint32_t cum = 0;
-            int bin = 255;
-            for (; bin > 0 && cum + hist[bin] < need; --bin) cum += hist[bin];
-            s_prefix = prefix | ((uint64_t)bin << shift);
-            s_mask = mask | (255ull << shift);
-            s_need = need - cum;
-            s_done = hist[bin] == need - cum;                  // the whole bin is kept: ranks >= the prefix are exactly the best `need`
-        }
-        __syncthreads();
-        if (s_done) break;
-    }
-    const uint64_t thr = s_prefix;
-    __syncthreads();                                           // the shared words may be reused by the next call
-    return thr;
 }
 
 // One workgroup per problem.  Every phase walks the candidates in c order with c = tid + 256 k, so a thread only ever re-reads
 // the survivor flags it wrote itself.
 template <class T>
 __global__ void __launch_bounds__(kSelThreads) k_select(SelectArgs a) {
-    __shared__ uint32_t red[4];
     const int64_t p = blockIdx.x;
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int tid = threadIdx.x;
     if (!a.active[p]) {
         if (tid == 0) a.sel_count[p] = 0;
         return;
@@ -294,7 +370,7 @@ __global__ void __launch_bounds__(kSelThreads) k_select(SelectArgs a) {
         const uint8_t f = a.flags[cand_j<T>(a, p, c)];
         if ((f & RC_SEARCH_VALID) && (f & RC_SEARCH_SOLVED)) { best = c; break; }   // c grows: the thread's first is its lowest
     }
-    best = block_min(best, red);
+    best = block_reduce(best, Min{});
     if (best != ~0u) {
         if (tid == 0) {
             a.length[p] = *a.depth;
@@ -311,23 +387,12 @@ __global__ void __launch_bounds__(kSelThreads) k_select(SelectArgs a) {
         const uint8_t f = a.flags[j];
         if (!(f & RC_SEARCH_VALID)) continue;
         uint64_t k[Key<T>::KW];
-        load_key<T>(a, j, k);
-        const uint64_t id = ((uint64_t)p << 32) | c;
-        uint64_t h = slot_of<T>(k, p, a.tmask);
-        while (true) {
-            const uint64_t v = a.table[h];
-            if (v == kEmpty) break;                            // cannot happen: every valid candidate was inserted
-            if (same_key<T>(a, v, k, p)) {
-                if (v == id) {
-                    a.flags[j] = f | RC_SEARCH_SURVIVOR;
-                    ++cnt;
-                }
-                break;
-            }
-            h = (h + 1) & a.tmask;
+        if (owns_key<T>(a, p, c, j, k)) {
+            a.flags[j] = f | RC_SEARCH_SURVIVOR;
+            ++cnt;
         }
     }
-    const uint32_t nsurv = block_sum(cnt, red);
+    const uint32_t nsurv = block_reduce(cnt, Sum{});
     // 3. the W-th best rank among the survivors (ranks are distinct)
     uint64_t thr = 0;
     if (nsurv > W)
@@ -338,31 +403,19 @@ __global__ void __launch_bounds__(kSelThreads) k_select(SelectArgs a) {
             return true;
         });
     // 4. the kept candidates in ascending c
-    uint32_t base = 0;
-    for (uint32_t c0 = 0; c0 < M; c0 += kSelThreads) {
-        const uint32_t c = c0 + tid;
-        bool keep = false;
-        if (c < M) {
+    const uint32_t kept = ordered_compact(
+        M,
+        [&](uint32_t c) {
             const int64_t j = cand_j<T>(a, p, c);
-            keep = (a.flags[j] & RC_SEARCH_SURVIVOR) && (nsurv <= W || rank_of(a.scores[j], c) >= thr);
-        }
-        const unsigned long long bal = __ballot(keep);
-        if (lane == 0) red[wv] = (uint32_t)__popcll(bal);
-        __syncthreads();
-        uint32_t off = base;
-        for (int q = 0; q < wv; ++q) off += red[q];
-        const uint32_t tot = red[0] + red[1] + red[2] + red[3];
-        if (keep) {
-            const uint32_t slot = off + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
+            return (a.flags[j] & RC_SEARCH_SURVIVOR) && (nsurv <= W || rank_of(a.scores[j], c) >= thr);
+        },
+        [&](uint32_t c, uint32_t slot) {
             if (slot < W) {
                 a.sel_parent[p * a.width + slot] = (uint16_t)(c / T::A);
                 a.sel_action[p * a.width + slot] = (uint8_t)(c % T::A);
             }
-        }
-        base += tot;
-        __syncthreads();
-    }
-    if (tid == 0) a.sel_count[p] = (int32_t)min(base, W);
+        });
+    if (tid == 0) a.sel_count[p] = (int32_t)min(kept, W);
 }
 
 // ----------------------------------------------------------------------------------------------- advance
@@ -457,6 +510,10 @@ int fail(const char *msg) {
     snprintf(t_err, sizeof t_err, "%s", msg);
     return -1;
 }
+int fail(const char *fn, const char *msg) {
+    snprintf(t_err, sizeof t_err, "%s: %s", fn, msg);
+    return -1;
+}
 #define RCS_HIP(call)                                                                               \
     do {                                                                                            \
         const hipError_t e_ = (call);                                                               \
@@ -468,6 +525,10 @@ int fail(const char *msg) {
 
 inline hipStream_t S(void *s) { return static_cast<hipStream_t>(s); }
 inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+template <class... P>
+bool any_null(P... p) { return (... || (p == nullptr)); }
+template <class... P>
+bool all_aligned16(P... p) { return (... && aligned16(p)); }
 inline int log2_exact(int64_t v) {
     int s = 0;
     while (((int64_t)1 << s) < v) ++s;
@@ -497,12 +558,25 @@ int geometry(int64_t n_problems, int width, int64_t pitch, Geo &g) {
     return 0;
 }
 
-int64_t table_slots(int A, int64_t n_problems, int width) {
-    const int64_t need = 2 * (int64_t)A * n_problems * width;
+// Where fn's roots lie: one tile (root_pitch >= n, root_pitch % 16 == 0: rshift 63) or power-of-two tiles of root_pitch = 1 << rshift
+template <class T>
+int root_layout(const char *fn, int64_t n, int64_t root_pitch, int &rshift) {
+    rshift = 63;
+    if (root_pitch <= 0 || (root_pitch & 15) != 0 || root_pitch * T::S >= ((int64_t)1 << 32)) return fail(fn, "bad root_pitch");
+    if (n > root_pitch) {
+        if (root_pitch < 512 || (root_pitch & (root_pitch - 1)) != 0) return fail(fn, "several root tiles need a power-of-two pitch >= 512");
+        rshift = log2_exact(root_pitch);
+    }
+    return 0;
+}
+
+// slots of an open-addressing table that holds `need` / 2 entries: a power of two, half empty at the least
+int64_t pow2_slots(int64_t need) {
     int64_t s = 1024;
     while (s < need) s <<= 1;
     return s;
 }
+int64_t table_slots(int A, int64_t n_problems, int width) { return pow2_slots(2 * (int64_t)A * n_problems * width); }
 
 }  // namespace
 
@@ -528,13 +602,9 @@ int rc_search_init(const uint8_t *roots, int64_t n, int64_t root_pitch, int cube
         using T = decltype(t);
         Geo g;
         if (int rc = geometry<T>(n, width, pitch, g)) return rc;
-        if (!roots || !beam || !last_action || !live || !active || !length || !solution) return fail("rc_search_init: null buffer");
-        int rshift = 63;                                       // roots: one tile (pitch >= n, pitch % 16 == 0) or power-of-two tiles
-        if (root_pitch <= 0 || (root_pitch & 15) != 0 || root_pitch * T::S >= ((int64_t)1 << 32)) return fail("rc_search_init: bad root_pitch");
-        if (n > root_pitch) {
-            if (root_pitch < 512 || (root_pitch & (root_pitch - 1)) != 0) return fail("rc_search_init: several root tiles need a power-of-two pitch >= 512");
-            rshift = log2_exact(root_pitch);
-        }
+        if (any_null(roots, beam, last_action, live, active, length, solution)) return fail("rc_search_init: null buffer");
+        int rshift;
+        if (int rc = root_layout<T>("rc_search_init", n, root_pitch, rshift)) return rc;
         hipLaunchKernelGGL((k_init<T>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, S(stream), roots, n, root_pitch, rshift, beam, pitch,
                            g.shift, width, last_action, live, active, length, solution);
         RCS_HIP(hipGetLastError());
@@ -548,9 +618,8 @@ int rc_search_expand(const uint8_t *beam, int64_t n, int width, int64_t pitch, i
         using T = decltype(t);
         Geo g;
         if (int rc = geometry<T>(n, width, pitch, g)) return rc;
-        if (!beam || !last_action || !live || !active || !code || !flags || !keys) return fail("rc_search_expand: null buffer");
-        if (!aligned16(beam) || !aligned16(last_action) || !aligned16(code) || !aligned16(flags) || !aligned16(keys))
-            return fail("rc_search_expand: buffers must be 16-byte aligned");
+        if (any_null(beam, last_action, live, active, code, flags, keys)) return fail("rc_search_expand: null buffer");
+        if (!all_aligned16(beam, last_action, code, flags, keys)) return fail("rc_search_expand: buffers must be 16-byte aligned");
         const ExpandArgs a{beam, last_action, live, active, code, flags, keys, g.nb, g.nbp, pitch, width, g.shift};
         hipLaunchKernelGGL((k_expand<T>), dim3((unsigned)(g.nbp / kSpan)), dim3(kWave), 0, S(stream), a);
         RCS_HIP(hipGetLastError());
@@ -565,16 +634,17 @@ int rc_search_select(uint8_t *flags, const uint64_t *keys, const float *scores, 
         using T = decltype(t);
         Geo g;
         if (int rc = geometry<T>(n, width, pitch, g)) return rc;
-        if (!flags || !keys || !scores || !live || !active || !length || !solution || !depth || !sel_parent || !sel_action || !sel_count || !workspace)
+        if (any_null(flags, keys, scores, live, active, length, solution, depth, sel_parent, sel_action, sel_count, workspace))
             return fail("rc_search_select: null buffer");
         if (!aligned16(workspace)) return fail("rc_search_select: workspace must be 16-byte aligned");
         const int64_t slots = table_slots(T::A, n, width);
         if (workspace_bytes < slots * 8) return fail("rc_search_select: workspace smaller than rc_search_workspace_bytes()");
         if (n > 0x7fffffff) return fail("rc_search_select: too many problems for one launch");
-        const SelectArgs a{flags, keys, scores, live, active, length, solution, depth, sel_parent, sel_action, sel_count,
-                           static_cast<unsigned long long *>(workspace), (uint64_t)(slots - 1), g.nbp, width};
+        const Cands c{flags, keys, scores, live, active, length, solution, static_cast<unsigned long long *>(workspace), (uint64_t)(slots - 1),
+                      g.nbp, width};
+        const SelectArgs a{c, depth, sel_parent, sel_action, sel_count};
         RCS_HIP(hipMemsetAsync(workspace, 0xFF, (size_t)slots * 8, S(stream)));       // every slot kEmpty
-        hipLaunchKernelGGL((k_insert<T>), dim3((unsigned)((T::A * g.nbp + 255) / 256)), dim3(256), 0, S(stream), a);
+        hipLaunchKernelGGL((k_insert<T>), dim3((unsigned)((T::A * g.nbp + 255) / 256)), dim3(256), 0, S(stream), c);
         RCS_HIP(hipGetLastError());
         hipLaunchKernelGGL((k_select<T>), dim3((unsigned)n), dim3(kSelThreads), 0, S(stream), a);
         RCS_HIP(hipGetLastError());
@@ -589,7 +659,7 @@ int rc_search_advance(const uint8_t *beam_in, uint8_t *beam_out, int64_t n, int 
         using T = decltype(t);
         Geo g;
         if (int rc = geometry<T>(n, width, pitch, g)) return rc;
-        if (!beam_in || !beam_out || !sel_parent || !sel_action || !sel_count || !live || !last_action || !hist_parent || !hist_action || !depth)
+        if (any_null(beam_in, beam_out, sel_parent, sel_action, sel_count, live, last_action, hist_parent, hist_action, depth))
             return fail("rc_search_advance: null buffer");
         if (max_depth < 1) return fail("rc_search_advance: max_depth must be >= 1");
         if (!aligned16(beam_out)) return fail("rc_search_advance: beam_out must be 16-byte aligned");
@@ -609,7 +679,7 @@ int rc_search_backtrack(const uint16_t *hist_parent, const uint8_t *hist_action,
         using T = decltype(t);
         Geo g;
         if (int rc = geometry<T>(n, width, pitch, g)) return rc;
-        if (!hist_parent || !hist_action || !length || !solution || !actions) return fail("rc_search_backtrack: null buffer");
+        if (any_null(hist_parent, hist_action, length, solution, actions)) return fail("rc_search_backtrack: null buffer");
         if (max_depth < 1) return fail("rc_search_backtrack: max_depth must be >= 1");
         hipLaunchKernelGGL(k_backtrack, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, S(stream), hist_parent, hist_action, n, width, g.nbp,
                            T::A, max_depth, length, solution, actions);
@@ -625,7 +695,7 @@ int rc_search_backtrack(const uint16_t *hist_parent, const uint8_t *hist_action,
 //   k_astar_init       root -> node 0 of every problem's pool (open, prio +inf), its key into the persistent table
 //   k_astar_pop        one workgroup per problem: radix select of the B best open nodes (prio desc, node index desc), closed and
 //                      gathered in ascending node index into the beam
-//   k_insert           (the beam's, unchanged) the iteration's valid candidates into the scratch table: equal keys keep the lowest c
+//   k_insert           (the beam's) the iteration's valid candidates into the scratch table: equal keys keep the lowest c
 //   k_astar_merge      one workgroup per problem: solved check, new = owner of its scratch slot and key absent from the persistent
 //                      table, the new candidates appended in ascending c, their keys into the persistent table
 //   k_astar_backtrack  parent links -> actions [D][P]
@@ -650,21 +720,6 @@ struct Pool {
     int32_t cap;
 };
 
-__device__ __forceinline__ uint64_t block_min64(uint64_t v, uint64_t *red) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const uint64_t w = ((uint64_t)(uint32_t)__shfl_xor((int)(v >> 32), o) << 32) | (uint32_t)__shfl_xor((int)(uint32_t)v, o);
-        v = w < v ? w : v;
-    }
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    uint64_t r = red[0];
-#pragma unroll
-    for (int q = 1; q < 4; ++q) r = red[q] < r ? red[q] : r;
-    __syncthreads();
-    return r;
-}
-
 // node `gid` of the pool holds key k
 template <class T>
 __device__ __forceinline__ bool node_has_key(const Pool &o, int64_t gid, const uint64_t (&k)[Key<T>::KW]) {
@@ -687,22 +742,14 @@ __global__ void __launch_bounds__(256) k_astar_init(const uint8_t *roots, int64_
     const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (p >= n) return;
     const int64_t gid = p * o.cap;
-    const uint8_t *src = roots + (rshift >= 63 ? p : tiled(p, rpitch, rshift, T::S));
-    uint8_t *dst = o.stickers + tiled(gid, o.ppitch, o.pshift, T::S);
-    bool solved = true;
-    uint8_t first = 0;
     uint64_t k[K::KW] = {};
     int kk = 0;
-    for (int i = 0; i < T::S; ++i) {
-        const uint8_t v = src[(int64_t)i * rpitch];
-        dst[(int64_t)i * o.ppitch] = v;
-        if (i % T::FACE == 0) first = v;
-        else solved = solved && v == first;
+    const bool solved = copy_root<T>(roots, p, rpitch, rshift, o.stickers + tiled(gid, o.ppitch, o.pshift, T::S), o.ppitch, [&](int i, uint8_t v) {
         if (!(T::SIZE == 3 && i % 9 == 4)) {                   // Key<T>::sticker enumerates the non-centre stickers in ascending order
             k[kk / 16] |= (uint64_t)(v & 7u) << (3 * (kk % 16));
             ++kk;
         }
-    }
+    });
 #pragma unroll
     for (int x = 0; x < K::KW; ++x) o.keys[(int64_t)x * o.np + gid] = k[x];
     o.parent[gid] = -1;
@@ -742,16 +789,15 @@ struct PopArgs {
 // One workgroup per problem.  Ranks are distinct (the node index is their low word), so the radix select keeps exactly B nodes.
 template <class T>
 __global__ void __launch_bounds__(kSelThreads) k_astar_pop(PopArgs a) {
-    __shared__ uint32_t red[4];
     const PopArgs &o = a;
     const int64_t p = blockIdx.x;
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int tid = threadIdx.x;
     if (!a.active[p]) return;
     const int64_t g0 = p * o.cap;
     const uint32_t n = (uint32_t)min(max(o.count[p], 0), o.cap), B = (uint32_t)a.batch;
     uint32_t cnt = 0;
     for (uint32_t i = tid; i < n; i += kSelThreads) cnt += o.state[g0 + i] == kOpen;
-    const uint32_t nopen = block_sum(cnt, red);
+    const uint32_t nopen = block_reduce(cnt, Sum{});
     if (nopen == 0) {                                          // exhausted: length stays -1
         if (tid == 0) {
             a.active[p] = 0;
@@ -767,37 +813,24 @@ __global__ void __launch_bounds__(kSelThreads) k_astar_pop(PopArgs a) {
             r = rank_of(o.prio[g0 + i], 0xFFFFFFFFu - i);
             return true;
         });
-    uint32_t base = 0;
-    for (uint32_t i0 = 0; i0 < n; i0 += kSelThreads) {         // the popped nodes in ascending node index
-        const uint32_t i = i0 + tid;
-        const bool keep = i < n && o.state[g0 + i] == kOpen && (nopen <= B || rank_of(o.prio[g0 + i], 0xFFFFFFFFu - i) >= thr);
-        const unsigned long long bal = __ballot(keep);
-        if (lane == 0) red[wv] = (uint32_t)__popcll(bal);
-        __syncthreads();
-        uint32_t off = base;
-        for (int q = 0; q < wv; ++q) off += red[q];
-        const uint32_t tot = red[0] + red[1] + red[2] + red[3];
-        if (keep) {
-            const uint32_t slot = off + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
-            if (slot < B) {
-                const int64_t b = p * a.batch + slot;
-                o.state[g0 + i] = kClosed;
-                a.pop_node[b] = (int32_t)i;
-                a.last_action[b] = o.action[g0 + i];
-                const uint8_t *src = o.stickers + tiled(g0 + i, o.ppitch, o.pshift, T::S);
-                uint8_t *dst = a.beam + tiled(b, a.pitch, a.shift, T::S);
+    const uint32_t npop = ordered_compact(                     // the popped nodes in ascending node index
+        n, [&](uint32_t i) { return o.state[g0 + i] == kOpen && (nopen <= B || rank_of(o.prio[g0 + i], 0xFFFFFFFFu - i) >= thr); },
+        [&](uint32_t i, uint32_t slot) {
+            if (slot >= B) return;
+            const int64_t b = p * a.batch + slot;
+            o.state[g0 + i] = kClosed;
+            a.pop_node[b] = (int32_t)i;
+            a.last_action[b] = o.action[g0 + i];
+            const uint8_t *src = o.stickers + tiled(g0 + i, o.ppitch, o.pshift, T::S);
+            uint8_t *dst = a.beam + tiled(b, a.pitch, a.shift, T::S);
 #pragma unroll
-                for (int s = 0; s < T::S; ++s) dst[(int64_t)s * a.pitch] = src[(int64_t)s * o.ppitch];
-            }
-        }
-        base += tot;
-        __syncthreads();
-    }
-    if (tid == 0) a.live[p] = (int32_t)min(base, B);
+            for (int s = 0; s < T::S; ++s) dst[(int64_t)s * a.pitch] = src[(int64_t)s * o.ppitch];
+        });
+    if (tid == 0) a.live[p] = (int32_t)min(npop, B);
 }
 
 struct MergeArgs {
-    SelectArgs s;                 // the iteration's candidates and the scratch table k_insert filled
+    Cands s;                      // the iteration's candidates and the scratch table k_insert filled
     Pool o;
     const int32_t *iteration, *pop_node;
     int32_t *ended;
@@ -812,12 +845,10 @@ __device__ __forceinline__ int32_t popped(const MergeArgs &a, int64_t p, uint32_
 template <class T>
 __global__ void __launch_bounds__(kSelThreads) k_astar_merge(MergeArgs a) {
     using K = Key<T>;
-    __shared__ uint32_t red[4];
-    __shared__ uint64_t red64[4];
-    const SelectArgs &s = a.s;
+    const Cands &s = a.s;
     const Pool &o = a.o;
     const int64_t p = blockIdx.x;
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int tid = threadIdx.x;
     if (!s.active[p]) return;
     const int64_t g0 = p * o.cap;
     const uint32_t M = (uint32_t)min(max(s.live[p], 0), s.width) * T::A;
@@ -831,7 +862,7 @@ __global__ void __launch_bounds__(kSelThreads) k_astar_merge(MergeArgs a) {
             best = v < best ? v : best;
         }
     }
-    best = block_min64(best, red64);
+    best = block_reduce(best, Min{});
     if (best != ~0ull) {
         if (tid == 0) {
             const uint32_t c = (uint32_t)best;
@@ -851,19 +882,7 @@ __global__ void __launch_bounds__(kSelThreads) k_astar_merge(MergeArgs a) {
         const uint8_t f = s.flags[j];
         if (!(f & RC_SEARCH_VALID)) continue;
         uint64_t k[K::KW];
-        load_key<T>(s, j, k);
-        const uint64_t id = ((uint64_t)p << 32) | c;
-        const uint64_t h0 = slot_of<T>(k, p, s.tmask);
-        bool owner = false;
-        for (uint64_t h = h0;; h = (h + 1) & s.tmask) {
-            const uint64_t v = s.table[h];
-            if (v == kEmpty) break;                            // cannot happen: every valid candidate was inserted
-            if (same_key<T>(s, v, k, p)) {
-                owner = v == id;
-                break;
-            }
-        }
-        if (!owner) continue;
+        if (!owns_key<T>(s, p, c, j, k)) continue;
         bool known = false;
         for (uint64_t h = slot_of<T>(k, p, o.tmask);; h = (h + 1) & o.tmask) {
             const uint64_t v = o.table[h];
@@ -878,59 +897,41 @@ __global__ void __launch_bounds__(kSelThreads) k_astar_merge(MergeArgs a) {
     __syncthreads();
     // 3. append in ascending c: node count + r = the r-th new candidate, while the pool has room
     const uint32_t room = (uint32_t)(o.cap - count);
-    uint32_t base = 0;
-    for (uint32_t c0 = 0; c0 < M; c0 += kSelThreads) {
-        const uint32_t c = c0 + tid;
-        int64_t j = 0;
-        bool isnew = false;
-        if (c < M) {
-            j = cand_j<T>(s, p, c);
-            isnew = (s.flags[j] & RCA_NEW) != 0;
-        }
-        const unsigned long long bal = __ballot(isnew);
-        if (lane == 0) red[wv] = (uint32_t)__popcll(bal);
-        __syncthreads();
-        uint32_t off = base;
-        for (int q = 0; q < wv; ++q) off += red[q];
-        const uint32_t tot = red[0] + red[1] + red[2] + red[3];
-        if (isnew) {
-            const uint32_t r = off + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
-            if (r < room) {
-                const int64_t gid = g0 + count + r;
-                const int32_t par = popped(a, p, c / T::A, count);
-                uint64_t k[K::KW];
-                load_key<T>(s, j, k);
-                // the child's stickers are its key's 3-bit fields; a centre (3x3x3) never moves: the parent's
-                const uint8_t *src = o.stickers + tiled(g0 + par, o.ppitch, o.pshift, T::S);
-                uint8_t *dst = o.stickers + tiled(gid, o.ppitch, o.pshift, T::S);
-                sfor<T::S>([&](auto ic) {
-                    constexpr int i = decltype(ic)::value;
-                    if constexpr (T::SIZE == 3 && i % 9 == 4) dst[(int64_t)i * o.ppitch] = src[(int64_t)i * o.ppitch];
-                    else {
-                        constexpr int kk = T::SIZE == 3 ? (i / 9) * 8 + (i % 9 < 4 ? i % 9 : i % 9 - 1) : i;
-                        static_assert(K::sticker(kk) == i);
-                        dst[(int64_t)i * o.ppitch] = (uint8_t)((k[kk / 16] >> (3 * (kk % 16))) & 7u);
-                    }
-                });
+    const uint32_t nnew = ordered_compact(
+        M, [&](uint32_t c) { return (s.flags[cand_j<T>(s, p, c)] & RCA_NEW) != 0; },
+        [&](uint32_t c, uint32_t r) {
+            if (r >= room) return;
+            const int64_t j = cand_j<T>(s, p, c), gid = g0 + count + r;
+            const int32_t par = popped(a, p, c / T::A, count);
+            uint64_t k[K::KW];
+            load_key<T>(s, j, k);
+            // the child's stickers are its key's 3-bit fields; a centre (3x3x3) never moves: the parent's
+            const uint8_t *src = o.stickers + tiled(g0 + par, o.ppitch, o.pshift, T::S);
+            uint8_t *dst = o.stickers + tiled(gid, o.ppitch, o.pshift, T::S);
+            sfor<T::S>([&](auto ic) {
+                constexpr int i = decltype(ic)::value;
+                if constexpr (T::SIZE == 3 && i % 9 == 4) dst[(int64_t)i * o.ppitch] = src[(int64_t)i * o.ppitch];
+                else {
+                    constexpr int kk = T::SIZE == 3 ? (i / 9) * 8 + (i % 9 < 4 ? i % 9 : i % 9 - 1) : i;
+                    static_assert(K::sticker(kk) == i);
+                    dst[(int64_t)i * o.ppitch] = (uint8_t)((k[kk / 16] >> (3 * (kk % 16))) & 7u);
+                }
+            });
 #pragma unroll
-                for (int x = 0; x < K::KW; ++x) o.keys[(int64_t)x * o.np + gid] = k[x];
-                const int32_t g = o.g[g0 + par] + 1;
-                const float sc = s.scores[j];
-                o.parent[gid] = par;
-                o.action[gid] = (uint8_t)(c % T::A);
-                o.g[gid] = g;
-                o.score[gid] = sc;
-                o.prio[gid] = __fsub_rn(sc, __fmul_rn(a.weight, (float)g));   // two roundings, never an fma: numpy float32 bit for bit
-                o.state[gid] = kOpen;
-                table_put(o, slot_of<T>(k, p, o.tmask), gid);
-            }
-        }
-        base += tot;
-        __syncthreads();
-    }
+            for (int x = 0; x < K::KW; ++x) o.keys[(int64_t)x * o.np + gid] = k[x];
+            const int32_t g = o.g[g0 + par] + 1;
+            const float sc = s.scores[j];
+            o.parent[gid] = par;
+            o.action[gid] = (uint8_t)(c % T::A);
+            o.g[gid] = g;
+            o.score[gid] = sc;
+            o.prio[gid] = __fsub_rn(sc, __fmul_rn(a.weight, (float)g));   // two roundings, never an fma: numpy float32 bit for bit
+            o.state[gid] = kOpen;
+            table_put(o, slot_of<T>(k, p, o.tmask), gid);
+        });
     if (tid == 0) {
-        o.count[p] = count + (int32_t)min(base, room);
-        if (base > room) o.overflow[p] = 1;
+        o.count[p] = count + (int32_t)min(nnew, room);
+        if (nnew > room) o.overflow[p] = 1;
     }
 }
 
@@ -951,12 +952,11 @@ __global__ void __launch_bounds__(256) k_astar_backtrack(const int32_t *parent, 
     }
 }
 
-int64_t astar_slots(int64_t n_problems, int64_t capacity) {
-    const int64_t need = 2 * n_problems * capacity;
-    int64_t s = 1024;
-    while (s < need) s <<= 1;
-    return s;
+// node indices, and gids p * C + n, are int32
+bool pool_limits(int64_t n, int64_t capacity) {
+    return n >= 1 && capacity >= 1 && n < ((int64_t)1 << 31) && capacity < ((int64_t)1 << 31) && n * capacity < ((int64_t)1 << 31);
 }
+const char kPoolLimits[] = "need n_problems >= 1, capacity >= 1 and n_problems * capacity < 2^31";
 
 struct PoolGeo {
     int pshift;
@@ -965,27 +965,25 @@ struct PoolGeo {
 // the pool of P problems x C nodes at pool_pitch, and its table
 template <class T>
 int pool_geometry(int64_t n, int64_t capacity, int64_t pool_pitch, PoolGeo &g) {
-    if (n < 1 || capacity < 1 || capacity >= ((int64_t)1 << 31) || n >= ((int64_t)1 << 31) || n * capacity >= ((int64_t)1 << 31))
-        return fail("need n_problems >= 1, capacity >= 1 and n_problems * capacity < 2^31");
+    if (!pool_limits(n, capacity)) return fail(kPoolLimits);
     if (pool_pitch < 512 || (pool_pitch & (pool_pitch - 1)) != 0 || pool_pitch * T::S >= ((int64_t)1 << 32))
         return fail("pool_pitch must be a power of two >= 512 with S * pool_pitch < 2^32");
     g.pshift = log2_exact(pool_pitch);
-    g.slots = astar_slots(n, capacity);
+    g.slots = pow2_slots(2 * n * capacity);
     return 0;
 }
 
-template <class... P>
-bool any_null(P... p) { return (... || (p == nullptr)); }
-template <class... P>
-bool all_aligned16(P... p) { return (... && aligned16(p)); }
+Pool make_pool(uint8_t *stickers, uint64_t *keys, int32_t *parent, uint8_t *action, int32_t *g, float *score, float *prio, uint8_t *state,
+               int32_t *count, uint8_t *overflow, void *table, const PoolGeo &pg, int64_t n, int64_t capacity, int64_t pool_pitch) {
+    return Pool{stickers, keys, parent, action, g, score, prio, state, count, overflow, static_cast<unsigned long long *>(table),
+                (uint64_t)(pg.slots - 1), n * capacity, pool_pitch, pg.pshift, (int32_t)capacity};
+}
 
 }  // namespace
 
 int64_t rca_workspace_bytes(int cube_size, int64_t n_problems, int64_t capacity) {
-    if ((cube_size != 2 && cube_size != 3) || n_problems < 1 || capacity < 1 || n_problems >= ((int64_t)1 << 31) ||
-        capacity >= ((int64_t)1 << 31) || n_problems * capacity >= ((int64_t)1 << 31))
-        return -1;
-    return astar_slots(n_problems, capacity) * 8;
+    if ((cube_size != 2 && cube_size != 3) || !pool_limits(n_problems, capacity)) return -1;
+    return pow2_slots(2 * n_problems * capacity) * 8;
 }
 
 int rca_init(const uint8_t *roots, int64_t n, int64_t root_pitch, int cube_size, int64_t capacity, int64_t pool_pitch, uint8_t *pool_stickers,
@@ -1003,14 +1001,10 @@ int rca_init(const uint8_t *roots, int64_t n, int64_t root_pitch, int cube_size,
                            live, active, length, solution, ended, table))
             return fail("rca_init: buffers must be 16-byte aligned");
         if (table_bytes < pg.slots * 8) return fail("rca_init: table smaller than rca_workspace_bytes()");
-        int rshift = 63;                                       // roots: as rc_search_init
-        if (root_pitch <= 0 || (root_pitch & 15) != 0 || root_pitch * T::S >= ((int64_t)1 << 32)) return fail("rca_init: bad root_pitch");
-        if (n > root_pitch) {
-            if (root_pitch < 512 || (root_pitch & (root_pitch - 1)) != 0) return fail("rca_init: several root tiles need a power-of-two pitch >= 512");
-            rshift = log2_exact(root_pitch);
-        }
-        const Pool o{pool_stickers, pool_keys, pool_parent, pool_action, pool_g, pool_score, pool_prio, pool_state, count, overflow,
-                     static_cast<unsigned long long *>(table), (uint64_t)(pg.slots - 1), n * capacity, pool_pitch, pg.pshift, (int32_t)capacity};
+        int rshift;
+        if (int rc = root_layout<T>("rca_init", n, root_pitch, rshift)) return rc;
+        const Pool o = make_pool(pool_stickers, pool_keys, pool_parent, pool_action, pool_g, pool_score, pool_prio, pool_state, count, overflow,
+                                 table, pg, n, capacity, pool_pitch);
         RCS_HIP(hipMemsetAsync(table, 0xFF, (size_t)pg.slots * 8, S(stream)));           // every slot kEmpty, once per search
         hipLaunchKernelGGL((k_astar_init<T>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, S(stream), roots, n, root_pitch, rshift, o, live,
                            active, length, solution, ended);
@@ -1061,11 +1055,11 @@ int rca_merge(int64_t n, int cube_size, int batch, int64_t pitch, int64_t capaci
         const int64_t sslots = table_slots(T::A, n, batch);
         if (table_bytes < pg.slots * 8) return fail("rca_merge: table smaller than rca_workspace_bytes()");
         if (scratch_bytes < sslots * 8) return fail("rca_merge: scratch smaller than rc_search_workspace_bytes()");
-        const SelectArgs s{flags, keys, scores, live, active, length, solution, nullptr, nullptr, nullptr, nullptr,
-                           static_cast<unsigned long long *>(scratch), (uint64_t)(sslots - 1), g.nbp, batch};
-        const Pool o{pool_stickers, pool_keys, pool_parent, pool_action, pool_g, pool_score, pool_prio, pool_state, count, overflow,
-                     static_cast<unsigned long long *>(table), (uint64_t)(pg.slots - 1), n * capacity, pool_pitch, pg.pshift, (int32_t)capacity};
-        const MergeArgs a{s, o, iteration, pop_node, ended, weight};
+        const Cands s{flags, keys, scores, live, active, length, solution, static_cast<unsigned long long *>(scratch), (uint64_t)(sslots - 1),
+                      g.nbp, batch};
+        const MergeArgs a{s, make_pool(pool_stickers, pool_keys, pool_parent, pool_action, pool_g, pool_score, pool_prio, pool_state, count, overflow,
+                                       table, pg, n, capacity, pool_pitch),
+                          iteration, pop_node, ended, weight};
         RCS_HIP(hipMemsetAsync(scratch, 0xFF, (size_t)sslots * 8, S(stream)));
         hipLaunchKernelGGL((k_insert<T>), dim3((unsigned)((T::A * g.nbp + 255) / 256)), dim3(256), 0, S(stream), s);
         RCS_HIP(hipGetLastError());
@@ -1079,8 +1073,7 @@ int rca_backtrack(int64_t n, int cube_size, int64_t capacity, const int32_t *poo
                   const int32_t *solution, uint8_t *actions, int max_length, void *stream) {
     return by_size(cube_size, [&](auto t) {
         using T = decltype(t);
-        if (n < 1 || capacity < 1 || n >= ((int64_t)1 << 31) || capacity >= ((int64_t)1 << 31) || n * capacity >= ((int64_t)1 << 31))
-            return fail("need n_problems >= 1, capacity >= 1 and n_problems * capacity < 2^31");
+        if (!pool_limits(n, capacity)) return fail(kPoolLimits);
         if (max_length < 1) return fail("rca_backtrack: max_length must be >= 1");
         if (any_null(pool_parent, pool_action, length, solution, actions)) return fail("rca_backtrack: null buffer");
         if (!all_aligned16(pool_parent, pool_action, length, solution, actions)) return fail("rca_backtrack: buffers must be 16-byte aligned");

@@ -165,6 +165,47 @@ class BeamPlan:
         self.depth.add_(1)
 
 
+def _net_front(model, front, env):
+    """(model, dtype, hidden) a plan scores the cubes of `env` with: for front="codes" the model's CodeNet and its H1."""
+    from .adi import _module_dtype
+    if front not in ("dense", "codes"):
+        raise ValueError(f"front must be 'dense' or 'codes', got {front!r}")
+    if front == "dense":
+        return model, _module_dtype(model), None
+    from .codenet import CodeNet
+    model = model if isinstance(model, CodeNet) else CodeNet(model, env.cube_size)      # ValueError for a float16 model
+    if model.device != env.stickers.device:
+        raise ValueError(f"front='codes': the model is on {model.device}, the cubes on {env.stickers.device}")
+    return model, model.dtype, model.hidden
+
+
+def _run_steps(step, n_steps, active, dev, graph, sync_every, key=lambda t: 0):
+    """The step loop of a search: step(key(t)) for t = 1..n_steps, until a host check every `sync_every` steps finds no problem
+    `active`.  graph=True: step 1 runs eagerly on a side stream (warm-up outside capture: libraries pick their kernels there), every
+    later step replays a hipGraph captured once per key.  Returns how many steps ran."""
+    graphs, ran = {}, 0
+    for t in range(1, n_steps + 1):
+        k = key(t)
+        if not graph:
+            step(k)
+        elif t == 1:
+            s = torch.cuda.Stream(dev)
+            s.wait_stream(torch.cuda.current_stream(dev))
+            with torch.cuda.stream(s):
+                step(k)
+            torch.cuda.current_stream(dev).wait_stream(s)
+        else:
+            if k not in graphs:
+                graphs[k] = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(graphs[k]):              # capture does not execute
+                    step(k)
+            graphs[k].replay()
+        ran = t
+        if t % sync_every == 0 and not bool(active.any()):
+            break
+    return ran
+
+
 @torch.no_grad()
 def beam_search(model, env, width, max_depth, *, dense_budget_bytes=1 << 30, sync_every=4, graph=False, front="dense"):
     """Beam search from every cube of `env` (a VecCubeEnv, any observation mode; its state is left unchanged).
@@ -178,41 +219,10 @@ def beam_search(model, env, width, max_depth, *, dense_budget_bytes=1 << 30, syn
 
     Returns dict(solved bool [P], length int32 [P] (0: the root was solved, -1: not solved within max_depth), actions uint8
     [max_depth, P]: the solution's moves, then the no-op action_dim)."""
-    from .adi import _module_dtype
-    P, cs = env.num_envs, env.cube_size
-    dtype = _module_dtype(model)
-    if front == "codes":
-        from .codenet import CodeNet
-        model = model if isinstance(model, CodeNet) else CodeNet(model, cs)      # ValueError for a float16 model
-        dtype = model.dtype
-        if model.device != env.stickers.device:
-            raise ValueError(f"front='codes': the model is on {model.device}, the cubes on {env.stickers.device}")
-        plan = BeamPlan(P, cs, width, max_depth, env.device, dtype, dense_budget_bytes, front="codes", hidden=model.hidden)
-    else:
-        if front != "dense":
-            raise ValueError(f"front must be 'dense' or 'codes', got {front!r}")
-        plan = BeamPlan(P, cs, width, max_depth, env.device, dtype, dense_budget_bytes)
+    model, dtype, hidden = _net_front(model, front, env)
+    plan = BeamPlan(env.num_envs, env.cube_size, width, max_depth, env.device, dtype, dense_budget_bytes, front, hidden)
     plan.init(env.stickers, env.stickers.shape[-1])
-    graphs = {}
-    for t in range(1, plan.D + 1):
-        parity = (t - 1) & 1
-        if not graph:
-            plan.step(model, parity)
-        elif t == 1:                                           # warm-up outside capture (libraries pick their kernels here)
-            s = torch.cuda.Stream(plan.dev)
-            s.wait_stream(torch.cuda.current_stream(plan.dev))
-            with torch.cuda.stream(s):
-                plan.step(model, parity)
-            torch.cuda.current_stream(plan.dev).wait_stream(s)
-        else:
-            if parity not in graphs:
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g):                      # capture does not execute
-                    plan.step(model, parity)
-                graphs[parity] = g
-            graphs[parity].replay()
-        if t % sync_every == 0 and not bool(plan.active.any()):
-            break
+    _run_steps(lambda parity: plan.step(model, parity), plan.D, plan.active, plan.dev, graph, sync_every, key=lambda t: (t - 1) & 1)
     if plan.D:
         plan.backtrack()
     actions = plan.actions[:plan.D]
@@ -229,6 +239,17 @@ def pool_node_bytes(cube_size):
     return S + 8 * KEY_WORDS[cube_size] + 4 + 1 + 4 + 4 + 4 + 1 + 32
 
 
+def _check_astar(n_problems, batch, weight, capacity):
+    """The ValueErrors of an A* shape; capacity None: astar_capacity() will choose it, within these limits by construction."""
+    import math
+    if not 1 <= int(batch) <= MAX_WIDTH:
+        raise ValueError(f"batch must be in 1..{MAX_WIDTH}")
+    if int(n_problems) < 1 or (capacity is not None and (int(capacity) < 1 or int(n_problems) * int(capacity) >= 1 << 31)):
+        raise ValueError("need n_problems >= 1, capacity >= 1 and n_problems * capacity < 2^31")
+    if not (math.isfinite(float(weight)) and float(weight) >= 0.0):
+        raise ValueError(f"weight must be finite and >= 0, got {weight!r}")
+
+
 class AStarPlan:
     """Device buffers of one batch-weighted A* shape (P problems, B nodes popped per iteration, pool capacity C) and the launches of one
     iteration.  Layouts and THE RULE: include/rubiksearch.h "Batch-weighted A*".  It owns a BeamPlan of width B (self.beam: expand,
@@ -236,13 +257,7 @@ class AStarPlan:
 
     def __init__(self, n_problems, cube_size, batch, capacity, device, dtype=torch.float32, dense_budget_bytes=1 << 30, front="dense",
                  hidden=None, weight=1.0):
-        import math
-        if not 1 <= int(batch) <= MAX_WIDTH:
-            raise ValueError(f"batch must be in 1..{MAX_WIDTH}")
-        if int(n_problems) < 1 or int(capacity) < 1 or int(n_problems) * int(capacity) >= 1 << 31:
-            raise ValueError("need n_problems >= 1, capacity >= 1 and n_problems * capacity < 2^31")
-        if not (math.isfinite(float(weight)) and float(weight) >= 0.0):
-            raise ValueError(f"weight must be finite and >= 0, got {weight!r}")
+        _check_astar(n_problems, batch, weight, capacity)
         if cube_size not in KEY_WORDS:
             raise ValueError(f"cube_size must be 2 or 3, got {cube_size!r}")
         self.beam = BeamPlan(n_problems, cube_size, batch, 0, device, dtype, dense_budget_bytes, front, hidden)   # its ValueErrors too
@@ -347,49 +362,16 @@ def astar_search(model, env, batch, max_iterations, *, weight=1.0, capacity=None
     L = max(1, length.max()): the solution's moves, then the no-op action_dim, iterations int32 [P]: the iteration at which the cube
     was solved or found exhausted (0: solved root; the number of iterations run for a cube still active at the end), nodes int32 [P],
     overflow bool [P], capacity int)."""
-    import math
-    from .adi import _module_dtype
     P, cs = env.num_envs, env.cube_size
-    if not 1 <= int(batch) <= MAX_WIDTH:
-        raise ValueError(f"batch must be in 1..{MAX_WIDTH}")
+    _check_astar(P, batch, weight, capacity)                   # before astar_capacity() and the model are touched; the plan repeats it
     if int(max_iterations) < 0 or int(sync_every) < 1:
         raise ValueError("need max_iterations >= 0 and sync_every >= 1")
-    if not (math.isfinite(float(weight)) and float(weight) >= 0.0):
-        raise ValueError(f"weight must be finite and >= 0, got {weight!r}")
-    if front not in ("dense", "codes"):
-        raise ValueError(f"front must be 'dense' or 'codes', got {front!r}")
     if capacity is None:
         capacity = astar_capacity(P, cs, batch, max_iterations)
-    if int(capacity) < 1 or P * int(capacity) >= 1 << 31:
-        raise ValueError("need capacity >= 1 and n_problems * capacity < 2^31")
-    dtype, hidden = _module_dtype(model), None
-    if front == "codes":
-        from .codenet import CodeNet
-        model = model if isinstance(model, CodeNet) else CodeNet(model, cs)      # ValueError for a float16 model
-        dtype, hidden = model.dtype, model.hidden
-        if model.device != env.stickers.device:
-            raise ValueError(f"front='codes': the model is on {model.device}, the cubes on {env.stickers.device}")
+    model, dtype, hidden = _net_front(model, front, env)
     plan = AStarPlan(P, cs, batch, capacity, env.device, dtype, dense_budget_bytes, front, hidden, weight)
     plan.init(env.stickers, env.stickers.shape[-1])
-    g, ran = None, 0
-    for t in range(1, int(max_iterations) + 1):
-        if not graph:
-            plan.step(model)
-        elif t == 1:                                           # warm-up outside capture (libraries pick their kernels here)
-            s = torch.cuda.Stream(plan.dev)
-            s.wait_stream(torch.cuda.current_stream(plan.dev))
-            with torch.cuda.stream(s):
-                plan.step(model)
-            torch.cuda.current_stream(plan.dev).wait_stream(s)
-        else:
-            if g is None:
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g):                      # capture does not execute
-                    plan.step(model)
-            g.replay()
-        ran = t
-        if t % sync_every == 0 and not bool(plan.beam.active.any()):
-            break
+    ran = _run_steps(lambda _: plan.step(model), int(max_iterations), plan.beam.active, plan.dev, graph, sync_every)
     length = plan.beam.length
     actions = plan.backtrack(max(1, int(length.max())))
     iterations = torch.where(plan.beam.active != 0, torch.full_like(plan.ended, ran), plan.ended)
@@ -457,19 +439,25 @@ def beam_search_symmetric(model, env, width, max_depth, symmetries="rotations", 
     return out
 
 
-@torch.no_grad()
-def beam_solve_percentage(model, cube_size, sample_scramble_count, sample_cube_count, width, max_depth, device="cuda", seeds=None,
-                          graph=False, front="dense"):
-    """rollout.solve_percentage with the beam search as the solver: for scramble_count = 1..sample_scramble_count, the percentage
-    of the sample_cube_count cubes (seeds i * 10, train.py:180) solved within max_depth.  All (k, seed) pairs run as ONE batch."""
+def _solve_percentage(solve, cube_size, sample_scramble_count, sample_cube_count, device, seeds):
+    """For scramble_count = 1..sample_scramble_count, the percentage of the sample_cube_count cubes (seeds i * 10, train.py:180) that
+    solve(env)["solved"] reports solved.  All (k, seed) pairs run as ONE batch."""
     from .vec_env import VecCubeEnv
     seeds = list(seeds) if seeds is not None else [i * 10 for i in range(sample_cube_count)]
     ks = [k for k in range(1, sample_scramble_count + 1) for _ in seeds]
     env = VecCubeEnv(len(ks), device, cube_size, obs=None)
     env.reset(seeds=seeds * sample_scramble_count, scramble_count=ks)
-    res = beam_search(model, env, width, max_depth, graph=graph, front=front)
-    solved = res["solved"].view(sample_scramble_count, len(seeds)).float().mean(1) * 100.0
+    solved = solve(env)["solved"].view(sample_scramble_count, len(seeds)).float().mean(1) * 100.0
     return [float(x) for x in solved.cpu()]
+
+
+@torch.no_grad()
+def beam_solve_percentage(model, cube_size, sample_scramble_count, sample_cube_count, width, max_depth, device="cuda", seeds=None,
+                          graph=False, front="dense"):
+    """rollout.solve_percentage with the beam search as the solver: for scramble_count = 1..sample_scramble_count, the percentage
+    of the sample_cube_count cubes (seeds i * 10, train.py:180) solved within max_depth.  All (k, seed) pairs run as ONE batch."""
+    return _solve_percentage(lambda env: beam_search(model, env, width, max_depth, graph=graph, front=front), cube_size,
+                             sample_scramble_count, sample_cube_count, device, seeds)
 
 
 @torch.no_grad()
@@ -477,11 +465,5 @@ def astar_solve_percentage(model, cube_size, sample_scramble_count, sample_cube_
                            weight=1.0, capacity=None, graph=False, front="dense"):
     """beam_solve_percentage with astar_search as the solver: for scramble_count = 1..sample_scramble_count, the percentage of the
     sample_cube_count cubes (seeds i * 10, train.py:180) solved within max_iterations.  All (k, seed) pairs run as ONE batch."""
-    from .vec_env import VecCubeEnv
-    seeds = list(seeds) if seeds is not None else [i * 10 for i in range(sample_cube_count)]
-    ks = [k for k in range(1, sample_scramble_count + 1) for _ in seeds]
-    env = VecCubeEnv(len(ks), device, cube_size, obs=None)
-    env.reset(seeds=seeds * sample_scramble_count, scramble_count=ks)
-    res = astar_search(model, env, batch, max_iterations, weight=weight, capacity=capacity, graph=graph, front=front)
-    solved = res["solved"].view(sample_scramble_count, len(seeds)).float().mean(1) * 100.0
-    return [float(x) for x in solved.cpu()]
+    return _solve_percentage(lambda env: astar_search(model, env, batch, max_iterations, weight=weight, capacity=capacity, graph=graph,
+                                                      front=front), cube_size, sample_scramble_count, sample_cube_count, device, seeds)

@@ -29,6 +29,19 @@ def test_header_exports_and_signature_table_agree():
     assert (_astar_lib.OPEN, _astar_lib.CLOSED, _astar_lib.NEW) == (R.OPEN, R.CLOSED, R.NEW)
 
 
+def test_an_extension_names_what_the_library_lacks():
+    """_native.extension, the loader behind astar_lib / sym_lib / episode_lib: a signature table with a function the library does
+    not export raises, naming that function (and no other) and the library's path; the real loaders all hand out ONE object."""
+    from rubiks_cube_solver_amd import _astar_lib, _native, _search_lib, _sym_lib
+    loader = _native.extension(_search_lib.search_lib, {**_astar_lib.ASTAR_SIGNATURES, "rca_no_such_function": []}, "search")
+    for _ in range(2):                                                       # a failed call leaves nothing behind
+        with pytest.raises(_native.RubikHipError) as e:
+            loader()
+        assert "rca_no_such_function" in str(e.value) and _search_lib.LIB_PATH in str(e.value) and "rca_init" not in str(e.value)
+    L = _search_lib.search_lib()
+    assert _astar_lib.astar_lib() is L and _sym_lib.sym_lib() is L and _astar_lib.astar_lib() is _astar_lib.astar_lib()
+
+
 def test_workspace_bytes():
     from rubiks_cube_solver_amd import _astar_lib
     wb = _astar_lib.workspace_bytes
