@@ -385,6 +385,53 @@ const char *rc_last_error(void);
 #define RC_VARIANT_LEGACY_LDS 1                       /* the LDS form alone */
 #define RC_VARIANT_LEGACY_STREAM(limit) (2 + 16 * (limit)) /* the streaming form with `limit` outputs per lane (1..623; 0 = 623) + fix-up */
 
+/* ---------------------------------------------------------------------------------------------------------------------------------
+ * Cubie coordinates (prefix rcc_): the cube as pieces.  No reference counterpart: the reference's only piece-level view is getOP_3
+ * (py333.py:224-227 = RC_FMT_CODE), whose corner table is incomplete and not injective; the bytes below are exact for ANY colouring.
+ *
+ * THE RULE.  Slots and pieces are numbered as rc_get_tables' corner_defs / edge_defs: piece q is the cubie that sits in slot q of the
+ * solved cube.  One byte per slot, SLOTS = 20 | 7 rows, corner slots first, tiled like an RC_FMT_CODE buffer:
+ *   edge     piece * 2 + ori   -- DEFINED as RC_FMT_CODE's edge byte: ori = 0 when the piece's first colour (edge_defs order of its home
+ *                              slot) shows on the slot's first sticker;
+ *   corner   piece * 3 + ori   -- ori = the number of clockwise steps, seen from outside the cube looking at that corner, from the slot's
+ *                              U/D-face sticker to the sticker that shows the piece's U/D colour.  The handedness of every slot comes from
+ *                              the cube's geometry (rcc_tables corner_cw), not from the listing order of corner_defs, which mixes
+ *                              handedness.  This is deliberately NOT RC_FMT_CODE's corner byte;
+ *   0xFF     the slot's colours are no cubie: two equal or opposite colours, a mirror-image corner, a value above 5.
+ * status, one byte per cube, is 0 exactly when the state can be reached from the solved cube by the env's moves: */
+#define RCC_BAD_COLOUR 1u  /* a sticker value is above 5 */
+#define RCC_BAD_FIXED 2u   /* a sticker the moves never touch differs from solved: the 6 centres | the 3 stickers of the 2x2x2's DLB cubie */
+#define RCC_BAD_PIECE 4u   /* some slot reads 0xFF */
+#define RCC_DUP_PIECE 8u   /* a piece occurs twice (among the slots that name one) */
+#define RCC_TWIST 16u      /* the sum of the corner ori is not 0 mod 3 */
+#define RCC_FLIP 32u       /* the sum of the edge ori is odd (3x3x3 only) */
+#define RCC_PARITY 64u     /* corner-permutation parity != edge-permutation parity, both relative to solved (3x3x3 only) */
+/* Bits 16..64 are evaluated only when bits 1..8 are clear, and are 0 otherwise.
+ * Indices, NC = 8 | 7:
+ *   corner_index = lehmer(corner pieces) * 3^(NC-1) + sum_{q < NC-1} ori[q] * 3^q,  lehmer = sum_q #{r > q : piece[r] < piece[q]} * (NC-1-q)!
+ *                  (below 88 179 840 | 3 674 160);
+ *   edge_index   = lehmer(edge pieces) * 2^11 + sum_{q < 11} ori[q] * 2^q  (below 479 001 600 * 2048; 3x3x3 only);
+ * both all-ones when status != 0.  On the 2x2x2, corner_index alone is a bijection from the group onto 0 .. 3 674 159.
+ *
+ * Conventions as above: caller-owned device memory, stream-ordered, nothing allocated; RC_EINVAL before any launch (rc_last_error names
+ * the operand); pad columns and every byte outside the rows keep their bytes; n_cubes == 0 succeeds without a launch; every pointer
+ * needs 16-byte alignment and no more.
+ *
+ * rcc_cubies: one launch, whichever outputs are asked for.  cubies [tiles][SLOTS][cubie_pitch], status [n_cubes], corner_index
+ * [n_cubes], edge_index [n_cubes]: each may be NULL, not all four; edge_index must be NULL for cube_size 2. */
+int rcc_cubies(const uint8_t *st, int64_t n_cubes, int64_t pitch, int cube_size, uint8_t *cubies, int64_t cubie_pitch,
+               uint8_t *status, uint32_t *corner_index, uint64_t *edge_index, void *stream);
+/* The inverse: all S stickers of cubes < n_cubes from their cubie rows; centres and the DLB stickers come out solved.  It does NOT
+ * require a legal assembly: a twisted corner or a repeated piece is written as given.  A byte that names no (piece, ori) -- a corner
+ * byte >= 3 * NC, an edge byte >= 24 -- cannot raise on the device: that cube is written as solved and *bad (one device byte the
+ * caller zeroes and reads, required) is set to 1, the idea of RC_STATUS_BAD_ACTION. */
+int rcc_from_cubies(const uint8_t *cubies, int64_t n_cubes, int64_t cubie_pitch, int cube_size, uint8_t *st, int64_t pitch,
+                    uint8_t *bad, void *stream);
+/* Host copies of the rule's tables, no device (any pointer may be NULL): corner_cw [NC][3] the stickers of each corner slot clockwise
+ * seen from outside, the U/D sticker first; edge_facelets [NE][2] = edge_defs; corner_colours [NC][3] / edge_colours [NE][2] the colours
+ * of piece p in the order of corner_cw[p] / edge_facelets[p]. */
+int rcc_tables(int cube_size, uint8_t *corner_cw, uint8_t *edge_facelets, uint8_t *corner_colours, uint8_t *edge_colours);
+
 #ifdef __cplusplus
 }
 #endif

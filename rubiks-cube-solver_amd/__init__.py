@@ -7,13 +7,16 @@ Drop-in surface for the env path of SUNGBEOMCHOI/Rubiks-Cube-Solver:
   get_env_config      (utils.py:162-186)
   CodeNet             the reference's DeepCube (model.py:7-45) evaluated from compact codes: no dense one-hot, HIP first layer
   ops                 batched operator layer (assets/py333.py:211-246)
+  get_cubies, RCC_*   the cube as pieces: (piece, orientation) bytes, the legality status bits, perfect indices (ops.cubies / from_cubies)
   py333               the same operators under the reference's names, one cube per call
   py222               the six names cube_env.py:8 imports from the file the reference does not ship (2x2x2, one cube per call)
 The directory is named `rubiks-cube-solver_amd`; import it as `rubiks_cube_solver_amd`.
 """
-from .tables import ACTION_NAMES, get_env_config, get_tables  # noqa: F401
+from .tables import (ACTION_NAMES, RCC_BAD_COLOUR, RCC_BAD_FIXED, RCC_BAD_PIECE, RCC_DUP_PIECE, RCC_FLIP, RCC_NAMES, RCC_PARITY,  # noqa: F401
+                     RCC_TWIST, get_cubies, get_env_config, get_tables)
 
-__all__ = ["get_env_config", "get_tables", "ACTION_NAMES", "ops", "make_env", "CubeEnv", "VecCubeEnv", "TensorReplayBuffer", "CodeNet"]
+__all__ = ["get_env_config", "get_tables", "get_cubies", "ACTION_NAMES", "RCC_BAD_COLOUR", "RCC_BAD_FIXED", "RCC_BAD_PIECE", "RCC_DUP_PIECE",
+           "RCC_TWIST", "RCC_FLIP", "RCC_PARITY", "RCC_NAMES", "ops", "make_env", "CubeEnv", "VecCubeEnv", "TensorReplayBuffer", "CodeNet"]
 
 
 def __getattr__(name):  # torch-dependent parts load lazily

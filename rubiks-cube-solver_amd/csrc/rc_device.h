@@ -865,4 +865,182 @@ struct WalkRng {
     }
 };
 
+// ------------------------------------------------------------------------ cubie coordinates
+// include/rubikhip.h "Cubie coordinates" (rcc_*), tables.py get_cubies.  Everything stays in packed bytes: one cube per byte, no
+// per-cube loop, no branch that depends on a cube.
+//
+// A sticker byte above 5 is no colour.  clean_colour maps it to a value >= 13 (0xff, or 0x10 for 8, 9, 10, 12, which v_perm_b32 reads
+// as "sign of a table byte" / "zero"): as a selector such a value reads 0xff from every table, and the three row masks of a second
+// colour read 0xff from it too, which selects row 7 = 0xff below.  0..5 pass unchanged.
+template <int V>
+__device__ __forceinline__ Pk<V> clean_colour(Pk<V> x) {
+    Pk<V> r = perm<V>(0xFFFF0504u, 0x03020100u, x);
+    RC_V r.d[k] |= (x.d[k] << 1) & 0xF0F0F0F0u;
+    return r;
+}
+template <int V>
+struct RowMasks { Pk<V> b0, b1, b2; };
+template <int V>
+__device__ __forceinline__ RowMasks<V> row_masks(Pk<V> c1) {
+    return {perm<V>(0xFF00FF00u, 0xFF00FF00u, c1), perm<V>(0xFFFF0000u, 0xFFFF0000u, c1), perm<V>(0xFFFFFFFFu, 0x00000000u, c1)};
+}
+// lut_pair's look-up (row = second colour, byte = first colour) on the EXACT tables of rc_tables.h: WHICH 0 xcorner_dw, 1 xthird_dw,
+// 2 xedge_dw.  Rows 6 and 7 read 0xff, so the result is 0xff (xthird: 0x0f or 0xff) unless both colours are 0..5 and some cubie shows them.
+template <class T, int V, int WHICH>
+__device__ __forceinline__ Pk<V> lut_exact(Pk<V> c0, const RowMasks<V> &m) {
+    Pk<V> g[6];
+    sfor<6>([&](auto kc) {
+        constexpr int k = decltype(kc)::value;
+        constexpr uint32_t lo = WHICH == 0 ? T::xcorner_dw[k][0] : WHICH == 1 ? T::xthird_dw[k][0] : T::xedge_dw[k][0];
+        constexpr uint32_t hi = WHICH == 0 ? T::xcorner_dw[k][1] : WHICH == 1 ? T::xthird_dw[k][1] : T::xedge_dw[k][1];
+        g[k] = perm<V>(hi, lo, c0);
+    });
+    const Pk<V> a0 = sel(m.b0, g[1], g[0]), a1 = sel(m.b0, g[3], g[2]), a2 = sel(m.b0, g[5], g[4]);
+    return sel(m.b2, sel(m.b1, splat<V>(0xFFFFFFFFu), a2), sel(m.b1, a1, a0));
+}
+// bit 7 of every byte that is not zero
+template <int V>
+__device__ __forceinline__ Pk<V> nonzero7(Pk<V> x) { Pk<V> r; RC_V r.d[k] = (((x.d[k] & 0x7f7f7f7fu) + 0x7f7f7f7fu) | x.d[k]) & 0x80808080u; return r; }
+// 0x01 in every byte that is not zero
+template <int V>
+__device__ __forceinline__ Pk<V> nonzero01(Pk<V> x) { Pk<V> r = nonzero7(x); RC_V r.d[k] >>= 7; return r; }
+
+template <class T, int V>
+struct Cubies {
+    Pk<V> code[T::SLOTS];    // the cubie bytes: piece * 3 + ori | piece * 2 + ori | 0xff
+    Pk<V> piece[T::SLOTS];   // piece, or 0x40 + slot where the slot names none (below 0x80, equal to no piece and to no other slot's)
+    Pk<V> ori[T::SLOTS];     // 0 where the slot names none
+    Pk<V> status;            // RCC_* bits
+    Pk<V> lt[T::SLOTS];      // INDEX only: #{r > q of the same kind : piece[r] < piece[q]}
+};
+
+// s: the S sticker rows as loaded (any bytes).  INDEX: also the Lehmer digits.
+template <class T, int V, bool INDEX>
+__device__ __forceinline__ void cubies_of(Pk<V> (&s)[T::S], Cubies<T, V> &c) {
+    Pk<V> colour = splat<V>(0);                                           // bits 3..7: some sticker is no colour
+    sfor<T::S>([&](auto ic) {
+        constexpr int i = decltype(ic)::value;
+        s[i] = clean_colour(s[i]);
+        colour = colour | s[i];
+    });
+    Pk<V> fixed = splat<V>(0), none = splat<V>(0);
+    sfor<T::NFIX>([&](auto fc) {
+        constexpr int i = T::fixed[decltype(fc)::value];
+        fixed = fixed | (s[i] ^ splat<V>((uint32_t)(i / T::FACE) * 0x01010101u));
+    });
+    sfor<T::NC>([&](auto qc) {
+        constexpr int q = decltype(qc)::value;
+        constexpr int i0 = T::ccw[q][0], i1 = T::ccw[q][1], i2 = T::ccw[q][2];
+        const RowMasks<V> m = row_masks(s[i1]);
+        const Pk<V> pc = lut_exact<T, V, 0>(s[i0], m);                   // piece * 4 + ori, 0xff: no cubie shows (c0, c1)
+        const Pk<V> third = lut_exact<T, V, 1>(s[i0], m);
+        const Pk<V> bad = signmask(nonzero7(third ^ s[i2]) | pc);        // the third colour is another one (a mirror image), or 0xff
+        Pk<V> pp, code;
+        RC_V {
+            pp.d[k] = (pc.d[k] >> 2) & 0x3f3f3f3fu;                      // piece
+            code.d[k] = (pc.d[k] - pp.d[k]) | bad.d[k];                  // piece * 3 + ori
+        }
+        c.code[q] = code;
+        c.piece[q] = sel(bad, splat<V>((uint32_t)(0x40 + q) * 0x01010101u), pp);
+        c.ori[q] = andn(pc & 0x03030303u, bad);
+        none = none | bad;
+    });
+    sfor<T::NE>([&](auto ec) {
+        constexpr int e = decltype(ec)::value, q = T::NC + e;
+        constexpr int i0 = T::edef[e][0], i1 = T::edef[e][1];
+        const Pk<V> code = lut_exact<T, V, 2>(s[i0], row_masks(s[i1]));  // piece * 2 + ori: RC_FMT_CODE's edge byte, 0xff: no cubie
+        const Pk<V> bad = signmask(code);
+        Pk<V> pp;
+        RC_V pp.d[k] = (code.d[k] >> 1) & 0x7f7f7f7fu;
+        c.code[q] = code;
+        c.piece[q] = sel(bad, splat<V>((uint32_t)(0x40 + q) * 0x01010101u), pp);
+        c.ori[q] = andn(code & 0x01010101u, bad);
+        none = none | bad;
+    });
+    // every pair of slots of one kind: ge = (a | 0x80) - b has bit 7 set iff a >= b (both below 0x80, no borrow leaves a byte)
+    Pk<V> twice = splat<V>(0), parity = splat<V>(0);
+    sfor<T::SLOTS>([&](auto qc) {
+        constexpr int q = decltype(qc)::value;
+        constexpr int end = q < T::NC ? T::NC : T::SLOTS;
+        Pk<V> cnt = splat<V>(0);
+        sfor<end - q - 1>([&](auto rc) {
+            constexpr int r = q + 1 + decltype(rc)::value;
+            Pk<V> ge, le;
+            RC_V {
+                ge.d[k] = (c.piece[q].d[k] | 0x80808080u) - c.piece[r].d[k];
+                le.d[k] = (c.piece[r].d[k] | 0x80808080u) - c.piece[q].d[k];
+                twice.d[k] |= ge.d[k] & le.d[k];
+                parity.d[k] ^= ge.d[k];                                   // without repeats: piece[q] > piece[r], an inversion
+            }
+            if constexpr (INDEX) RC_V cnt.d[k] += (~le.d[k] >> 7) & 0x01010101u;
+        });
+        if constexpr (INDEX) c.lt[q] = cnt;
+    });
+    Pk<V> twist = splat<V>(0), flip = splat<V>(0);
+    sfor<T::NC>([&](auto qc) { RC_V twist.d[k] += c.ori[decltype(qc)::value].d[k]; });
+    sfor<T::NE>([&](auto ec) { RC_V flip.d[k] += c.ori[T::NC + decltype(ec)::value].d[k]; });
+    RC_V twist.d[k] = (twist.d[k] & 0x03030303u) + ((twist.d[k] >> 2) & 0x07070707u);    // 4 = 1 mod 3; at most 16 -> at most 7
+    twist = perm<V>(0x10001010u, 0x00101000u, twist);                     // RCC_TWIST where the sum is not 0, 3 or 6
+    const Pk<V> c1 = nonzero01(colour & 0xF8F8F8F8u), f1 = nonzero01(fixed);
+    Pk<V> low, high;
+    RC_V {
+        low.d[k] = c1.d[k] | (f1.d[k] << 1) | (none.d[k] & 0x04040404u) | ((twice.d[k] >> 4) & 0x08080808u);
+        high.d[k] = twist.d[k];
+        if constexpr (T::NE > 0) high.d[k] |= ((flip.d[k] & 0x01010101u) << 5) | ((parity.d[k] >> 1) & 0x40404040u);
+    }
+    c.status = low | andn(high, signmask(nonzero7(low)));
+}
+
+// the colour at position K of a slot by its cubie byte (cstick_dw / estick_dw: 24 entries); bytes >= 24 read something, the caller masks
+template <class T, int V, bool CORNER, int K>
+__device__ __forceinline__ Pk<V> slot_colour(Pk<V> lo3, Pk<V> m3, Pk<V> m4) {
+    Pk<V> g[3];
+    sfor<3>([&](auto jc) {
+        constexpr int j = decltype(jc)::value;
+        constexpr uint32_t lo = CORNER ? T::cstick_dw[K][2 * j] : T::estick_dw[K][2 * j];
+        constexpr uint32_t hi = CORNER ? T::cstick_dw[K][2 * j + 1] : T::estick_dw[K][2 * j + 1];
+        g[j] = perm<V>(hi, lo, lo3);
+    });
+    return sel(m4, g[2], sel(m3, g[1], g[0]));
+}
+// bit 7 of every byte that is >= LIMIT (LIMIT <= 0x80)
+template <int V, int LIMIT>
+__device__ __forceinline__ Pk<V> at_least7(Pk<V> x) {
+    Pk<V> r;
+    RC_V r.d[k] = (((x.d[k] & 0x7f7f7f7fu) + (uint32_t)(0x80 - LIMIT) * 0x01010101u) | x.d[k]) & 0x80808080u;
+    return r;
+}
+// The inverse: SLOTS cubie bytes -> S stickers.  Returns 0xff in the bytes of the cubes that hold a byte naming no (piece, ori);
+// those cubes come out solved.  Nothing else is checked: a twisted corner or a repeated piece is written as given.
+template <class T, int V>
+__device__ __forceinline__ Pk<V> stickers_of(const Pk<V> (&code)[T::SLOTS], Pk<V> (&s)[T::S]) {
+    Pk<V> bad7 = splat<V>(0);
+    sfor<T::SLOTS>([&](auto qc) {
+        constexpr int q = decltype(qc)::value;
+        if constexpr (q < T::NC) bad7 = bad7 | at_least7<V, 3 * T::NC>(code[q]);
+        else bad7 = bad7 | at_least7<V, 2 * T::NE>(code[q]);
+    });
+    const Pk<V> bad = signmask(bad7);
+    sfor<T::S>([&](auto ic) {
+        constexpr int i = decltype(ic)::value;
+        s[i] = splat<V>((uint32_t)(i / T::FACE) * 0x01010101u);
+    });
+    sfor<T::SLOTS>([&](auto qc) {
+        constexpr int q = decltype(qc)::value;
+        const Pk<V> lo3 = code[q] & 0x07070707u, m3 = signmask(shl(code[q], 4)), m4 = signmask(shl(code[q], 3));
+        if constexpr (q < T::NC) {
+            sfor<3>([&](auto kc) {
+                constexpr int k = decltype(kc)::value, i = T::ccw[q][k];
+                s[i] = sel(bad, s[i], slot_colour<T, V, true, k>(lo3, m3, m4));
+            });
+        } else {
+            sfor<2>([&](auto kc) {
+                constexpr int k = decltype(kc)::value, i = T::edef[q - T::NC][k];
+                s[i] = sel(bad, s[i], slot_colour<T, V, false, k>(lo3, m3, m4));
+            });
+        }
+    });
+    return bad;
+}
+
 }  // namespace rc

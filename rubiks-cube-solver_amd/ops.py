@@ -314,6 +314,62 @@ def canonical_symmetry(st, n, pitch, cube_size, sym_out=None, out=None, pitch_ou
     return sym_out
 
 
+def cubies(st, n, cube_size, pitch=None, cubies=True, status=True, index=False, cubie_pitch=None):
+    """The cube as pieces (rcc_cubies, include/rubikhip.h "Cubie coordinates"; the rule in numpy: tables.get_cubies): one launch.
+    st: a state buffer (pitch None: the tensor's last dimension).  Each output is True (a fresh tensor), False / None (not computed) or
+    a tensor of the caller's: cubies uint8 [tiles, SLOTS, cubie_pitch] (tiled like a code buffer), status uint8 [n] (0 = reachable
+    from solved, else RCC_* bits), index -> corner_index uint32 [n] (held in an int32 tensor: torch has no arithmetic on uint32;
+    all-ones = -1 where status != 0) and, on the 3x3x3, edge_index uint64 [n] (an int64 tensor, likewise).  index may also be a
+    pair of tensors (corner_index, edge_index | None).
+    Returns dict(cubies=, status=, corner_index=, edge_index=) with None for what was not asked for."""
+    from . import _cubie_lib
+    S, _, SL = _size(cube_size)
+    p_in = _state_arg(st, S, n, pitch, "cubies st")
+    dev = st.device
+    vec = lambda dtype: torch.empty(_lib.pitch_for(n, 16), dtype=dtype, device=dev)[:n]
+    cub = alloc_code(n, cube_size, dev, cubie_pitch) if cubies is True else (cubies if isinstance(cubies, torch.Tensor) else None)
+    p_c = _state_arg(cub, SL, n, cubie_pitch, "cubies cubies") if cub is not None else 0
+    stat = vec(torch.uint8) if status is True else (status if isinstance(status, torch.Tensor) else None)
+    _vec(stat, n, torch.uint8, "cubies status", out=True)
+    ci = ei = None
+    if index is True:
+        ci, ei = vec(torch.int32), (vec(torch.int64) if cube_size == 3 else None)
+    elif isinstance(index, (tuple, list)):
+        ci, ei = index
+    elif index not in (False, None):
+        raise RubikHipError("cubies: index must be True, False or (corner_index, edge_index)")
+    _vec(ci, n, torch.int32, "cubies corner_index", out=True)
+    _vec(ei, n, torch.int64, "cubies edge_index", out=True)
+    if ei is not None and cube_size == 2:
+        raise RubikHipError("cubies: the 2x2x2 has no edge_index")
+    if cub is None and stat is None and ci is None and ei is None:
+        raise RubikHipError("cubies: nothing to compute (cubies, status and index are all off)")
+    _lib.init(dev)
+    check(_cubie_lib.cubie_lib().rcc_cubies(ptr(st), n, p_in, cube_size, ptr(cub), p_c, ptr(stat), ptr(ci), ptr(ei), stream_ptr(dev)))
+    return dict(cubies=cub, status=stat, corner_index=ci, edge_index=ei)
+
+
+def from_cubies(cub, n, cube_size, cubie_pitch=None, out=None, pitch=None, bad=None):
+    """Sticker states from cubie bytes (rcc_from_cubies): cub uint8 [tiles, SLOTS, cubie_pitch] -> out, a state buffer (default: a
+    fresh one with cub's tiling).  Any (piece, ori) per slot is written as given -- the assembly need not be legal.  A byte that names
+    no (piece, ori) cannot raise on the device: that cube comes out solved and a flag is set.  bad: that flag, a uint8 device tensor
+    [1] the caller zeroes and reads (nothing synchronises); None: a flag of the call's own, read back at once (a synchronisation)
+    and raised as ValueError.  Returns out."""
+    from . import _cubie_lib
+    S, _, SL = _size(cube_size)
+    p_c = _state_arg(cub, SL, n, cubie_pitch, "from_cubies cubies")
+    if out is None:
+        tiles = _tiles_of(n, p_c)
+        out, pitch = torch.empty((tiles, S, p_c), dtype=torch.uint8, device=cub.device), None
+    p_out = _state_arg(out, S, n, pitch, "from_cubies out")
+    flag = torch.zeros(1, dtype=torch.uint8, device=cub.device) if bad is None else _vec(bad, 1, torch.uint8, "from_cubies bad")
+    _lib.init(cub.device)
+    check(_cubie_lib.cubie_lib().rcc_from_cubies(ptr(cub), n, p_c, cube_size, ptr(out), p_out, ptr(flag), stream_ptr(cub.device)))
+    if bad is None and int(flag):
+        raise ValueError("from_cubies: a cubie byte names no (piece, orientation)")
+    return out
+
+
 def search_pack(leaf_code, child_code, child_solved, n, cube_size, leaf_out, child_out, solved_out):
     """The results of one expansion launch, laid out per root for the host trees of a lockstep search (rc_search_pack):
     leaf_code [tiles, SLOTS, pitch], child_code [A, tiles, SLOTS, pitch], child_solved [A, tiles * pitch]  ->

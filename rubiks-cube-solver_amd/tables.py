@@ -363,3 +363,158 @@ def get_env_config(cube_size: int = 3):
     if cube_size not in (2, 3):
         raise NotImplementedError(f"cube_size {cube_size}")
     return list(STATE_DIM[cube_size]), ACTION_DIM[cube_size]
+
+
+# ------------------------------------------------------------------------------------------- cubie coordinates
+# THE RULE (include/rubikhip.h "Cubie coordinates", rcc_*).  Slots and pieces are numbered as CORNER_SLOTS_* / EDGE_SLOTS_3 (corner_defs
+# / edge_defs): piece q is the cubie that sits in slot q of the solved cube.  One byte per slot, corner slots first:
+#   edge    piece * 2 + ori   ori = 0 when the piece's first colour shows on the slot's first sticker (edge_defs order): RC_FMT_CODE's byte;
+#   corner  piece * 3 + ori   ori = clockwise steps, seen from outside the cube looking at the corner, from the slot's U/D sticker to the
+#                             sticker that shows the piece's U/D colour.  The handedness of a slot comes from the geometry
+#                             (_sticker_geometry), not from the listing order of corner_defs -- so this is NOT RC_FMT_CODE's corner byte;
+#   0xFF    the slot's colours are no cubie (equal or opposite colours, a mirror-image corner, a value above 5).
+# status (one byte per cube) is 0 exactly when the state can be reached from solved by the env's moves:
+RCC_BAD_COLOUR, RCC_BAD_FIXED, RCC_BAD_PIECE, RCC_DUP_PIECE, RCC_TWIST, RCC_FLIP, RCC_PARITY = 1, 2, 4, 8, 16, 32, 64
+RCC_NAMES = {RCC_BAD_COLOUR: "RCC_BAD_COLOUR", RCC_BAD_FIXED: "RCC_BAD_FIXED", RCC_BAD_PIECE: "RCC_BAD_PIECE", RCC_DUP_PIECE: "RCC_DUP_PIECE",
+             RCC_TWIST: "RCC_TWIST", RCC_FLIP: "RCC_FLIP", RCC_PARITY: "RCC_PARITY"}
+#   1 a sticker above 5; 2 a sticker the moves never touch (centres; the DLB cubie of the 2x2x2) differs from solved; 4 a slot reads 0xFF;
+#   8 a piece occurs twice (among the slots that name one); and, evaluated only when bits 1..8 are clear: 16 the corner oris do not
+#   sum to 0 mod 3; 32 the edge oris sum to an odd number; 64 corner- and edge-permutation parities differ (32, 64: 3x3x3 only).
+# corner_index = lehmer(corner pieces) * 3^(NC-1) + sum_{q < NC-1} ori[q] * 3^q, lehmer = sum_q #{r > q: piece[r] < piece[q]} * (NC-1-q)!;
+# edge_index = lehmer(edge pieces) * 2^11 + sum_{q < 11} ori[q] * 2^q; both all-ones when status != 0.
+RCC_NO_CUBIE = 0xFF
+RCC_NO_INDEX32, RCC_NO_INDEX64 = 0xFFFFFFFF, 0xFFFFFFFFFFFFFFFF
+
+
+def rcc_status_names(status: int):
+    return [name for bit, name in RCC_NAMES.items() if status & bit]
+
+
+@dataclass(frozen=True)
+class CubieTables:
+    cube_size: int
+    nc: int
+    ne: int
+    corner_cw: np.ndarray  # uint8 [NC][3]  the slot's stickers clockwise seen from outside, the U/D sticker first
+    edge_facelets: np.ndarray  # uint8 [NE][2]  = edge_defs
+    corner_colours: np.ndarray  # uint8 [NC][3]  colours of piece p in the order of corner_cw[p]
+    edge_colours: np.ndarray  # uint8 [NE][2]
+    fixed: np.ndarray  # sticker indices no move touches: the 6 centres | the 3 stickers of DLB
+    solved: np.ndarray  # uint8 [S]
+    # the device look-ups (rc_tables.h): row = second colour, byte = first colour, 0xFF (0x0F for `third`) where no cubie has them
+    corner_pair: np.ndarray  # uint8 [6][8]  piece * 4 + ori by the colours at corner_cw positions 0, 1
+    corner_third: np.ndarray  # uint8 [6][8]  the colour such a cubie shows at position 2
+    edge_pair: np.ndarray  # uint8 [6][8]  piece * 2 + ori by the colours at the slot's two stickers
+    corner_sticker: np.ndarray  # uint8 [3][24]  colour at corner_cw position k of a slot whose byte is `code` (0xFF beyond 3 * NC)
+    edge_sticker: np.ndarray  # uint8 [2][24]
+
+    @property
+    def n_slots(self):
+        return self.nc + self.ne
+
+    def cubies(self, states):
+        """[n, S] sticker rows -> (cubies uint8 [n, SLOTS], status uint8 [n], corner_index uint32 [n], edge_index uint64 [n] | None)."""
+        st = np.asarray(states, np.uint8)
+        n, nc, ne = len(st), self.nc, self.ne
+        cub = np.full((n, nc + ne), RCC_NO_CUBIE, np.uint8)
+        seen = st[:, self.corner_cw.astype(np.int64)]                                    # [n, NC, 3]
+        for p in range(nc):
+            for o in range(3):
+                hit = (seen == np.roll(self.corner_colours[p], o)).all(axis=2)          # colour a_k shows at position (k + o) % 3
+                cub[:, :nc][hit] = 3 * p + o
+        if ne:
+            seen = st[:, self.edge_facelets.astype(np.int64)]
+            for p in range(ne):
+                for o in range(2):
+                    hit = (seen == np.roll(self.edge_colours[p], o)).all(axis=2)
+                    cub[:, nc:][hit] = 2 * p + o
+        named = cub != RCC_NO_CUBIE
+        cp, co = np.where(named[:, :nc], cub[:, :nc] // 3, 0).astype(np.int64), np.where(named[:, :nc], cub[:, :nc] % 3, 0).astype(np.int64)
+        ep, eo = np.where(named[:, nc:], cub[:, nc:] // 2, 0).astype(np.int64), np.where(named[:, nc:], cub[:, nc:] % 2, 0).astype(np.int64)
+
+        def twice(piece, ok, count):
+            hist = np.zeros((n, count + 1), np.int64)
+            np.add.at(hist, (np.arange(n)[:, None], np.where(ok, piece, count)), 1)
+            return (hist[:, :count] > 1).any(axis=1)
+
+        def lehmer(piece):                                                               # (value, parity of the permutation)
+            k = piece.shape[1]
+            cnt = np.stack([(piece[:, q + 1:] < piece[:, q:q + 1]).sum(axis=1) for q in range(k)], axis=1) if k else np.zeros((n, 0), np.int64)
+            fact = np.array([int(np.prod(np.arange(1, k - q, dtype=np.int64))) for q in range(k)], np.int64)
+            return (cnt * fact).sum(axis=1), cnt.sum(axis=1) & 1
+
+        status = np.zeros(n, np.uint8)
+        status |= np.uint8(RCC_BAD_COLOUR) * (st > 5).any(axis=1)
+        status |= np.uint8(RCC_BAD_FIXED) * (st[:, self.fixed] != self.solved[self.fixed]).any(axis=1)
+        status |= np.uint8(RCC_BAD_PIECE) * (~named).any(axis=1)
+        status |= np.uint8(RCC_DUP_PIECE) * (twice(cp, named[:, :nc], nc) | (twice(ep, named[:, nc:], ne) if ne else False))
+        clean = status == 0
+        clehmer, cpar = lehmer(cp)
+        status |= np.uint8(RCC_TWIST) * (clean & (co.sum(axis=1) % 3 != 0))
+        cidx = clehmer * 3 ** (nc - 1) + (co[:, :nc - 1] * 3 ** np.arange(nc - 1)).sum(axis=1)
+        eidx = None
+        if ne:
+            elehmer, epar = lehmer(ep)
+            status |= np.uint8(RCC_FLIP) * (clean & (eo.sum(axis=1) % 2 != 0))
+            status |= np.uint8(RCC_PARITY) * (clean & (cpar != epar))
+            eidx = (elehmer * 2 ** (ne - 1) + (eo[:, :ne - 1] << np.arange(ne - 1)).sum(axis=1)).astype(np.uint64)
+            eidx[status != 0] = RCC_NO_INDEX64
+        cidx = cidx.astype(np.uint32)
+        cidx[status != 0] = RCC_NO_INDEX32
+        return cub, status, cidx, eidx
+
+    def from_cubies(self, cubies):
+        """[n, SLOTS] cubie bytes -> (states uint8 [n, S], bad bool [n]).  Any (piece, ori) per slot is written as given -- a twisted
+        corner, a repeated piece; a cube with a byte that names none is written as solved and flagged."""
+        cub = np.asarray(cubies, np.uint8)
+        n, nc = len(cub), self.nc
+        bad = (cub[:, :nc] >= 3 * nc).any(axis=1) | (cub[:, nc:] >= 2 * self.ne).any(axis=1)
+        st = np.tile(self.solved, (n, 1))
+        home = np.array([3 * q for q in range(nc)] + [2 * q for q in range(self.ne)], np.uint8)      # the solved cube's bytes
+        safe = np.where(bad[:, None], home, cub)
+        for q in range(nc):
+            for k in range(3):
+                st[:, self.corner_cw[q][k]] = self.corner_sticker[k][safe[:, q]]
+        for q in range(self.ne):
+            for k in range(2):
+                st[:, self.edge_facelets[q][k]] = self.edge_sticker[k][safe[:, nc + q]]
+        return st, bad
+
+
+@functools.lru_cache(maxsize=None)
+def get_cubies(cube_size: int) -> CubieTables:
+    """The cubie tables of one cube size and the rule above in numpy (CubieTables.cubies / from_cubies)."""
+    t = get_tables(cube_size)
+    n = cube_size
+    geo = _sticker_geometry(n)
+    cw = []
+    for d in t.corner_defs:
+        n0, n1, n2 = (geo[i][1] for i in d)
+        assert n0[1] != 0                                                    # the slot's first sticker is its U/D sticker
+        det = sum(a * b for a, b in zip(n0, _cross(n1, n2)))                 # +1: (n0, n1, n2) runs counter-clockwise seen from outside
+        cw.append([d[0], d[1], d[2]] if det < 0 else [d[0], d[2], d[1]])
+    cw = np.array(cw, np.uint8)
+    ccol, ecol = t.solved[cw], (t.solved[t.edge_defs] if len(t.edge_defs) else np.zeros((0, 2), np.uint8))
+    moved = np.zeros(t.n_stickers, bool)
+    for p in t.perm:
+        moved |= p != np.arange(t.n_stickers)
+    nc, ne = len(cw), len(t.edge_defs)
+    cpair, cthird, epair = np.full((6, 8), 0xFF, np.uint8), np.full((6, 8), 0x0F, np.uint8), np.full((6, 8), 0xFF, np.uint8)
+    cstick, estick = np.full((3, 24), 0xFF, np.uint8), np.full((2, 24), 0xFF, np.uint8)
+    for p in range(nc):
+        for o in range(3):
+            c = np.roll(ccol[p], o)
+            assert cpair[c[1]][c[0]] == 0xFF
+            cpair[c[1]][c[0]], cthird[c[1]][c[0]] = 4 * p + o, c[2]
+            cstick[:, 3 * p + o] = c
+    for p in range(ne):
+        for o in range(2):
+            c = np.roll(ecol[p], o)
+            assert epair[c[1]][c[0]] == 0xFF
+            epair[c[1]][c[0]] = 2 * p + o
+            estick[:, 2 * p + o] = c
+            assert t.edge_code[c[0] + 10 * c[1]] == 2 * p + o                # the edge byte IS RC_FMT_CODE's
+    assert (cpair != 0xFF).sum() == 3 * nc and (epair != 0xFF).sum() == 2 * ne
+    return CubieTables(cube_size=n, nc=nc, ne=ne, corner_cw=cw, edge_facelets=t.edge_defs.copy(), corner_colours=ccol, edge_colours=ecol,
+                       fixed=np.flatnonzero(~moved).astype(np.uint8), solved=t.solved, corner_pair=cpair, corner_third=cthird, edge_pair=epair,
+                       corner_sticker=cstick, edge_sticker=estick)

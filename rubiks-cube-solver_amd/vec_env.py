@@ -202,10 +202,50 @@ class VecCubeEnv:
         """[N, S] uint8 tensor: one row per cube (a copy; the live buffer is `stickers`)."""
         return ops.to_aos(self.stickers, self.num_envs).contiguous()
 
-    def set_sim_cube(self, states):
-        """Load [N, S] sticker rows (host or device)."""
+    def set_sim_cube(self, states, check=False):
+        """Load [N, S] sticker rows (host or device).  check=True: refuse states that are no cube reachable from solved (legality());
+        ValueError names the first offending cube, its status bits and how many cubes failed, and the env keeps its old cubes.
+        check=False (the default) loads any uint8 array, as before."""
         t = torch.as_tensor(states, dtype=torch.uint8).cpu()
-        self.stickers.copy_(ops.from_aos(t, self.device, self.stickers.shape[2]))
+        if check and tuple(t.shape) != (self.num_envs, self.stickers.shape[1]):
+            raise ValueError(f"states must be [{self.num_envs}, {self.stickers.shape[1]}], got {tuple(t.shape)}")
+        buf = ops.from_aos(t, self.device, self.stickers.shape[2])
+        if check:
+            status = ops.cubies(buf, self.num_envs, self.cube_size, cubies=False)["status"].cpu().numpy()
+            failed = np.flatnonzero(status)
+            if len(failed):
+                from .tables import rcc_status_names
+                first = int(failed[0])
+                raise ValueError(f"set_sim_cube: cube {first} is not reachable from the solved cube (status {int(status[first])}: "
+                                 f"{' | '.join(rcc_status_names(int(status[first])))}); {len(failed)} of {self.num_envs} cubes failed")
+        self.stickers.copy_(buf)
+
+    def cubies(self, index=False):
+        """The cubes as pieces (ops.cubies; the rule: include/rubikhip.h "Cubie coordinates"): the cubie tensor uint8 [tiles, SLOTS,
+        pitch] -- ops.to_aos(t, N) gives [N, SLOTS] --, or with index=True (cubies, corner_index int32 [N][, edge_index int64 [N] on
+        the 3x3x3]); an index is all-ones (-1) where the cube is not legal."""
+        out = ops.cubies(self.stickers, self.num_envs, self.cube_size, status=False, index=bool(index))
+        if not index:
+            return out["cubies"]
+        return (out["cubies"], out["corner_index"]) + ((out["edge_index"],) if self.cube_size == 3 else ())
+
+    def legality(self):
+        """uint8 [N]: 0 where the cube can be reached from solved by the env's moves, else the RCC_* bits that say why not."""
+        return ops.cubies(self.stickers, self.num_envs, self.cube_size, cubies=False)["status"]
+
+    def from_cubies(self, cubies):
+        """Set every cube from its cubie bytes: [N, SLOTS] rows (host or device) or a tiled cubie tensor as cubies() returns it.  The
+        assembly need not be legal (legality() tells); a byte that names no (piece, orientation) raises ValueError and the env keeps
+        its old cubes.  Starts new episodes like reset(); returns the observation."""
+        n, SL = self.num_envs, ops.N_SLOTS[self.cube_size]
+        c = cubies if isinstance(cubies, torch.Tensor) else torch.as_tensor(np.asarray(cubies), dtype=torch.uint8)
+        if c.dim() == 2 and tuple(c.shape) == (n, SL):
+            c = ops.from_aos(c.cpu(), self.device, self.stickers.shape[2])
+        elif not (c.dim() == 3 and c.shape[1] == SL and c.dtype == torch.uint8):
+            raise ValueError(f"cubies must be [{n}, {SL}] rows or a tiled uint8 tensor [tiles, {SL}, pitch]")
+        self.stickers.copy_(ops.from_cubies(c.to(self.device), n, self.cube_size, out=torch.empty_like(self.stickers)))
+        self._new_episodes()
+        return self._observe()
 
     def expand(self, children=False, codes=True, pitch=None):
         """All A children of every cube (cube_env.py:212-236, mcts.py:96-101).
