@@ -1231,6 +1231,25 @@ int by_size(int cube_size, F &&f) {
     return fail(RC_EINVAL, "cube_size must be 2 or 3%s");  // NotImplementedError, cube_env.py:44
 }
 
+// The twin of by_size for the dense one-hot formats: f gets Fmt<E>{} of fmt's element type (fmt is one of RC_FMT_U8 .. RC_FMT_BF16).
+template <class E>
+struct Fmt {
+    using type = E;
+    static constexpr const char *name = std::is_same_v<E, uint8_t> ? "u8" : std::is_same_v<E, uint16_t> ? "f16" : std::is_same_v<E, Bf16> ? "bf16" : "f32";
+    static constexpr int size = sizeof(E);
+    static constexpr int cpp = 240 / (480 / (16 / size));                // cubes per 3840-byte pass of the front writer: 8 / 4 / 2
+    static constexpr int fronts = size == 1 ? 2 : 1;                     // the front writer's measured shape (front_shape)
+    static constexpr bool lds = size != 4;
+};
+template <class F>
+auto by_fmt(int fmt, F &&f) {
+    if (fmt == RC_FMT_U8) return f(Fmt<uint8_t>{});
+    if (fmt == RC_FMT_F16) return f(Fmt<uint16_t>{});
+    if (fmt == RC_FMT_BF16) return f(Fmt<Bf16>{});
+    return f(Fmt<float>{});
+}
+inline bool dense_fmt(int fmt) { return fmt >= RC_FMT_U8 && fmt <= RC_FMT_BF16; }
+
 // Per-call tuning override of the *_ex entry points (0 = the measured defaults).  Decimal digits:
 //   units      pack width: 1,2 -> V = 1,2 (4, 8 cubes per lane)
 //   tens       row-traffic policy of the step kernel: 1 -> POL 2 (stream), 2 -> POL 0 (cached), 3 -> POL 1 (keep)
@@ -1241,37 +1260,37 @@ int by_size(int cube_size, F &&f) {
 // policy follows the working set (RowPolicy).
 // Round-3 sweep over 2^18 .. 2^24 cubes x {done, reward, code, in place} (profiles/r03_ab.json): with every side store a
 // contiguous 1-KiB instruction V = 2 wins or ties everywhere from 2^18 cubes up (V = 1 is 2 % ahead only around 2^21).
+struct Variant { int units, tens, hundreds, thousands, form, segs, rest; };   // thousands, segs: 2 digits; form: the 100000s digit; rest: above (-1: negative)
+inline Variant decode_variant(int variant) {
+    return {variant % 10, variant / 10 % 10, variant / 100 % 10, variant / 1000 % 100, variant / 100000 % 10, variant / 1000000 % 100,
+            variant < 0 ? -1 : variant / 100000000};
+}
 // Which decimal fields of `variant` an entry point defines (include/rubikhip.h RC_VARIANT_*): anything else is RC_EINVAL, in the
 // *_ex launchers and in rc_describe_dispatch alike, so a value composed for one entry point cannot silently mean something else in another.
-int check_variant(int op, int A, int variant) {
-    if (variant == 0) return RC_OK;
-    const int units = variant % 10, tens = (variant / 10) % 10, hundreds = (variant / 100) % 10, field = (variant / 1000) % 100,
-              form = (variant / 100000) % 10, segs = (variant / 1000000) % 100, rest = variant / 100000000;
-    bool ok = variant > 0 && rest == 0;
-    if (op == RC_OP_STEP) ok = ok && units <= 2 && tens <= 4 && hundreds == 0 && field == 0 && form <= 2 && segs == 0;
-    else if (op == RC_OP_EXPAND) ok = ok && units <= 2 && tens == 0 && hundreds <= 8 && field <= A && form == 0 && segs == 0;
-    else if (op == RC_OP_ADI) ok = ok && units <= 2 && tens == 0 && hundreds == 0 && field <= A && form == 0 && segs <= 16;
+int check_variant(int op, int A, const Variant &v) {
+    bool ok = v.rest == 0;
+    if (op == RC_OP_STEP) ok = ok && v.units <= 2 && v.tens <= 4 && v.hundreds == 0 && v.thousands == 0 && v.form <= 2 && v.segs == 0;
+    else if (op == RC_OP_EXPAND) ok = ok && v.units <= 2 && v.tens == 0 && v.hundreds <= 8 && v.thousands <= A && v.form == 0 && v.segs == 0;
+    else if (op == RC_OP_ADI) ok = ok && v.units <= 2 && v.tens == 0 && v.hundreds == 0 && v.thousands <= A && v.form == 0 && v.segs <= 16;
     else if (op == RC_OP_CODE_TO_DENSE) {
-        ok = ok && hundreds == 0 && segs == 0 && form <= 4;
-        if (form == 3) ok = ok && units == 0;                                               // wide: tens = skew, field = groups / 16
-        else if (form == 0 || form == 4) ok = ok && (units <= 2 || units == 4) && (tens == 0 || (tens >= 2 && tens <= 4)) && field == 0;   // front
-        else ok = ok && units == 0 && tens == 0 && field == 0;
-    } else ok = false;                                                                       // RC_OP_FAMILY_TO_DENSE: no tuning fields
+        ok = ok && v.hundreds == 0 && v.segs == 0 && v.form <= 4;
+        if (v.form == 3) ok = ok && v.units == 0;                                           // wide: tens = skew, thousands = groups / 16
+        else if (v.form == 0 || v.form == 4) ok = ok && (v.units <= 2 || v.units == 4) && (v.tens == 0 || (v.tens >= 2 && v.tens <= 4)) && v.thousands == 0;   // front
+        else ok = ok && v.units == 0 && v.tens == 0 && v.thousands == 0;
+    } else ok = ok && (v.units | v.tens | v.hundreds | v.thousands | v.form | v.segs) == 0;  // RC_OP_FAMILY_TO_DENSE: no tuning fields
     return ok ? RC_OK : fail(RC_EINVAL, "variant: a field this entry point does not define is set (include/rubikhip.h RC_VARIANT_*)%s");
 }
 
-int pick_v(int64_t n, int variant) {
-    const int v = variant % 10;
-    if (v == 1 || v == 2) return v;
+int pick_v(int64_t n, const Variant &v) {
+    if (v.units == 1 || v.units == 2) return v.units;
     return n >= (int64_t)1 << 18 ? 2 : 1;
 }
 constexpr int64_t kMallBytes = (int64_t)240 << 20;   // what we count on of the 256 MiB Infinity Cache
-int pick_policy(int64_t in_bytes, int64_t out_bytes, bool in_place, int64_t side_bytes, int variant) {
-    const int p = (variant / 10) % 10;
-    if (p == 1) return 2;
-    if (p == 2) return 0;
-    if (p == 3) return 1;
-    if (p == 4) return 3;
+int pick_policy(int64_t in_bytes, int64_t out_bytes, bool in_place, int64_t side_bytes, const Variant &v) {
+    if (v.tens == 1) return 2;
+    if (v.tens == 2) return 0;
+    if (v.tens == 3) return 1;
+    if (v.tens == 4) return 3;
     const int64_t touched = in_place ? in_bytes : in_bytes + out_bytes;
     if (touched + side_bytes <= kMallBytes) return 0;   // resident: default-cached (1M cubes run out of the Infinity Cache)
     if (touched <= kMallBytes) return 3;                // the state is resident, its side outputs (code, reward, done) stream past it
@@ -1282,40 +1301,7 @@ int pick_policy(int64_t in_bytes, int64_t out_bytes, bool in_place, int64_t side
 template <class T>
 int64_t side_bytes(int64_t n, bool code, bool done, bool reward) { return n * ((code ? T::SLOTS : 0) + (done ? 1 : 0) + (reward ? 4 : 0)); }
 
-struct StepPlan { int v, pol; };
-// One place decides pack width and row-traffic policy of a step launch (the launcher and rc_describe_dispatch both call it).
-template <class T>
-StepPlan plan_step(int64_t n, bool writes, bool in_place, bool code, bool done, bool reward, int variant) {
-    const int pol = pick_policy(n * T::S, writes ? n * T::S : 0, writes && in_place, side_bytes<T>(n, code, done, reward), variant);
-    return {pick_v(n, variant), pol};
-}
-
-template <class T, int V, bool MOVE, bool STORE, bool CODE>
-int launch_step(const StepArgs &a, hipStream_t st, int pol) {
-    constexpr int BLOCK = 64;
-    const int64_t lanes = (a.n + 4 * V - 1) / (4 * V);
-    const int64_t blocks = (lanes + BLOCK - 1) / BLOCK;
-    RC_GRID(blocks);
-    const dim3 g((unsigned)blocks), b(BLOCK);
-    if (pol == 4) {
-        if constexpr (CODE) hipLaunchKernelGGL((k_step<T, V, MOVE, STORE, CODE, 4, BLOCK>), g, b, 0, st, a);
-        else return fail(RC_EINVAL, "row policy 4 belongs to the workspace route%s");
-    } else if (pol == 3) hipLaunchKernelGGL((k_step<T, V, MOVE, STORE, CODE, 3, BLOCK>), g, b, 0, st, a);
-    else if (pol == 2) hipLaunchKernelGGL((k_step<T, V, MOVE, STORE, CODE, 2, BLOCK>), g, b, 0, st, a);
-    else if (pol == 1) hipLaunchKernelGGL((k_step<T, V, MOVE, STORE, CODE, 1, BLOCK>), g, b, 0, st, a);
-    else hipLaunchKernelGGL((k_step<T, V, MOVE, STORE, CODE, 0, BLOCK>), g, b, 0, st, a);
-    RC_HIP(hipGetLastError());
-    return RC_OK;
-}
-
-// keep_code: the compact code is read back by the next launch (workspace route): beyond the resident case it is written with POL 4
-template <class T, bool MOVE, bool STORE, bool CODE>
-int dispatch_step(const StepArgs &a, hipStream_t st, int variant, bool keep_code = false) {
-    const bool writes = STORE && a.out != nullptr;
-    StepPlan p = plan_step<T>(a.n, writes, writes && a.out == a.in, CODE, a.done != nullptr, a.reward != nullptr, variant);
-    if (keep_code && p.pol != 0) p.pol = 4;
-    return p.v == 2 ? launch_step<T, 2, MOVE, STORE, CODE>(a, st, p.pol) : launch_step<T, 1, MOVE, STORE, CODE>(a, st, p.pol);
-}
+inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 // Dense writer form.  100000s digit of `variant`: 1 -> 64-cube tiles, 2 -> 256-cube tiles (256-thread workgroups), 3 -> the wide
 // form (3x3x3 only).  Default: wide from 2^17 cubes (3x3x3), 256-cube tiles for 2x2x2 batches of that size, else 64-cube tiles
@@ -1324,20 +1310,19 @@ int dispatch_step(const StepArgs &a, hipStream_t st, int variant, bool keep_code
 // 4.9 / 5.4 with 1024-cube tiles -- shorter private write streams per workgroup; the wide form: see k_code_to_dense_wide.
 enum DenseForm { kDense64 = 64, kDense256 = 256, kDenseWide = 960, kDenseFront = 1 };
 template <class T>
-inline DenseForm dense_form(int64_t n, int variant, bool fused, int fmt) {
+inline DenseForm dense_form(int64_t n, const Variant &v, bool fused, int fmt) {
     const bool wide_ok = T::SIZE == 3 && !fused;   // the wide form exists for code -> dense only: a FUSED wide kernel (every wave
     //   produces a tile, then all sweep 15 tiles) was built and measured in round 3 and lost to the 256-thread form for every
     //   format and group count (bf16 0.62-0.74 against 0.74-0.76: its ~110 workgroups funnel the state traffic and stall the
     //   dense stream while they produce; profiles/r03_ab.json "dense_wide_groups")
-    const int forced = (variant / 100000) % 10;
-    if (forced == 1) return kDense64;
-    if (forced == 2) return kDense256;
-    if (forced == 3) return wide_ok ? kDenseWide : kDense256;
-    if (forced == 4) return wide_ok ? kDenseFront : kDense256;
+    if (v.form == 1) return kDense64;
+    if (v.form == 2) return kDense256;
+    if (v.form == 3) return wide_ok ? kDenseWide : kDense256;
+    if (v.form == 4) return wide_ok ? kDenseFront : kDense256;
     // Measured over 2^15 .. 2^22 cubes, two buffers each (profiles/r04_dense_sizes.json, fraction of the 8 TB/s peak):
     //   code -> dense: the front writer from 2^15 (f32: 0.73 against 0.63), 2^16 (16-bit: 0.69 against 0.65), 2^18 (u8: 0.75 against
     //                  0.72) cubes -- 0.83-0.95 / 0.77-0.89 / 0.75-0.82 beyond, on every allocation; 64-cube tiles below
-    //   fused step   : (without a workspace; with one see step_common) 64-cube tiles below 2^17 cubes; from there 16-bit formats
+    //   fused step   : (without a workspace; with one see plan_step) 64-cube tiles below 2^17 cubes; from there 16-bit formats
     //                  64-cube tiles from 2^19 (0.78-0.80 against 0.73-0.76), 256-cube tiles otherwise
     if (!fused && wide_ok && n >= ((int64_t)1 << (fmt == RC_FMT_F32 ? 15 : fmt == RC_FMT_U8 ? 18 : 16))) return kDenseFront;
     if (n < ((int64_t)1 << 17) || (!fused && wide_ok)) return kDense64;
@@ -1345,150 +1330,193 @@ inline DenseForm dense_form(int64_t n, int variant, bool fused, int fmt) {
     //   f32 (0.66 against 0.58 at 1M cubes) and the 16-bit formats (0.53 against 0.48), 256-cube tiles for u8 (0.52 against 0.34)
     return T::SIZE == 3 && (fmt == RC_FMT_F16 || fmt == RC_FMT_BF16) && n >= ((int64_t)1 << 19) ? kDense64 : kDense256;
 }
-struct WideGrid { int64_t groups, per; };
-// `variant` thousands field (2 digits, otherwise the expansion's parts): wanted workgroups / 16, for tuning sweeps
-inline WideGrid wide_grid(int64_t n, int variant) {
-    const int64_t tiles = (n + kWideTile - 1) / kWideTile;
-    const int f = (variant / 1000) % 100;
-    const int64_t want = f ? f * 16 : kWideGroups;
-    const int64_t per = (tiles + want - 1) / want;
-    return {(tiles + per - 1) / per, per};
-}
+
+// Everything one dense-writer launch needs, for the launcher and for rc_describe_dispatch alike.
+struct DensePlan {
+    DenseForm form;                              // kDense64 / kDense256: the tile kernels with TILE = form
+    int f = 1, cpp = 0;                          // front: fronts per XCD per workgroup, cubes per pass ...
+    bool lds = false, linear = false;            // ... code bytes through LDS (else a gather per lane), one linear front
+    int64_t per_xcd = 0, per_front = 0;          // front: passes per XCD / per front (0 when linear)
+    int64_t per = 0;                             // wide: tiles per group ...
+    int skew = 0;                                // ... and the sweep skew
+    int64_t grid_x = 0, grid_y = 1;
+    int block = 256;
+};
 
 // The dense kernels loop over tiles (grid-stride).  f32 rows (1920 B per cube) run 5 % faster at 1M cubes when the grid is
 // capped at the 2048 workgroups the chip holds at once (8 per CU), each taking tiles b, b + 2048, ...: 330 us against 347
 // (tools/exp/dense_exp.py); the 1- and 2-byte formats show no gain and keep one workgroup per tile.
 inline int64_t dense_grid(int64_t blocks, int fmt) { return fmt == RC_FMT_F32 && blocks > 2048 ? 2048 : blocks; }
-
-template <class T, bool MOVE, bool STORE, int TILE>
-int launch_dense_t(const StepArgs &a, void *onehot, int fmt, hipStream_t st) {
-    int64_t blocks = (a.n + TILE - 1) / TILE;
-    RC_GRID(blocks);
-    blocks = dense_grid(blocks, fmt);
-    const dim3 g((unsigned)blocks);
-    if (fmt == RC_FMT_U8) hipLaunchKernelGGL((k_step_dense<T, uint8_t, MOVE, STORE, TILE>), g, dim3(kDenseThreads<T, uint8_t>), 0, st, a, static_cast<uint8_t *>(onehot));
-    else if (fmt == RC_FMT_F16) hipLaunchKernelGGL((k_step_dense<T, uint16_t, MOVE, STORE, TILE>), g, dim3(kDenseThreads<T, uint16_t>), 0, st, a, static_cast<uint16_t *>(onehot));
-    else if (fmt == RC_FMT_BF16) hipLaunchKernelGGL((k_step_dense<T, Bf16, MOVE, STORE, TILE>), g, dim3(kDenseThreads<T, Bf16>), 0, st, a, static_cast<Bf16 *>(onehot));
-    else hipLaunchKernelGGL((k_step_dense<T, float, MOVE, STORE, TILE>), g, dim3(kDenseThreads<T, float>), 0, st, a, static_cast<float *>(onehot));
-    RC_HIP(hipGetLastError());
-    return RC_OK;
-}
-
-template <class T, bool MOVE, bool STORE>
-int launch_dense(const StepArgs &a, void *onehot, int fmt, hipStream_t st, int variant) {
-    switch (dense_form<T>(a.n, variant, true, fmt)) {
-        case kDense64: return launch_dense_t<T, MOVE, STORE, 64>(a, onehot, fmt, st);
-        default: return launch_dense_t<T, MOVE, STORE, 256>(a, onehot, fmt, st);
-    }
-}
-
-template <class T, int TILE>
-int launch_code_to_dense(const uint8_t *code, int64_t n, int64_t code_pitch, int sh, void *onehot, int fmt, hipStream_t st,
-                         int n_blocks = 1, int64_t src_bs = 0, int64_t dst_bs = 0) {
-    int64_t blocks = (n + TILE - 1) / TILE;
-    RC_GRID(blocks);
-    blocks = dense_grid(blocks, fmt);
-    const dim3 g((unsigned)blocks, (unsigned)n_blocks);
-    if (fmt == RC_FMT_U8) hipLaunchKernelGGL((k_code_to_dense<T, uint8_t, TILE>), g, dim3(kDenseThreads<T, uint8_t>), 0, st, code, n, code_pitch, sh, static_cast<uint8_t *>(onehot), src_bs, dst_bs);
-    else if (fmt == RC_FMT_F16) hipLaunchKernelGGL((k_code_to_dense<T, uint16_t, TILE>), g, dim3(kDenseThreads<T, uint16_t>), 0, st, code, n, code_pitch, sh, static_cast<uint16_t *>(onehot), src_bs, dst_bs);
-    else if (fmt == RC_FMT_BF16) hipLaunchKernelGGL((k_code_to_dense<T, Bf16, TILE>), g, dim3(kDenseThreads<T, Bf16>), 0, st, code, n, code_pitch, sh, static_cast<Bf16 *>(onehot), src_bs, dst_bs);
-    else hipLaunchKernelGGL((k_code_to_dense<T, float, TILE>), g, dim3(kDenseThreads<T, float>), 0, st, code, n, code_pitch, sh, static_cast<float *>(onehot), src_bs, dst_bs);
-    RC_HIP(hipGetLastError());
-    return RC_OK;
+template <class T>
+DensePlan plan_tiles(int64_t n, int fmt, DenseForm tile, int64_t grid_y = 1) {
+    DensePlan p{tile};
+    p.grid_x = dense_grid(ceil_div(n, tile), fmt);
+    p.grid_y = grid_y;
+    p.block = by_fmt(fmt, [](auto e) { return kDenseThreads<T, typename decltype(e)::type>; });
+    return p;
 }
 
 // Shape of the front writer per format (kernel comment; measured side by side at 2^20 cubes, four buffers each): f32 a byte gather
 // per lane, one front per XCD (0.95); 16-bit wave 0's load + LDS, one front (0.87); u8 LDS, two fronts per XCD per workgroup
 // (0.82-0.86; one front 0.76).  `variant`: units digit 1, 2, 4 force F; tens digit 2 = one linear front, 3 = gather, 4 = LDS.
-struct FrontShape { int f; bool lds, linear; };
-inline FrontShape front_shape(int fmt, int variant) {
-    const int v = variant % 10, t = (variant / 10) % 10;
-    FrontShape s{fmt == RC_FMT_U8 ? 2 : 1, fmt != RC_FMT_F32, t == 2};
-    if (v == 1 || v == 2 || v == 4) s.f = v;
-    if (t == 3) s.lds = false;
-    if (t == 4) s.lds = true;
-    if (s.linear) s.f = 1;
-    return s;
-}
-template <class T, class E, int F, bool LDS>
-int launch_front_e(const uint8_t *code, int64_t n, int64_t code_pitch, int sh, E *onehot, hipStream_t st, bool linear) {
-    constexpr int cpp = 240 / (480 / (16 / (int)sizeof(E)));                        // cubes per 3840-byte pass: 2 / 4 / 8
-    const int64_t passes = (n + cpp - 1) / cpp;
-    int64_t per_xcd = 0, per_front = 0, blocks = passes;
-    if (!linear) {
-        per_front = (passes + 8 * F - 1) / (8 * F);                                  // passes of one front
-        per_xcd = per_front * F;
-        blocks = per_front * 8;
+// grid_y > 1: the family writer's blocks (all A children and the parent of every depth), same shapes per format.
+inline DensePlan plan_front(int64_t n, int fmt, const Variant &v, int64_t grid_y = 1) {
+    DensePlan p{kDenseFront};
+    by_fmt(fmt, [&](auto e) { p.f = e.fronts, p.lds = e.lds, p.cpp = e.cpp; return 0; });
+    p.linear = v.tens == 2;
+    if (v.units == 1 || v.units == 2 || v.units == 4) p.f = v.units;
+    if (v.tens == 3) p.lds = false;
+    if (v.tens == 4) p.lds = true;
+    if (p.linear) p.f = 1;
+    const int64_t passes = ceil_div(n, p.cpp);
+    if (!p.linear) {
+        p.per_front = ceil_div(passes, 8 * p.f);                                     // passes of one front
+        p.per_xcd = p.per_front * p.f;
     }
-    RC_GRID(blocks);
-    hipLaunchKernelGGL((k_code_to_dense_front<T, E, F, LDS>), dim3((unsigned)blocks), dim3(256), 0, st, code, n, code_pitch, sh, onehot, per_xcd, per_front);
-    RC_HIP(hipGetLastError());
-    return RC_OK;
-}
-template <class T, class E>
-int launch_front_shape(const uint8_t *code, int64_t n, int64_t code_pitch, int sh, E *onehot, hipStream_t st, FrontShape s) {
-    if (s.lds) {
-        if (s.f == 4) return launch_front_e<T, E, 4, true>(code, n, code_pitch, sh, onehot, st, s.linear);
-        if (s.f == 2) return launch_front_e<T, E, 2, true>(code, n, code_pitch, sh, onehot, st, s.linear);
-        return launch_front_e<T, E, 1, true>(code, n, code_pitch, sh, onehot, st, s.linear);
-    }
-    if (s.f == 4) return launch_front_e<T, E, 4, false>(code, n, code_pitch, sh, onehot, st, s.linear);
-    if (s.f == 2) return launch_front_e<T, E, 2, false>(code, n, code_pitch, sh, onehot, st, s.linear);
-    return launch_front_e<T, E, 1, false>(code, n, code_pitch, sh, onehot, st, s.linear);
-}
-// family rows -> the dense one-hots of all A children and the parent (block a at onehot + a * block_stride cubes): the front writer
-// over (A + 1) * ceil(n / cubes per pass) passes, same shapes per format as the code -> dense launch
-struct FamilyDepths { int n_depths; int64_t src_depth_stride, dst_depth_stride; };   // strides: bytes of one depth's record / cubes of one depth's blocks
-template <class T, class E, int F, bool LDS>
-int launch_family_e(const uint8_t *fam, int64_t n, int64_t pitch, int sh, E *onehot, int64_t block_stride, FamilyDepths dp, hipStream_t st) {
-    constexpr int cpp = 240 / (480 / (16 / (int)sizeof(E)));
-    const int64_t ppb = (n + cpp - 1) / cpp;                                      // passes per block
-    const int64_t per_front = (ppb + 8 * F - 1) / (8 * F), per_xcd = per_front * F, blocks = per_front * 8;   // gridDim.x % 8 == 0: x % 8 is the XCD in every row
-    RC_GRID(blocks);
-    const int64_t nblk = (int64_t)(T::A + 1) * dp.n_depths;
-    if (nblk > 65535) return fail(RC_EINVAL, "rc_onehot_from_family: at most 5041 depths per launch%s");
-    const FamilyBlocks fb{block_stride, dp.src_depth_stride, dp.dst_depth_stride};
-    hipLaunchKernelGGL((k_code_to_dense_front<T, E, F, LDS, true>), dim3((unsigned)blocks, (unsigned)nblk), dim3(256), 0, st, fam, n, pitch, sh, onehot, per_xcd, per_front, fb);
-    RC_HIP(hipGetLastError());
-    return RC_OK;
-}
-template <class T>
-int launch_family_to_dense(const uint8_t *fam, int64_t n, int64_t pitch, int sh, void *onehot, int fmt, int64_t block_stride, FamilyDepths dp, hipStream_t st) {
-    if (fmt == RC_FMT_U8) return launch_family_e<T, uint8_t, 2, true>(fam, n, pitch, sh, static_cast<uint8_t *>(onehot), block_stride, dp, st);
-    if (fmt == RC_FMT_F16) return launch_family_e<T, uint16_t, 1, true>(fam, n, pitch, sh, static_cast<uint16_t *>(onehot), block_stride, dp, st);
-    if (fmt == RC_FMT_BF16) return launch_family_e<T, Bf16, 1, true>(fam, n, pitch, sh, static_cast<Bf16 *>(onehot), block_stride, dp, st);
-    return launch_family_e<T, float, 1, false>(fam, n, pitch, sh, static_cast<float *>(onehot), block_stride, dp, st);
+    p.grid_x = p.linear ? passes : p.per_front * 8;                                  // gridDim.x % 8 == 0: x % 8 is the XCD in every row
+    p.grid_y = grid_y;
+    return p;
 }
 
+// code -> dense: tile, wide or front form.  Wide: `variant` thousands field (2 digits, otherwise the expansion's parts) = wanted
+// workgroups / 16, tens digit = the sweep skew, for tuning sweeps.
 template <class T>
-int launch_code_to_dense_front(const uint8_t *code, int64_t n, int64_t code_pitch, int sh, void *onehot, int fmt, hipStream_t st, int variant) {
-    if constexpr (T::SIZE == 3) {
-        const FrontShape s = front_shape(fmt, variant);
-        if (fmt == RC_FMT_U8) return launch_front_shape<T>(code, n, code_pitch, sh, static_cast<uint8_t *>(onehot), st, s);
-        if (fmt == RC_FMT_F16) return launch_front_shape<T>(code, n, code_pitch, sh, static_cast<uint16_t *>(onehot), st, s);
-        if (fmt == RC_FMT_BF16) return launch_front_shape<T>(code, n, code_pitch, sh, static_cast<Bf16 *>(onehot), st, s);
-        return launch_front_shape<T>(code, n, code_pitch, sh, static_cast<float *>(onehot), st, s);
-    } else {
-        return launch_code_to_dense<T, 256>(code, n, code_pitch, sh, onehot, fmt, st);
-    }
+DensePlan plan_code_to_dense(int64_t n, int fmt, const Variant &v) {
+    const DenseForm form = dense_form<T>(n, v, false, fmt);
+    if (form == kDenseFront) return plan_front(n, fmt, v);
+    if (form != kDenseWide) return plan_tiles<T>(n, fmt, form);
+    DensePlan p{kDenseWide};
+    const int64_t tiles = ceil_div(n, kWideTile), want = v.thousands ? v.thousands * 16 : kWideGroups;
+    p.per = ceil_div(tiles, want);
+    p.skew = v.tens ? v.tens : kWideSkew;
+    p.grid_x = ceil_div(tiles, p.per);
+    p.block = kWideBlock;
+    return p;
 }
 
+template <class T, class E, bool LDS>
+void launch_front(const uint8_t *code, int64_t n, int64_t code_pitch, int sh, E *onehot, hipStream_t st, const DensePlan &p) {
+    const dim3 g((unsigned)p.grid_x), b(p.block);
+    if (p.f == 4) hipLaunchKernelGGL((k_code_to_dense_front<T, E, 4, LDS>), g, b, 0, st, code, n, code_pitch, sh, onehot, p.per_xcd, p.per_front);
+    else if (p.f == 2) hipLaunchKernelGGL((k_code_to_dense_front<T, E, 2, LDS>), g, b, 0, st, code, n, code_pitch, sh, onehot, p.per_xcd, p.per_front);
+    else hipLaunchKernelGGL((k_code_to_dense_front<T, E, 1, LDS>), g, b, 0, st, code, n, code_pitch, sh, onehot, p.per_xcd, p.per_front);
+}
+// one code -> dense launch of any form; src_bs / dst_bs: the block strides of rc_onehot_from_code_blocks (tile kernels, grid_y blocks)
 template <class T>
-int launch_code_to_dense_wide(const uint8_t *code, int64_t n, int64_t code_pitch, int sh, void *onehot, int fmt, hipStream_t st, int variant) {
-    if constexpr (T::SIZE == 3) {
-        const WideGrid w = wide_grid(n, variant);
-        RC_GRID(w.groups);
-        const int skew = (variant / 10) % 10 ? (variant / 10) % 10 : kWideSkew;
-        const dim3 g((unsigned)w.groups), b(kWideBlock);
-        if (fmt == RC_FMT_U8) hipLaunchKernelGGL((k_code_to_dense_wide<T, uint8_t>), g, b, 0, st, code, n, code_pitch, sh, static_cast<uint8_t *>(onehot), w.per, skew);
-        else if (fmt == RC_FMT_F16) hipLaunchKernelGGL((k_code_to_dense_wide<T, uint16_t>), g, b, 0, st, code, n, code_pitch, sh, static_cast<uint16_t *>(onehot), w.per, skew);
-        else if (fmt == RC_FMT_BF16) hipLaunchKernelGGL((k_code_to_dense_wide<T, Bf16>), g, b, 0, st, code, n, code_pitch, sh, static_cast<Bf16 *>(onehot), w.per, skew);
-        else hipLaunchKernelGGL((k_code_to_dense_wide<T, float>), g, b, 0, st, code, n, code_pitch, sh, static_cast<float *>(onehot), w.per, skew);
+int launch_code_to_dense(const uint8_t *code, int64_t n, int64_t code_pitch, int sh, void *onehot, int fmt, hipStream_t st, const DensePlan &p,
+                         int64_t src_bs = 0, int64_t dst_bs = 0) {
+    RC_GRID(p.grid_x);
+    return by_fmt(fmt, [&](auto e) {
+        using E = typename decltype(e)::type;
+        E *out = static_cast<E *>(onehot);
+        const dim3 g((unsigned)p.grid_x, (unsigned)p.grid_y), b(p.block);
+        if (p.form == kDense64) hipLaunchKernelGGL((k_code_to_dense<T, E, 64>), g, b, 0, st, code, n, code_pitch, sh, out, src_bs, dst_bs);
+        else if (p.form == kDense256) hipLaunchKernelGGL((k_code_to_dense<T, E, 256>), g, b, 0, st, code, n, code_pitch, sh, out, src_bs, dst_bs);
+        else if constexpr (T::SIZE == 3) {
+            if (p.form == kDenseWide) hipLaunchKernelGGL((k_code_to_dense_wide<T, E>), g, b, 0, st, code, n, code_pitch, sh, out, p.per, p.skew);
+            else if (p.lds) launch_front<T, E, true>(code, n, code_pitch, sh, out, st, p);
+            else launch_front<T, E, false>(code, n, code_pitch, sh, out, st, p);
+        } else return fail(RC_EINVAL, "the wide and front writers are 3x3x3 only%s");
         RC_HIP(hipGetLastError());
         return RC_OK;
-    } else {
-        return launch_code_to_dense<T, 256>(code, n, code_pitch, sh, onehot, fmt, st);
+    });
+}
+
+// family rows -> the dense one-hots of all A children and the parent (block a at onehot + a * block_stride cubes): the front writer
+// over (A + 1) * ceil(n / cubes per pass) passes, same shapes per format as the code -> dense launch
+template <class T>
+DensePlan plan_family_to_dense(int64_t n, int fmt, int n_depths) { return plan_front(n, fmt, Variant{}, (int64_t)(T::A + 1) * n_depths); }
+template <class T>
+int launch_family_to_dense(const uint8_t *fam, int64_t n, int64_t pitch, int sh, void *onehot, int fmt, const FamilyBlocks &fb, hipStream_t st, const DensePlan &p) {
+    RC_GRID(p.grid_x);
+    if (p.grid_y > 65535) return fail(RC_EINVAL, "rc_onehot_from_family: at most 5041 depths per launch%s");
+    return by_fmt(fmt, [&](auto e) {                     // (E, F, LDS) of the format's default shape only: four instantiations
+        using F = decltype(e);
+        using E = typename F::type;
+        hipLaunchKernelGGL((k_code_to_dense_front<T, E, F::fronts, F::lds, true>), dim3((unsigned)p.grid_x, (unsigned)p.grid_y), dim3(p.block), 0, st, fam, n, pitch, sh,
+                           static_cast<E *>(onehot), p.per_xcd, p.per_front, fb);
+        RC_HIP(hipGetLastError());
+        return RC_OK;
+    });
+}
+
+// Two-launch dense route (rc_apply_moves_ws): the step kernel writes the compact code into the caller's workspace (one tile,
+// [SLOTS][ws_pitch]), the front writer expands it.  3x3x3 only, from kFrontMin cubes; 0 = not applicable.
+// Measured over 2^17 .. 2^22 cubes (profiles/r04_dense_sizes.json): f32 0.78-0.92 of peak on every allocation against 0.63-0.86
+// (placement dependent) for the one-launch kernel, 16-bit formats 0.65-0.85 against 0.62-0.80.  u8 gains nothing while its state
+// ping-pong fits the Infinity Cache (0.80 against 0.81 at 2^20) and takes the route from 2^22 cubes only (0.79 against 0.65).
+constexpr int64_t kFrontMin = (int64_t)1 << 17, kFrontMinU8 = (int64_t)1 << 22, kWsTile = 32768;     // workspace = a tiled code buffer [tile][SLOTS][32768]
+inline int64_t dense_workspace_bytes(int cube_size, int64_t n, int fmt) {
+    if (cube_size != 3 || !dense_fmt(fmt) || n < (fmt == RC_FMT_U8 ? kFrontMinU8 : kFrontMin)) return 0;
+    return ceil_div(n, kWsTile) * kWsTile * 20;
+}
+
+// One place decides route, pack width, row-traffic policy and grids of a step launch (the launcher and rc_describe_dispatch both call it).
+constexpr int kStepBlock = 64;
+enum StepRoute { kStepAlone, kStepDense, kStepThenFront };   // k_step | k_step_dense | k_step with code into the workspace + the front writer
+struct StepPlan {
+    StepRoute route;
+    int v, pol;               // k_step: pack width, row policy, CODE, grid and block
+    bool code;
+    int64_t grid;
+    int block;
+    int64_t ws_need;          // kStepThenFront: bytes of the workspace the two launches use
+    DensePlan dense;          // kStepDense: k_step_dense with TILE = dense.form; kStepThenFront: the second launch
+};
+// ws_bytes: the caller's workspace (0 = none).  kStepThenFront keeps the compact code for the next launch: beyond the resident case it
+// is written with POL 4.
+template <class T>
+StepPlan plan_step(int64_t n, bool writes, bool in_place, bool code, bool done, bool reward, int fmt, const Variant &v, int64_t ws_bytes) {
+    StepPlan p{};
+    if (dense_fmt(fmt)) {
+        p.ws_need = dense_workspace_bytes(T::SIZE, n, fmt);
+        p.route = p.ws_need > 0 && ws_bytes >= p.ws_need && v.form == 0 ? kStepThenFront : kStepDense;
+        p.dense = p.route == kStepThenFront ? plan_front(n, fmt, Variant{}) : plan_tiles<T>(n, fmt, dense_form<T>(n, v, true, fmt));   // fused: 64- / 256-cube tiles only
+        if (p.route == kStepDense) return p;
     }
+    p.code = code || p.route == kStepThenFront;
+    p.v = pick_v(n, v);
+    p.pol = pick_policy(n * T::S, writes ? n * T::S : 0, writes && in_place, side_bytes<T>(n, p.code, done, reward), v);
+    if (p.route == kStepThenFront && p.pol != 0) p.pol = 4;
+    p.grid = ceil_div(n, 4 * p.v * kStepBlock);
+    p.block = kStepBlock;
+    return p;
+}
+
+template <class T, int V, bool MOVE, bool CODE>
+int launch_step(const StepArgs &a, hipStream_t st, const StepPlan &p) {
+    RC_GRID(p.grid);
+    const dim3 g((unsigned)p.grid), b(p.block);
+    if (p.pol == 4) {
+        if constexpr (CODE) hipLaunchKernelGGL((k_step<T, V, MOVE, MOVE, CODE, 4, kStepBlock>), g, b, 0, st, a);
+        else return fail(RC_EINVAL, "row policy 4 belongs to the workspace route%s");
+    } else if (p.pol == 3) hipLaunchKernelGGL((k_step<T, V, MOVE, MOVE, CODE, 3, kStepBlock>), g, b, 0, st, a);
+    else if (p.pol == 2) hipLaunchKernelGGL((k_step<T, V, MOVE, MOVE, CODE, 2, kStepBlock>), g, b, 0, st, a);
+    else if (p.pol == 1) hipLaunchKernelGGL((k_step<T, V, MOVE, MOVE, CODE, 1, kStepBlock>), g, b, 0, st, a);
+    else hipLaunchKernelGGL((k_step<T, V, MOVE, MOVE, CODE, 0, kStepBlock>), g, b, 0, st, a);
+    RC_HIP(hipGetLastError());
+    return RC_OK;
+}
+template <class T, bool MOVE, int TILE>
+int launch_step_dense(const StepArgs &a, void *onehot, int fmt, hipStream_t st, const DensePlan &p) {
+    RC_GRID(p.grid_x);
+    return by_fmt(fmt, [&](auto e) {
+        using E = typename decltype(e)::type;
+        hipLaunchKernelGGL((k_step_dense<T, E, MOVE, MOVE, TILE>), dim3((unsigned)p.grid_x), dim3(p.block), 0, st, a, static_cast<E *>(onehot));
+        RC_HIP(hipGetLastError());
+        return RC_OK;
+    });
+}
+// MOVE: move + store (rc_apply_moves*), else the flags / encoding of the states as they are; a.code is the workspace on the two-launch route
+template <class T, bool MOVE>
+int launch_step_plan(const StepArgs &a, void *onehot, int fmt, hipStream_t st, const StepPlan &p) {
+    if (p.route == kStepDense)
+        return p.dense.form == kDense64 ? launch_step_dense<T, MOVE, 64>(a, onehot, fmt, st, p.dense) : launch_step_dense<T, MOVE, 256>(a, onehot, fmt, st, p.dense);
+    int rc;
+    if (p.code) rc = p.v == 2 ? launch_step<T, 2, MOVE, true>(a, st, p) : launch_step<T, 1, MOVE, true>(a, st, p);
+    else rc = p.v == 2 ? launch_step<T, 2, MOVE, false>(a, st, p) : launch_step<T, 1, MOVE, false>(a, st, p);
+    if (rc || p.route != kStepThenFront) return rc;
+    return launch_code_to_dense<T>(a.code, a.n, a.code_pitch, a.sh_code, onehot, fmt, st, p.dense);
 }
 
 int check_fmt(void *onehot, int fmt, int64_t code_pitch, int64_t n, int *sh_code) {
@@ -1508,16 +1536,15 @@ int check_fmt(void *onehot, int fmt, int64_t code_pitch, int64_t n, int *sh_code
 struct Geometry { int v, parts, segs; };
 constexpr int64_t kExpandStreamGrid = 512;   // 1M parents: 113 us (0.83) with 512 waves, 114 (256), 115 (1024), 116.4 us for 2048 short-lived waves
 constexpr double kReplayCostCodes = 0.2, kReplayCostStickers = 0.35;   // replayed depth / emitted depth (RNG + move against everything)
-Geometry pick_geometry(int64_t n, int A, int variant, bool stickers_out, int64_t out_bytes) {
-    const int fv = variant % 10, fp = (variant / 1000) % 100;
+Geometry pick_geometry(int64_t n, int A, const Variant &var, bool stickers_out, int64_t out_bytes) {
     const bool stream = stickers_out && out_bytes >= ((int64_t)256 << 20);
     const int64_t want = stream ? 96 : stickers_out ? 2048 : 700;
     int v = 1;
-    if (fv == 1 || fv == 2) v = fv;
+    if (var.units == 1 || var.units == 2) v = var.units;
     else if (stream && n >= want * kWave * 8) v = 2;
-    const int64_t groups = (n + kWave * 4 * v - 1) / (kWave * 4 * v);
+    const int64_t groups = ceil_div(n, kWave * 4 * v);
     int parts = 1;
-    if (fp >= 1 && fp <= A) parts = fp;
+    if (var.thousands >= 1 && var.thousands <= A) parts = var.thousands;
     else while (parts < A && groups * parts < want) ++parts;
     while (A % parts) ++parts;
     return {v, parts, 1};
@@ -1530,13 +1557,12 @@ Geometry pick_geometry(int64_t n, int A, int variant, bool stickers_out, int64_t
 // FAMILY records (118 B per state instead of 327): with a third of the stores the launch is VALU-bound and wants MORE, narrower
 // waves -- 4 walks per lane and about 1560 waves (100k x 30: 82 us against 109 us with 8 walks per lane x 4 segments and 89 us x 5;
 // 1M x 4: 86 us against 103 us; profiles/r04_adi_family.json); small batches keep the 700-wave rule (20k x 30: 36 us).
-Geometry pick_geometry_adi(int64_t n, int A, int variant, bool stickers_out, int64_t out_bytes, bool codes, bool family = false) {
-    Geometry g = pick_geometry(n, A, variant, stickers_out, out_bytes);
+Geometry pick_geometry_adi(int64_t n, int A, const Variant &var, bool stickers_out, int64_t out_bytes, bool codes, bool family) {
+    Geometry g = pick_geometry(n, A, var, stickers_out, out_bytes);
     if (codes && !stickers_out) {
-        const int fv = variant % 10, fp = (variant / 1000) % 100;
-        g.v = fv == 1 || fv == 2 ? fv : (n >= 64 * kWave * 8 && !family ? 2 : 1);
-        g.parts = fp >= 1 && fp <= A ? g.parts : 1;
-        const int64_t waves = (n + kWave * 4 * g.v - 1) / (kWave * 4 * g.v) * g.parts;
+        g.v = var.units == 1 || var.units == 2 ? var.units : (n >= 64 * kWave * 8 && !family ? 2 : 1);
+        g.parts = var.thousands >= 1 && var.thousands <= A ? g.parts : 1;
+        const int64_t waves = ceil_div(n, kWave * 4 * g.v) * g.parts;
         const int64_t target = !family ? 600 : n >= 64 * kWave * 8 ? 1560 : 700;
         const int64_t segs = (target + waves / 2) / (waves > 0 ? waves : 1);
         g.segs = segs < 1 ? 1 : segs > kMaxSegs ? kMaxSegs : (int)segs;
@@ -1544,71 +1570,104 @@ Geometry pick_geometry_adi(int64_t n, int A, int variant, bool stickers_out, int
     return g;
 }
 
+struct AdiPlan {
+    int v, parts, segs;                    // walks per lane / 4, waves per walk group, depth segments (1..kMaxSegs, at most the depth)
+    uint16_t seg_lo[kMaxSegs + 1];         // AdiArgs::seg_lo
+    bool code, family;                     // k_adi<T, V, CODE, FAM>
+    int64_t grid;
+    int block;
+};
 // Depth segments of the ADI kernel (k_adi): boundaries that equalise the work of the segments when a replayed depth
 // costs `replay` of an emitted one (segment s replays seg_lo[s] depths and emits seg_lo[s+1] - seg_lo[s]).
-void fill_segments(AdiArgs &a, int segs, double replay) {
-    if (segs > a.depth) segs = a.depth;
+void fill_segments(AdiPlan &p, int depth, int segs, double replay) {
+    if (segs > depth) segs = depth;
     if (segs > kMaxSegs) segs = kMaxSegs;
     if (segs < 1) segs = 1;
-    a.segs = segs;
-    double lo_c = 0, hi_c = a.depth;                        // bisection on the per-segment cost
+    p.segs = segs;
+    double lo_c = 0, hi_c = depth;                          // bisection on the per-segment cost
     for (int it = 0; it < 60; ++it) {
         const double c = 0.5 * (lo_c + hi_c);
         double lo = 0;
         for (int k = 0; k < segs; ++k) lo += c - replay * lo > 0 ? c - replay * lo : 0;
-        (lo < a.depth ? lo_c : hi_c) = c;
+        (lo < depth ? lo_c : hi_c) = c;
     }
     double lo = 0;
     int prev = 0;
-    a.seg_lo[0] = 0;
+    p.seg_lo[0] = 0;
     for (int k = 1; k <= segs; ++k) {
         lo += hi_c - replay * lo;
-        int b = k == segs ? a.depth : (int)(lo + 0.5);
+        int b = k == segs ? depth : (int)(lo + 0.5);
         if (b < prev + 1) b = prev + 1;                      // every segment emits at least one depth ...
-        if (b > a.depth - (segs - k)) b = a.depth - (segs - k);   // ... and leaves one for each later segment
-        a.seg_lo[k] = (uint16_t)b;
+        if (b > depth - (segs - k)) b = depth - (segs - k);  // ... and leaves one for each later segment
+        p.seg_lo[k] = (uint16_t)b;
         prev = b;
     }
 }
+// stickers / codes / family: the child stickers, any compact code (the family record included), the family record are written;
+// any_child: some per-child output is (without one a single part does all there is to do, unless the caller forces `parts`)
+template <class T>
+AdiPlan plan_adi(int64_t n, int depth, bool stickers, bool codes, bool family, bool any_child, const Variant &v) {
+    const Geometry geo = pick_geometry_adi(n, T::A, v, stickers, n * depth * T::S * T::A, codes, family);
+    AdiPlan p{};
+    p.v = geo.v;
+    p.parts = !any_child && v.thousands == 0 ? 1 : geo.parts;
+    p.code = codes;
+    p.family = family;
+    // a replayed depth is RNG + move; an emitted one adds the flags, the code look-ups and the stores
+    fill_segments(p, depth, v.segs ? v.segs : geo.segs, codes ? kReplayCostCodes : kReplayCostStickers);
+    p.grid = ceil_div(n, kWave * 4 * p.v) * p.parts * p.segs;
+    p.block = kWave;
+    return p;
+}
 
-// grid of the streaming expansion: hundreds digit of `variant` 1..7 -> 128, 192, 256, 384, 512, 768, 1024 waves; 8 -> not streamed
+// EXPAND: the streaming form (few persistent waves) against k_expand.
+// Grid of the streaming expansion: hundreds digit of `variant` 1..7 -> 128, 192, 256, 384, 512, 768, 1024 waves; 8 -> not streamed
 // out_bytes = n * S * A of the cube size at hand (1M 2x2x2 parents write 151 MB: below the threshold, they keep k_expand -- the
 // streaming form was only measured on 3x3x3).  A forced `parts` value (thousands field, 1 included) or pack width 1 selects k_expand.
-inline int64_t expand_stream_grid(int64_t out_bytes, bool stickers, bool codes, int variant) {
+inline int64_t expand_stream_grid(int64_t out_bytes, bool stickers, bool codes, const Variant &v) {
     static const int table[8] = {0, 128, 192, 256, 384, 512, 768, 1024};
-    const int h = (variant / 100) % 10;
-    if (!stickers || codes || h == 8 || (variant % 10) == 1 || (variant / 1000) % 100 >= 1) return 0;
-    if (h >= 1 && h <= 7) return table[h];                         // forced (tests reach the kernel with small batches too)
+    if (!stickers || codes || v.hundreds == 8 || v.units == 1 || v.thousands >= 1) return 0;
+    if (v.hundreds >= 1 && v.hundreds <= 7) return table[v.hundreds];   // forced (tests reach the kernel with small batches too)
     return out_bytes >= ((int64_t)256 << 20) ? kExpandStreamGrid : 0;   // large write-once streams only
+}
+struct ExpandPlan {
+    bool stream;              // k_expand_stream, else k_expand<T, V, CODE>
+    int v, parts;
+    bool code;
+    int64_t grid;
+    int block;
+};
+template <class T>
+ExpandPlan plan_expand(int64_t n, bool stickers, bool codes, const Variant &v) {
+    const Geometry geo = pick_geometry(n, T::A, v, stickers, n * T::S * T::A);
+    ExpandPlan p{false, geo.v, geo.parts, codes, ceil_div(n, kWave * 4 * geo.v) * geo.parts, kWave};
+    if (const int64_t grid = expand_stream_grid(n * T::S * T::A, stickers, codes, v)) {
+        const int64_t groups = ceil_div(n, kWave * 8);
+        p.stream = true;
+        p.grid = grid < groups ? grid : groups;
+    }
+    return p;
 }
 
 template <class T>
-int launch_expand_stream(ExpandArgs a, hipStream_t st, int64_t grid) {
-    const int64_t groups = (a.n + kWave * 8 - 1) / (kWave * 8);
-    if (grid > groups) grid = groups;
-    hipLaunchKernelGGL((k_expand_stream<T>), dim3((unsigned)grid), dim3(kWave), 0, st, a);
+int launch_expand(const ExpandArgs &a, hipStream_t st, const ExpandPlan &p) {
+    RC_GRID(p.grid);
+    const dim3 g((unsigned)p.grid), b(p.block);
+    if (p.stream) hipLaunchKernelGGL((k_expand_stream<T>), g, b, 0, st, a);
+    else if (p.v == 2 && p.code) hipLaunchKernelGGL((k_expand<T, 2, true>), g, b, 0, st, a);
+    else if (p.v == 2) hipLaunchKernelGGL((k_expand<T, 2, false>), g, b, 0, st, a);
+    else if (p.code) hipLaunchKernelGGL((k_expand<T, 1, true>), g, b, 0, st, a);
+    else hipLaunchKernelGGL((k_expand<T, 1, false>), g, b, 0, st, a);
     RC_HIP(hipGetLastError());
     return RC_OK;
 }
 
 template <class T, int V>
-int launch_expand(ExpandArgs a, hipStream_t st) {
-    const int64_t groups = (a.n + kWave * 4 * V - 1) / (kWave * 4 * V);
-    RC_GRID(groups * a.parts);
-    const dim3 g((unsigned)(groups * a.parts)), b(kWave);
-    if (a.child_code) hipLaunchKernelGGL((k_expand<T, V, true>), g, b, 0, st, a);
-    else hipLaunchKernelGGL((k_expand<T, V, false>), g, b, 0, st, a);
-    RC_HIP(hipGetLastError());
-    return RC_OK;
-}
-
-template <class T, int V>
-int launch_adi(AdiArgs a, hipStream_t st) {
-    const int64_t groups = (a.n_walks + kWave * 4 * V - 1) / (kWave * 4 * V);
-    RC_GRID(groups * a.parts * a.segs);
-    const dim3 g((unsigned)(groups * a.parts * a.segs)), b(kWave);
-    if (a.family) hipLaunchKernelGGL((k_adi<T, V, true, true>), g, b, 0, st, a);      // (adi_common: no codes beside the family record)
-    else if (a.parent_code || a.child_code) hipLaunchKernelGGL((k_adi<T, V, true>), g, b, 0, st, a);
+int launch_adi(const AdiArgs &a, hipStream_t st, const AdiPlan &p) {
+    RC_GRID(p.grid);
+    const dim3 g((unsigned)p.grid), b(p.block);
+    if (p.family) hipLaunchKernelGGL((k_adi<T, V, true, true>), g, b, 0, st, a);      // (adi_common: no codes beside the family record)
+    else if (p.code) hipLaunchKernelGGL((k_adi<T, V, true>), g, b, 0, st, a);
     else hipLaunchKernelGGL((k_adi<T, V, false>), g, b, 0, st, a);
     RC_HIP(hipGetLastError());
     return RC_OK;
@@ -1681,22 +1740,12 @@ int rc_fill_solved(uint8_t *stp, int64_t n, int64_t pitch, int cube_size, void *
     });
 }
 
-// Two-launch dense route (rc_apply_moves_ws): the step kernel writes the compact code into the caller's workspace (one tile,
-// [SLOTS][ws_pitch]), the front writer expands it.  3x3x3 only, from kFrontMin cubes; 0 = not applicable.
-// Measured over 2^17 .. 2^22 cubes (profiles/r04_dense_sizes.json): f32 0.78-0.92 of peak on every allocation against 0.63-0.86
-// (placement dependent) for the one-launch kernel, 16-bit formats 0.65-0.85 against 0.62-0.80.  u8 gains nothing while its state
-// ping-pong fits the Infinity Cache (0.80 against 0.81 at 2^20) and takes the route from 2^22 cubes only (0.79 against 0.65).
-constexpr int64_t kFrontMin = (int64_t)1 << 17, kFrontMinU8 = (int64_t)1 << 22, kWsTile = 32768;     // workspace = a tiled code buffer [tile][SLOTS][32768]
-inline int64_t dense_workspace_bytes(int cube_size, int64_t n, int fmt) {
-    if (cube_size != 3 || fmt < RC_FMT_U8 || fmt > RC_FMT_BF16 || n < (fmt == RC_FMT_U8 ? kFrontMinU8 : kFrontMin)) return 0;
-    return (n + kWsTile - 1) / kWsTile * kWsTile * 20;
-}
-
 static int step_common(const uint8_t *in, uint8_t *out, const uint8_t *actions, int64_t n, int64_t pitch_in, int64_t pitch_out,
                        int cube_size, float *reward, uint8_t *done, void *onehot, int fmt, int64_t code_pitch, void *stream,
                        bool move, bool store, int variant, void *workspace = nullptr, int64_t workspace_bytes = 0) {
     RC_NEED_INIT();
-    if (int rc = check_variant(RC_OP_STEP, 12, variant)) return rc;
+    const Variant v = decode_variant(variant);
+    if (int rc = check_variant(RC_OP_STEP, 12, v)) return rc;
     const int sh_in = tile_shift(pitch_in, n), sh_out = store ? tile_shift(pitch_out, n) : 63;
     int sh_code = 63;
     if (!in || !aligned16(in) || n < 0 || sh_in < 0) return fail(RC_EINVAL, "bad input state buffer / pitch%s");
@@ -1710,43 +1759,28 @@ static int step_common(const uint8_t *in, uint8_t *out, const uint8_t *actions, 
     if (n == 0) return RC_OK;
     StepArgs a{in, out, actions, n, pitch_in, pitch_out, reward, done, fmt == RC_FMT_CODE ? static_cast<uint8_t *>(onehot) : nullptr, code_pitch,
                sh_in, sh_out, sh_code};
-    hipStream_t st = S(stream);
     return by_size(cube_size, [&](auto t) {
         using T = decltype(t);
-        if (fmt >= RC_FMT_U8) {
-            if constexpr (T::SIZE == 3) {
-                const int64_t need = dense_workspace_bytes(3, n, fmt);
-                if (workspace && need > 0 && workspace_bytes >= need && (variant / 100000) % 10 == 0) {
-                    // the workspace is written by the first launch and read by the second while `onehot` is being written: it must not
-                    // share a byte with any operand (a caller carving it out of the one-hot allocation would get silently wrong rows)
-                    const auto hits = [&](const void *p, int64_t bytes) {
-                        const uintptr_t w0 = reinterpret_cast<uintptr_t>(workspace), p0 = reinterpret_cast<uintptr_t>(p);
-                        return p != nullptr && bytes > 0 && p0 < w0 + (uintptr_t)need && w0 < p0 + (uintptr_t)bytes;
-                    };
-                    const auto state_bytes = [&](int64_t pitch) { return (n <= pitch ? 1 : (n + pitch - 1) / pitch) * T::S * pitch; };
-                    const int64_t esize = fmt == RC_FMT_U8 ? 1 : fmt == RC_FMT_F32 ? 4 : 2;
-                    if (hits(in, state_bytes(pitch_in)) || (store && hits(out, state_bytes(pitch_out))) || hits(actions, n) || hits(reward, 4 * n) ||
-                        hits(done, n) || hits(onehot, n * T::R * T::C * esize))
-                        return fail(RC_EINVAL, "workspace overlaps an input or output buffer%s");
-                    // step (or encode) + reward + done + compact code (into the workspace), then the front writer: the dense stream
-                    // leaves as one sweeping window instead of thousands of private 240-KiB streams (k_code_to_dense_front)
-                    StepArgs a2 = a;
-                    a2.code = static_cast<uint8_t *>(workspace);
-                    a2.code_pitch = kWsTile;
-                    a2.sh_code = 15;                                                 // log2(kWsTile)
-                    if (int rc = move ? dispatch_step<T, true, true, true>(a2, st, variant, true) : dispatch_step<T, false, false, true>(a2, st, variant, true)) return rc;
-                    return launch_code_to_dense_front<T>(a2.code, n, a2.code_pitch, a2.sh_code, onehot, fmt, st, 0);
-                }
-            }
-            if (move) return launch_dense<T, true, true>(a, onehot, fmt, st, variant);
-            return launch_dense<T, false, false>(a, onehot, fmt, st, variant);
+        const StepPlan p = plan_step<T>(n, store, store && out == in, fmt == RC_FMT_CODE, done != nullptr, reward != nullptr, fmt, v, workspace ? workspace_bytes : 0);
+        if (p.route == kStepThenFront) {
+            // the workspace is written by the first launch and read by the second while `onehot` is being written: it must not
+            // share a byte with any operand (a caller carving it out of the one-hot allocation would get silently wrong rows)
+            const auto hits = [&](const void *q, int64_t bytes) {
+                const uintptr_t w0 = reinterpret_cast<uintptr_t>(workspace), q0 = reinterpret_cast<uintptr_t>(q);
+                return q != nullptr && bytes > 0 && q0 < w0 + (uintptr_t)p.ws_need && w0 < q0 + (uintptr_t)bytes;
+            };
+            const auto state_bytes = [&](int64_t pitch) { return (n <= pitch ? 1 : (n + pitch - 1) / pitch) * T::S * pitch; };
+            const int64_t esize = by_fmt(fmt, [](auto e) { return decltype(e)::size; });
+            if (hits(in, state_bytes(pitch_in)) || (store && hits(out, state_bytes(pitch_out))) || hits(actions, n) || hits(reward, 4 * n) ||
+                hits(done, n) || hits(onehot, n * T::R * T::C * esize))
+                return fail(RC_EINVAL, "workspace overlaps an input or output buffer%s");
+            // step (or encode) + reward + done + compact code (into the workspace), then the front writer: the dense stream
+            // leaves as one sweeping window instead of thousands of private 240-KiB streams (k_code_to_dense_front)
+            a.code = static_cast<uint8_t *>(workspace);
+            a.code_pitch = kWsTile;
+            a.sh_code = 15;                                                 // log2(kWsTile)
         }
-        if (move) {
-            if (fmt == RC_FMT_CODE) return dispatch_step<T, true, true, true>(a, st, variant);
-            return dispatch_step<T, true, true, false>(a, st, variant);
-        }
-        if (fmt == RC_FMT_CODE) return dispatch_step<T, false, false, true>(a, st, variant);
-        return dispatch_step<T, false, false, false>(a, st, variant);
+        return move ? launch_step_plan<T, true>(a, onehot, fmt, S(stream), p) : launch_step_plan<T, false>(a, onehot, fmt, S(stream), p);
     });
 }
 
@@ -1878,19 +1912,15 @@ int rc_encode_ws(const uint8_t *stp, int64_t n, int64_t pitch, int cube_size, vo
 
 int rc_onehot_from_code_ex(const uint8_t *code, int64_t n, int64_t code_pitch, int cube_size, void *onehot, int fmt, void *stream, int variant) {
     RC_NEED_INIT();
-    if (int rc = check_variant(RC_OP_CODE_TO_DENSE, 12, variant)) return rc;
+    const Variant v = decode_variant(variant);
+    if (int rc = check_variant(RC_OP_CODE_TO_DENSE, 12, v)) return rc;
     const int sh = tile_shift(code_pitch, n, 20);
     if (!code || !aligned16(code) || n < 0 || sh < 0) return fail(RC_EINVAL, "bad code buffer / pitch%s");
     if (fmt < RC_FMT_U8 || fmt > RC_FMT_BF16 || !onehot || !aligned16(onehot)) return fail(RC_EINVAL, "rc_onehot_from_code: dense fmt and aligned buffer required%s");
     if (n == 0) return RC_OK;
     return by_size(cube_size, [&](auto t) {
         using T = decltype(t);
-        switch (dense_form<T>(n, variant, false, fmt)) {
-            case kDenseFront: return launch_code_to_dense_front<T>(code, n, code_pitch, sh, onehot, fmt, S(stream), variant);
-            case kDenseWide: return launch_code_to_dense_wide<T>(code, n, code_pitch, sh, onehot, fmt, S(stream), variant);
-            case kDense256: return launch_code_to_dense<T, 256>(code, n, code_pitch, sh, onehot, fmt, S(stream));
-            default: return launch_code_to_dense<T, 64>(code, n, code_pitch, sh, onehot, fmt, S(stream));
-        }
+        return launch_code_to_dense<T>(code, n, code_pitch, sh, onehot, fmt, S(stream), plan_code_to_dense<T>(n, fmt, v));
     });
 }
 
@@ -1906,22 +1936,23 @@ int rc_onehot_from_code_blocks(const uint8_t *code, int64_t n, int64_t code_pitc
     if (fmt < RC_FMT_U8 || fmt > RC_FMT_BF16 || !onehot || !aligned16(onehot)) return fail(RC_EINVAL, "rc_onehot_from_code_blocks: dense fmt and aligned buffer required%s");
     if (n_blocks < 1 || n_blocks > 65535 || src_block_stride < 0 || src_block_stride % 16 || dst_block_stride < n)
         return fail(RC_EINVAL, "rc_onehot_from_code_blocks: 1..65535 blocks, source stride a multiple of 16 bytes, destination stride >= n cubes%s");
-    const int64_t esz = fmt == RC_FMT_U8 ? 1 : fmt == RC_FMT_F32 ? 4 : 2;
+    const int64_t esz = by_fmt(fmt, [](auto e) { return decltype(e)::size; });
     if (n == 0) return RC_OK;
     return by_size(cube_size, [&](auto t) {
         using T = decltype(t);
         if ((dst_block_stride * T::R * T::C * esz) % 16) return fail(RC_EINVAL, "rc_onehot_from_code_blocks: every block of the output must start 16-byte aligned%s");
         // the tile kernels only (blocks of a small batch: the front / wide forms pay off from 2^15 cubes per launch, and a caller with
         // blocks that large loses nothing by launching them one by one)
-        if (n >= ((int64_t)1 << 17) && !(T::SIZE == 2 && fmt != RC_FMT_U8)) return launch_code_to_dense<T, 256>(code, n, code_pitch, sh, onehot, fmt, S(stream), n_blocks, src_block_stride, dst_block_stride);
-        return launch_code_to_dense<T, 64>(code, n, code_pitch, sh, onehot, fmt, S(stream), n_blocks, src_block_stride, dst_block_stride);
+        const DenseForm tile = n >= ((int64_t)1 << 17) && !(T::SIZE == 2 && fmt != RC_FMT_U8) ? kDense256 : kDense64;
+        return launch_code_to_dense<T>(code, n, code_pitch, sh, onehot, fmt, S(stream), plan_tiles<T>(n, fmt, tile, n_blocks), src_block_stride, dst_block_stride);
     });
 }
 
 int rc_expand_children_ex(const uint8_t *in, int64_t n, int64_t pitch_in, int cube_size, uint8_t *children, uint8_t *child_solved,
                           uint8_t *child_code, int64_t pitch_out, void *stream, int variant) {
     RC_NEED_INIT();
-    if (int rc = check_variant(RC_OP_EXPAND, cube_size == 2 ? 6 : 12, variant)) return rc;
+    const Variant v = decode_variant(variant);
+    if (int rc = check_variant(RC_OP_EXPAND, cube_size == 2 ? 6 : 12, v)) return rc;
     const int sh_in = tile_shift(pitch_in, n), sh_out = tile_shift(pitch_out, n);
     if (!in || !aligned16(in) || n < 0 || sh_in < 0 || sh_out < 0) return fail(RC_EINVAL, "rc_expand_children: bad buffer / pitch%s");
     if (!children && !child_solved && !child_code) return fail(RC_EINVAL, "rc_expand_children: nothing to write%s");
@@ -1930,12 +1961,10 @@ int rc_expand_children_ex(const uint8_t *in, int64_t n, int64_t pitch_in, int cu
     if (n == 0) return RC_OK;
     return by_size(cube_size, [&](auto t) {
         using T = decltype(t);
-        const Geometry geo = pick_geometry(n, T::A, variant, children != nullptr, n * T::S * T::A);
-        ExpandArgs a{in, n, pitch_in, children, child_solved, child_code, pitch_out, n <= pitch_out ? 1 : (n + pitch_out - 1) / pitch_out,
-                     geo.parts, sh_in, sh_out};
-        hipStream_t st = S(stream);
-        if (const int64_t grid = expand_stream_grid(n * T::S * T::A, children != nullptr, child_code != nullptr, variant)) return launch_expand_stream<T>(a, st, grid);
-        return geo.v == 2 ? launch_expand<T, 2>(a, st) : launch_expand<T, 1>(a, st);
+        const ExpandPlan p = plan_expand<T>(n, children != nullptr, child_code != nullptr, v);
+        const ExpandArgs a{in, n, pitch_in, children, child_solved, child_code, pitch_out, n <= pitch_out ? 1 : (n + pitch_out - 1) / pitch_out,
+                           p.parts, sh_in, sh_out};
+        return launch_expand<T>(a, S(stream), p);
     });
 }
 
@@ -1948,7 +1977,8 @@ static int adi_common(uint64_t seed, uint64_t stream_id, int64_t walk_offset, in
                       const uint8_t *actions_in, uint8_t *actions_out, uint8_t *parents, uint8_t *parent_code, uint8_t *children,
                       uint8_t *child_code, uint8_t *child_solved, uint8_t *family, void *stream, int variant) {
     RC_NEED_INIT();
-    if (int rc = check_variant(RC_OP_ADI, cube_size == 2 ? 6 : 12, variant)) return rc;
+    const Variant v = decode_variant(variant);
+    if (int rc = check_variant(RC_OP_ADI, cube_size == 2 ? 6 : 12, v)) return rc;
     if (family && !aligned16(family)) return fail(RC_EINVAL, "rc_adi_generate: buffers must be 16-byte aligned%s");
     const int sh = tile_shift(pitch, n_walks);
     if (n_walks < 0 || depth < 0 || sh < 0) return fail(RC_EINVAL, "rc_adi_generate: bad sizes / pitch%s");
@@ -1958,18 +1988,13 @@ static int adi_common(uint64_t seed, uint64_t stream_id, int64_t walk_offset, in
     if (n_walks == 0 || depth == 0) return RC_OK;
     return by_size(cube_size, [&](auto t) {
         using T = decltype(t);
-        const bool any_child = children || child_code || child_solved;
-        Geometry geo = pick_geometry_adi(n_walks, T::A, variant, children != nullptr, n_walks * depth * T::S * T::A, parent_code || child_code || family, family != nullptr);
-        if (!any_child && (variant / 1000) % 100 == 0) geo.parts = 1;
-        AdiArgs a{seed, stream_id, walk_offset, n_walks, pitch, n_walks <= pitch ? 1 : (n_walks + pitch - 1) / pitch, depth,
-                  geo.parts, sh, actions_in, actions_out, parents, parent_code, children, child_code, child_solved, family, 1, {}};
         if (depth > 0xffff) return fail(RC_EINVAL, "rc_adi_generate: depth must be below 65536%s");
-        const int fsegs = (variant / 1000000) % 100;
-        const bool codes = parent_code || child_code || family;
-        // a replayed depth is RNG + move; an emitted one adds the flags, the code look-ups and the stores
-        fill_segments(a, fsegs ? fsegs : geo.segs, codes ? kReplayCostCodes : kReplayCostStickers);
-        hipStream_t st = S(stream);
-        return geo.v == 2 ? launch_adi<T, 2>(a, st) : launch_adi<T, 1>(a, st);
+        const AdiPlan p = plan_adi<T>(n_walks, depth, children != nullptr, parent_code || child_code || family, family != nullptr,
+                                      children || child_code || child_solved, v);
+        AdiArgs a{seed, stream_id, walk_offset, n_walks, pitch, n_walks <= pitch ? 1 : (n_walks + pitch - 1) / pitch, depth,
+                  p.parts, sh, actions_in, actions_out, parents, parent_code, children, child_code, child_solved, family, p.segs, {}};
+        memcpy(a.seg_lo, p.seg_lo, sizeof a.seg_lo);
+        return p.v == 2 ? launch_adi<T, 2>(a, S(stream), p) : launch_adi<T, 1>(a, S(stream), p);
     });
 }
 
@@ -2015,8 +2040,8 @@ int rc_onehot_from_family_depths(const uint8_t *family, int64_t n, int64_t pitch
     if (n_depths < 0 || n_depths > 5041) return fail(RC_EINVAL, "rc_onehot_from_family: n_depths must be in 0..5041%s");
     if (n == 0 || n_depths == 0) return RC_OK;
     const int64_t tiles = n <= pitch ? 1 : (n + pitch - 1) / pitch;
-    const FamilyDepths dp{n_depths, tiles * kFamily<Cube3>.nf * pitch, (int64_t)(Cube3::A + 1) * block_stride};
-    return launch_family_to_dense<Cube3>(family, n, pitch, sh, onehot, fmt, block_stride, dp, S(stream));
+    const FamilyBlocks fb{block_stride, tiles * kFamily<Cube3>.nf * pitch, (int64_t)(Cube3::A + 1) * block_stride};   // + bytes of one depth's record / cubes of one depth's blocks
+    return launch_family_to_dense<Cube3>(family, n, pitch, sh, onehot, fmt, fb, S(stream), plan_family_to_dense<Cube3>(n, fmt, n_depths));
 }
 
 int rc_onehot_from_family(const uint8_t *family, int64_t n, int64_t pitch, int cube_size, void *onehot, int fmt, int64_t block_stride, void *stream) {
@@ -2177,95 +2202,65 @@ int rc_facade_expand(const uint8_t *stp, int64_t pitch, int cube_size, uint8_t *
     return facade_wait(host_out, seq, stream, "rc_facade_expand");
 }
 
-// What a call WOULD launch, from the same pick_* functions the launchers use (benchmarks label their records with this, so a
+// What a call WOULD launch: the plan_* function the launcher of `op` runs, formatted (benchmarks label their records with this, so a
 // change of the dispatch policy cannot leave a stale kernel name behind).
 int rc_describe_dispatch(int op, int cube_size, int64_t n, int depth, unsigned outputs, int fmt, int variant, char *buf, int buflen) {
     if (!buf || buflen < 16) return fail(RC_EINVAL, "rc_describe_dispatch: buffer too small%s");
     if (n <= 0) return fail(RC_EINVAL, "rc_describe_dispatch: n must be positive%s");
     if (op != RC_OP_STEP && op != RC_OP_EXPAND && op != RC_OP_ADI && op != RC_OP_CODE_TO_DENSE && op != RC_OP_FAMILY_TO_DENSE)
         return fail(RC_EINVAL, "rc_describe_dispatch: unknown op%s");
-    if (int rc = check_variant(op, cube_size == 2 ? 6 : 12, variant)) return rc;
+    const Variant v = decode_variant(variant);
+    if (int rc = check_variant(op, cube_size == 2 ? 6 : 12, v)) return rc;
     return by_size(cube_size, [&](auto t) {
         using T = decltype(t);
         const char *cube = T::SIZE == 3 ? "Cube3" : "Cube2";
-        const bool states = outputs & RC_OUT_STATES, code = outputs & RC_OUT_CODE;
+        const bool states = outputs & RC_OUT_STATES, code = outputs & RC_OUT_CODE, family = outputs & RC_OUT_FAMILY;
+        const auto name = [&] { return by_fmt(fmt, [](auto e) { return decltype(e)::name; }); };
+        const auto fetch = [](const DensePlan &d) { return d.lds ? "lds" : "gather"; };
         if (op == RC_OP_STEP) {
-            if (fmt >= RC_FMT_U8 && fmt <= RC_FMT_BF16) {
-                static const char *const names[] = {"", "", "u8", "f16", "f32", "bf16"};
-                if ((outputs & RC_OUT_WORKSPACE) && dense_workspace_bytes(T::SIZE, n, fmt) > 0 && (variant / 100000) % 10 == 0) {
-                    StepPlan p = plan_step<T>(n, states, states && (outputs & RC_OUT_INPLACE), true, outputs & RC_OUT_DONE, outputs & RC_OUT_REWARD, variant);
-                    if (p.pol != 0) p.pol = 4;
-                    const int cpp = fmt == RC_FMT_F32 ? 2 : fmt == RC_FMT_U8 ? 8 : 4;
-                    const FrontShape fs = front_shape(fmt, 0);
-                    snprintf(buf, buflen, "k_step<%s,V=%d%s,code,POL=%d> grid=%lld block=64 + k_code_to_dense_front<%s,%s,F=%d,%s> xcd grid=%lld block=256", cube, p.v,
-                             states ? ",move,store" : "", p.pol, (long long)((n + 256 * p.v - 1) / (256 * p.v)), cube, names[fmt], fs.f, fs.lds ? "lds" : "gather",
-                             (long long)(((n + cpp - 1) / cpp + 8 * fs.f - 1) / (8 * fs.f) * 8));
-                    return RC_OK;
-                }
-                const int form = (int)dense_form<T>(n, variant, true, fmt);
-                snprintf(buf, buflen, "k_step_dense<%s,%s,%s,TILE=%d> grid=%lld block=%d", cube, names[fmt], states ? "move,store" : "encode",
-                         form, (long long)dense_grid((n + form - 1) / form, fmt), fmt == RC_FMT_F32 ? kDenseThreads<T, float> : kDenseThreads<T, uint8_t>);
-                return RC_OK;
-            }
-            const bool with_code = code || fmt == RC_FMT_CODE;
-            const StepPlan p = plan_step<T>(n, states, states && (outputs & RC_OUT_INPLACE), with_code, outputs & RC_OUT_DONE, outputs & RC_OUT_REWARD, variant);
-            snprintf(buf, buflen, "k_step<%s,V=%d%s%s,POL=%d> grid=%lld block=64", cube, p.v, states ? ",move,store" : "", with_code ? ",code" : "", p.pol,
-                     (long long)((n + 256 * p.v - 1) / (256 * p.v)));
+            const StepPlan p = plan_step<T>(n, states, outputs & RC_OUT_INPLACE, code || fmt == RC_FMT_CODE, outputs & RC_OUT_DONE, outputs & RC_OUT_REWARD, fmt, v,
+                                            outputs & RC_OUT_WORKSPACE ? INT64_MAX : 0);
+            const char *moves = states ? ",move,store" : "";
+            if (p.route == kStepDense)
+                snprintf(buf, buflen, "k_step_dense<%s,%s,%s,TILE=%d> grid=%lld block=%d", cube, name(), states ? "move,store" : "encode", (int)p.dense.form, (long long)p.dense.grid_x, p.dense.block);
+            else if (p.route == kStepThenFront)
+                snprintf(buf, buflen, "k_step<%s,V=%d%s,code,POL=%d> grid=%lld block=%d + k_code_to_dense_front<%s,%s,F=%d,%s> xcd grid=%lld block=%d", cube, p.v, moves,
+                         p.pol, (long long)p.grid, p.block, cube, name(), p.dense.f, fetch(p.dense), (long long)p.dense.grid_x, p.dense.block);
+            else
+                snprintf(buf, buflen, "k_step<%s,V=%d%s%s,POL=%d> grid=%lld block=%d", cube, p.v, moves, p.code ? ",code" : "", p.pol, (long long)p.grid, p.block);
             return RC_OK;
         }
         if (op == RC_OP_CODE_TO_DENSE) {
-            static const char *const names[] = {"", "", "u8", "f16", "f32", "bf16"};
-            if (fmt < RC_FMT_U8 || fmt > RC_FMT_BF16) return fail(RC_EINVAL, "rc_describe_dispatch: dense fmt required%s");
-            const DenseForm form = dense_form<T>(n, variant, false, fmt);
-            if (form == kDenseFront) {
-                const int cpp = fmt == RC_FMT_F32 ? 2 : fmt == RC_FMT_U8 ? 8 : 4;
-                const FrontShape fs = front_shape(fmt, variant);
-                snprintf(buf, buflen, "k_code_to_dense_front<%s,%s,F=%d,%s> cubes_per_pass=%d%s grid=%lld block=256", cube, names[fmt], fs.f, fs.lds ? "lds" : "gather", cpp,
-                         fs.linear ? "" : " xcd", (long long)(fs.linear ? (n + cpp - 1) / cpp : ((n + cpp - 1) / cpp + 8 * fs.f - 1) / (8 * fs.f) * 8));
-            } else if (form == kDenseWide) {
-                const WideGrid w = wide_grid(n, variant);
-                snprintf(buf, buflen, "k_code_to_dense_wide<%s,%s> tiles_per_group=%lld grid=%lld block=%d", cube, names[fmt], (long long)w.per, (long long)w.groups, kWideBlock);
-            } else {
-                snprintf(buf, buflen, "k_code_to_dense<%s,%s,TILE=%d> grid=%lld block=%d", cube, names[fmt], (int)form, (long long)dense_grid((n + (int)form - 1) / (int)form, fmt), fmt == RC_FMT_F32 ? kDenseThreads<T, float> : kDenseThreads<T, uint8_t>);
-            }
+            if (!dense_fmt(fmt)) return fail(RC_EINVAL, "rc_describe_dispatch: dense fmt required%s");
+            const DensePlan p = plan_code_to_dense<T>(n, fmt, v);
+            if (p.form == kDenseFront)
+                snprintf(buf, buflen, "k_code_to_dense_front<%s,%s,F=%d,%s> cubes_per_pass=%d%s grid=%lld block=%d", cube, name(), p.f, fetch(p), p.cpp,
+                         p.linear ? "" : " xcd", (long long)p.grid_x, p.block);
+            else if (p.form == kDenseWide)
+                snprintf(buf, buflen, "k_code_to_dense_wide<%s,%s> tiles_per_group=%lld grid=%lld block=%d", cube, name(), (long long)p.per, (long long)p.grid_x, p.block);
+            else
+                snprintf(buf, buflen, "k_code_to_dense<%s,%s,TILE=%d> grid=%lld block=%d", cube, name(), (int)p.form, (long long)p.grid_x, p.block);
             return RC_OK;
         }
         if (op == RC_OP_FAMILY_TO_DENSE) {
-            static const char *const names[] = {"", "", "u8", "f16", "f32", "bf16"};
-            if (T::SIZE != 3 || fmt < RC_FMT_U8 || fmt > RC_FMT_BF16) return fail(RC_EINVAL, "rc_describe_dispatch: 3x3x3 and a dense fmt required%s");
+            if (T::SIZE != 3 || !dense_fmt(fmt)) return fail(RC_EINVAL, "rc_describe_dispatch: 3x3x3 and a dense fmt required%s");
             if (depth <= 0) return fail(RC_EINVAL, "rc_describe_dispatch: depth (the number of depths per launch) must be positive%s");
-            const int cpp = fmt == RC_FMT_F32 ? 2 : fmt == RC_FMT_U8 ? 8 : 4, f = fmt == RC_FMT_U8 ? 2 : 1;   // launch_family_to_dense's shapes
-            const int64_t ppb = (n + cpp - 1) / cpp;
-            snprintf(buf, buflen, "k_code_to_dense_front<%s,%s,F=%d,%s,family> depths=%d cubes_per_pass=%d xcd grid=%lldx%d block=256", cube, names[fmt], f,
-                     fmt == RC_FMT_F32 ? "gather" : "lds", depth, cpp, (long long)((ppb + 8 * f - 1) / (8 * f) * 8), (T::A + 1) * depth);
+            const DensePlan p = plan_family_to_dense<T>(n, fmt, depth);
+            snprintf(buf, buflen, "k_code_to_dense_front<%s,%s,F=%d,%s,family> depths=%d cubes_per_pass=%d xcd grid=%lldx%lld block=%d", cube, name(), p.f, fetch(p),
+                     depth, p.cpp, (long long)p.grid_x, (long long)p.grid_y, p.block);
             return RC_OK;
         }
         if (op == RC_OP_EXPAND) {
-            const Geometry geo = pick_geometry(n, T::A, variant, states, n * T::S * T::A);
-            if (const int64_t grid = expand_stream_grid(n * T::S * T::A, states, code, variant)) {
-                const int64_t groups = (n + 511) / 512;
-                snprintf(buf, buflen, "k_expand_stream<%s> grid=%lld block=64", cube, (long long)(grid < groups ? grid : groups));
-                return RC_OK;
-            }
-            snprintf(buf, buflen, "k_expand<%s,V=%d%s> parts=%d grid=%lld block=64", cube, geo.v, code ? ",code" : "", geo.parts,
-                     (long long)((n + 256 * geo.v - 1) / (256 * geo.v) * geo.parts));
+            const ExpandPlan p = plan_expand<T>(n, states, code, v);
+            if (p.stream) snprintf(buf, buflen, "k_expand_stream<%s> grid=%lld block=%d", cube, (long long)p.grid, p.block);
+            else snprintf(buf, buflen, "k_expand<%s,V=%d%s> parts=%d grid=%lld block=%d", cube, p.v, p.code ? ",code" : "", p.parts, (long long)p.grid, p.block);
             return RC_OK;
         }
-        if (op == RC_OP_ADI) {
-            if (depth <= 0) return fail(RC_EINVAL, "rc_describe_dispatch: depth must be positive%s");
-            const bool family = outputs & RC_OUT_FAMILY;
-            Geometry geo = pick_geometry_adi(n, T::A, variant, states, n * depth * T::S * T::A, code || family, family);
-            const bool any_child = states || code || (outputs & RC_OUT_FLAGS);
-            if (!any_child && (variant / 1000) % 100 == 0) geo.parts = 1;
-            AdiArgs a{};
-            a.depth = depth;
-            const int fsegs = (variant / 1000000) % 100;
-            fill_segments(a, fsegs ? fsegs : geo.segs, code || family ? kReplayCostCodes : kReplayCostStickers);
-            snprintf(buf, buflen, "k_adi<%s,V=%d%s> parts=%d segs=%d grid=%lld block=64", cube, geo.v, family ? ",code,family" : code ? ",code" : "", geo.parts, a.segs,
-                     (long long)((n + 256 * geo.v - 1) / (256 * geo.v) * geo.parts * a.segs));
-            return RC_OK;
-        }
-        return fail(RC_EINVAL, "rc_describe_dispatch: unknown op%s");
+        if (depth <= 0) return fail(RC_EINVAL, "rc_describe_dispatch: depth must be positive%s");
+        const AdiPlan p = plan_adi<T>(n, depth, states, code || family, family, states || code || (outputs & RC_OUT_FLAGS), v);
+        snprintf(buf, buflen, "k_adi<%s,V=%d%s> parts=%d segs=%d grid=%lld block=%d", cube, p.v, p.family ? ",code,family" : p.code ? ",code" : "", p.parts, p.segs,
+                 (long long)p.grid, p.block);
+        return RC_OK;
     });
 }
 
@@ -2442,7 +2437,7 @@ __global__ void __launch_bounds__(kWave) k_from_cubies(FromCubieArgs a) {
 // Pack width: 8 cubes per lane from 2^18 cubes on the 2x2x2, as the step kernel; 4 always on the 3x3x3, where 8 cubes' 54 sticker rows,
 // 20 cubie bytes, pieces and orientations do not fit 256 VGPRs (the V = 2 build of the index form spilled 48..136 bytes per lane).
 template <class T>
-int cubies_v(int64_t n) { return T::SIZE == 2 ? pick_v(n, 0) : 1; }
+int cubies_v(int64_t n) { return T::SIZE == 2 ? pick_v(n, Variant{}) : 1; }
 
 template <class T, int V, bool INDEX>
 int launch_cubies(const CubieArgs &a, hipStream_t st, bool stream_rows) {
@@ -2503,7 +2498,7 @@ int rcc_from_cubies(const uint8_t *cubies, int64_t n, int64_t cubie_pitch, int c
     const FromCubieArgs a{cubies, n, cubie_pitch, sh_c, stp, pitch, sh, badp};
     return by_size(cube_size, [&](auto t) {
         using T = decltype(t);
-        const int v = pick_v(n, 0);
+        const int v = pick_v(n, Variant{});
         const int64_t blocks = (n + kWave * 4 * v - 1) / (kWave * 4 * v);
         RC_GRID(blocks);
         if (v == 2) hipLaunchKernelGGL((k_from_cubies<T, 2>), dim3((unsigned)blocks), dim3(kWave), 0, S(stream), a);

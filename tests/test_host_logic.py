@@ -200,6 +200,27 @@ def test_dispatch_description_and_enodev_without_gpu():
         assert lib.rc_read_status(ctypes.byref(out), None) == -3
 
 
+def test_dispatch_fixture_replays():
+    """Every query of tests/golden/dispatch.txt (make_dispatch.py: all sizes x formats x output sets at variant 0, every variant
+    field value at two sizes, refused values) answers with the WHOLE recorded string, or is refused with the recorded return code:
+    a change of a launch plan that is not also a change of the fixture fails here, without a GPU."""
+    from rubiks_cube_solver_amd import _lib as L
+    fn, buf = L.lib().rc_describe_dispatch, ctypes.create_string_buffer(160)
+    lines = open(os.path.join(ROOT, "tests", "golden", "dispatch.txt")).read().splitlines()
+    assert len(lines) > 2000
+    ops_seen, wrong = set(), []
+    for line in lines:
+        query, want = line.split("\t")
+        q = [int(x) for x in query.split()]
+        rc = fn(*q, buf, len(buf))
+        got = buf.value.decode() if rc == 0 else f"!{rc}"
+        ops_seen.add((q[0], want[0] == "!"))
+        if got != want:
+            wrong.append((query, want, got))
+    assert not wrong, (len(wrong), wrong[:5])
+    assert ops_seen >= {(op, refused) for op in range(1, 6) for refused in (False, True)}
+
+
 def test_no_cpu_fallback_without_gpu():
     """Compute entry points refuse host tensors / a missing device instead of falling back."""
     from rubiks_cube_solver_amd import _lib, ops
