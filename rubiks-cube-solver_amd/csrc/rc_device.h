@@ -150,6 +150,68 @@ __device__ __forceinline__ void bst(__amdgpu_buffer_rsrc_t r, uint32_t lo, uint3
     else { const u32x4 u = {p.d[0], p.d[1], p.d[2], p.d[3]}; __builtin_amdgcn_raw_buffer_store_b128(u, r, lo, so, AUX); }
 }
 
+// Tiled structure-of-arrays addressing (include/rubikhip.h "State layout"; the host's rule is rc_host.h tile_shift): cube n of a
+// buffer with `rows` rows lives in tile n / pitch; tiles follow each other, [tile][row][pitch].  `shift` = log2(pitch) when the
+// buffer has several tiles, 63 when it has one (then tile = 0 and any pitch % 16 == 0 works).  Both give the byte offset of a
+// cube's row 0:
+//   tile_off  g0 is a WAVE-UNIFORM cube index and a multiple of the wave's span (<= 512 cubes: 8 per lane at most), the lanes add
+//             their own 32-bit offset: a wave never straddles tiles (a multi-tile pitch is a multiple of 512).  Any shift.
+//   tiled     any cube index b, one address per cube (gathers); the buffer is tiled, pitch = 1 << shift.
+__device__ __forceinline__ int64_t tile_off(int64_t g0, int64_t pitch, int shift, int rows) {
+    return g0 + (g0 >> shift) * (rows - 1) * pitch;
+}
+__device__ __forceinline__ int64_t tiled(int64_t b, int64_t pitch, int shift, int rows) {
+    return (b >> shift) * rows * pitch + (b & (pitch - 1));
+}
+
+// Row-traffic policy of a launch (the aux bits above; the host picks by the working set: rc_host.h mall_policy, rubikhip.hip pick_policy):
+//   POL 0  everything default-cached: the launch's working set fits the 256 MiB Infinity Cache;
+//   POL 1  inputs streamed (nt), outputs written through but kept (sc0 sc1): the next launch reads what this one
+//          wrote and the output alone still fits the Infinity Cache (state ping-pong of 2^22 cubes);
+//   POL 2  inputs streamed, outputs streamed (sc0 sc1 nt): beyond that;
+//   POL 3  state rows default-cached, side outputs streamed: the STATE fits the Infinity Cache but state + code + reward
+//          would not (in-place steps of 2^22 cubes with the fused code, ping-pong of 2^21).
+// SIDE = the outputs nobody re-reads in the next launch (compact code, done, reward): under POL 1 they are streamed past
+// the Infinity Cache so that they do not push the kept state rows out of it (226 MB of state + 84 MB of code would not fit).
+#ifndef RC_SIDE_AUX_POL1
+#define RC_SIDE_AUX_POL1 kAuxStreamStore
+#endif
+template <int POL> struct RowPolicy;
+template <> struct RowPolicy<0> { static constexpr int LD = kAuxCached, ST = kAuxCached, SIDE = kAuxCached; };
+template <> struct RowPolicy<1> { static constexpr int LD = kAuxStreamLoad, ST = kAuxKeepStore, SIDE = RC_SIDE_AUX_POL1; };
+template <> struct RowPolicy<2> { static constexpr int LD = kAuxStreamLoad, ST = kAuxStreamStore, SIDE = kAuxStreamStore; };
+template <> struct RowPolicy<3> { static constexpr int LD = kAuxCached, ST = kAuxCached, SIDE = kAuxStreamStore; };
+// POL 4 (rc_apply_moves_ws beyond the Infinity Cache): state rows streamed both ways, the side outputs -- the compact code the front
+// writer reads back in the very next launch -- written through and KEPT.  Streamed past the cache instead, the code comes back from
+// HBM with a miss latency per front workgroup: the two-launch route drops from 0.89 to 0.52 of peak at 2^21 cubes.
+template <> struct RowPolicy<4> { static constexpr int LD = kAuxStreamLoad, ST = kAuxStreamStore, SIDE = kAuxKeepStore; };
+
+// the N rows of a lane's pack (S sticker rows, SLOTS code rows), rs bytes apart, through one descriptor.  (store_rows and move_rows
+// below serve the kernels whose instruction stream they leave as it is: k_advance, k_episode_end.  The step, expansion, ADI,
+// scramble and cubie kernels keep their own loops: there the compiler orders the flag and code arithmetic by where the rows were
+// last written, and a helper in between changed registers or instruction counts -- tools/kernel_usage.py shows it.)
+template <int AUX, int V, int N>
+__device__ __forceinline__ void store_rows(__amdgpu_buffer_rsrc_t r, uint32_t lo, uint32_t rs, const Pk<V> (&s)[N]) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) bst<V, AUX>(r, lo, i * rs, s[i]);
+}
+// sticker row i of the solved cube: the colour of its face in every byte (py333.py:211-218)
+template <class T, int V>
+__device__ __forceinline__ Pk<V> solved_row(int i) { return splat<V>((uint32_t)(i / T::FACE) * 0x01010101u); }
+
+// The ragged last pack of a batch: 0xff in the bytes of dword k of a pack whose cubes exist (r = n - n0 > 0: cubes of the pack
+// inside the batch).  any_bad below has the same mask in 32-bit arithmetic for r < 4 * V.
+__device__ __forceinline__ uint32_t pack_valid(int64_t r, int k) {
+    const int64_t rk = r - 4 * k;
+    return rk >= 4 ? 0xffffffffu : rk <= 0 ? 0u : ((1u << (8 * (int)rk)) - 1u);
+}
+// a whole pack of one row, or (the ragged last pack, keep = pack_valid) only the bytes of the cubes that exist: pad columns keep theirs
+template <int V, int AUX>
+__device__ __forceinline__ void store_row(__amdgpu_buffer_rsrc_t r, uint32_t lo, uint32_t so, Pk<V> v, bool full, Pk<V> keep) {
+    if (full) bst<V, AUX>(r, lo, so, v);
+    else bst<V, kAuxCached>(r, lo, so, sel(keep, v, bld<V, kAuxCached>(r, lo, so)));
+}
+
 // ---------------------------------------------------------------------- action masks
 // m[a] selects (per byte) the cubes whose action is a.  Only the bits a sticker can use
 // (0..2) are guaranteed: mask bytes are 0x07 (a < 8) or 0xff (a >= 8); a stray 0x80 can show
@@ -206,6 +268,16 @@ __device__ __forceinline__ void apply_move(const Pk<V> (&in)[T::S], const Pk<V> 
         });
         out[i] = o;
     });
+}
+// One step of a pack: the masks of `act`, the move, the result back in s.  Returns action_masks' bad-action pack.
+template <class T, int V>
+__device__ __forceinline__ Pk<V> move_rows(Pk<V> (&s)[T::S], Pk<V> act) {
+    Pk<V> m[T::A], o[T::S];
+    const Pk<V> bad = action_masks<T, V>(act, m);
+    apply_move<T, V>(s, m, o);
+#pragma unroll
+    for (int i = 0; i < T::S; ++i) s[i] = o[i];
+    return bad;
 }
 
 // The same move IN PLACE, orbit by orbit: corner stickers only ever receive corner stickers and edge stickers edge stickers
@@ -325,7 +397,7 @@ __device__ __forceinline__ void child_flags_prepare(const Pk<V> (&s)[T::S], Chil
             Pk<V> acc = splat<V>(0);
             sfor<T::S>([&](auto jc) {
                 constexpr int j = decltype(jc)::value;
-                if constexpr (kRing<T>.sig[j] == c) acc = acc | (s[j] ^ splat<V>((uint32_t)(j / T::FACE) * 0x01010101u));
+                if constexpr (kRing<T>.sig[j] == c) acc = acc | (s[j] ^ solved_row<T, V>(j));
             });
             cls[c] = acc;
         }
@@ -926,7 +998,7 @@ __device__ __forceinline__ void cubies_of(Pk<V> (&s)[T::S], Cubies<T, V> &c) {
     Pk<V> fixed = splat<V>(0), none = splat<V>(0);
     sfor<T::NFIX>([&](auto fc) {
         constexpr int i = T::fixed[decltype(fc)::value];
-        fixed = fixed | (s[i] ^ splat<V>((uint32_t)(i / T::FACE) * 0x01010101u));
+        fixed = fixed | (s[i] ^ solved_row<T, V>(i));
     });
     sfor<T::NC>([&](auto qc) {
         constexpr int q = decltype(qc)::value;
@@ -1023,7 +1095,7 @@ __device__ __forceinline__ Pk<V> stickers_of(const Pk<V> (&code)[T::SLOTS], Pk<V
     const Pk<V> bad = signmask(bad7);
     sfor<T::S>([&](auto ic) {
         constexpr int i = decltype(ic)::value;
-        s[i] = splat<V>((uint32_t)(i / T::FACE) * 0x01010101u);
+        s[i] = solved_row<T, V>(i);
     });
     sfor<T::SLOTS>([&](auto qc) {
         constexpr int q = decltype(qc)::value;

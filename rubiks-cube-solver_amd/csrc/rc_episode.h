@@ -1,5 +1,5 @@
 // rc_episode.h -- episode bookkeeping and the masked re-scramble (include/rubikepisode.h), the last part of rubikhip.hip's
-// translation unit: it uses that file's helpers (tile_off, fail, tile_shift, by_size, ...) and rc_device.h, and adds the rcx_*
+// translation unit: it uses that file's helpers (need_init, kWave, ...), rc_host.h and rc_device.h, and adds the rcx_*
 // entry points to librubikhip.so.
 //
 //   k_episode_end     the launch after a step: counters of every cube, then solved + scramble for the cubes whose episode ended.
@@ -94,20 +94,15 @@ __global__ void __launch_bounds__(kWave) k_episode_end(EpisodeArgs a) {
     Pk<V> em;                                                 // 0xff in the bytes of the ended cubes
     em.d[0] = ((end_b | (end_b >> 1)) & 0x01010101u) * 0xffu;
 #pragma unroll
-    for (int i = 0; i < T::S; ++i) s[i] = sel(em, splat<V>((uint32_t)(i / T::FACE) * 0x01010101u), s[i]);
+    for (int i = 0; i < T::S; ++i) s[i] = sel(em, solved_row<T, V>(i), s[i]);
     for (int d = 0; d < kmax; ++d) {
-        uint32_t x = 0;                                       // the no-op A for cubes that did not end or are past their own depth
+        Pk<V> act;                                            // the no-op A for cubes that did not end or are past their own depth
+        act.d[0] = 0;
 #pragma unroll
-        for (int j = 0; j < 4; ++j) x |= (d < kd[j] ? rng[j].action(T::A) : (uint32_t)T::A) << (8 * j);
-        Pk<V> act, m[T::A], o[T::S];
-        act.d[0] = x;
-        action_masks<T, V>(act, m);
-        apply_move<T, V>(s, m, o);
-#pragma unroll
-        for (int i = 0; i < T::S; ++i) s[i] = o[i];
+        for (int j = 0; j < 4; ++j) act.d[0] |= (d < kd[j] ? rng[j].action(T::A) : (uint32_t)T::A) << (8 * j);
+        (void)move_rows<T, V>(s, act);                        // actions are 0..A by construction
     }
-#pragma unroll
-    for (int i = 0; i < T::S; ++i) bst<V, kAuxCached>(rows, lo, i * rs, s[i]);
+    store_rows<kAuxCached>(rows, lo, rs, s);
 }
 
 }  // namespace
@@ -141,7 +136,7 @@ int rcx_episode_end(uint8_t *stp, int64_t n, int64_t pitch, int cube_size, const
         const int64_t blocks = (n + kWave * 4 - 1) / (kWave * 4);
         RC_GRID(blocks);
         hipLaunchKernelGGL((k_episode_end<T>), dim3((unsigned)blocks), dim3(kWave), 0, S(stream), a);
-        RC_HIP(hipGetLastError());
+        RC_HIP(RC_EHIP, hipGetLastError());
         return RC_OK;
     });
 }

@@ -13,6 +13,7 @@
 #include <cstdio>
 
 #include "../../include/rubiknet.h"
+#include "rc_host.h"
 
 namespace {
 
@@ -167,22 +168,8 @@ __global__ void __launch_bounds__(kThreads) k_first_layer(Args a) {
 }
 
 // ------------------------------------------------------------------------------------------------- host side
-thread_local char t_err[256] = "";
-
-int fail(const char *msg) {
-    snprintf(t_err, sizeof t_err, "%s", msg);
-    return -1;
-}
-#define RCN_HIP(call)                                                                               \
-    do {                                                                                            \
-        const hipError_t e_ = (call);                                                               \
-        if (e_ != hipSuccess) {                                                                     \
-            snprintf(t_err, sizeof t_err, "%s: %s", #call, hipGetErrorString(e_));                   \
-            return -2;                                                                              \
-        }                                                                                           \
-    } while (0)
-
-inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+// -1: bad argument, -2: a HIP call failed (include/rubiknet.h)
+inline int fail(const char *msg) { return fail(-1, "%s", msg); }
 
 constexpr int kTargetBlocks = 256;               // one workgroup per CU of an MI355X at 3x3x3
 
@@ -196,8 +183,8 @@ int launch(Args a, void *stream) {
     if (ranges > 65535) ranges = 65535;
     a.passes_per_block = (a.passes + ranges - 1) / ranges;
     ranges = (a.passes + a.passes_per_block - 1) / a.passes_per_block;
-    hipLaunchKernelGGL((k_first_layer<T, W, O>), dim3((unsigned)slabs, (unsigned)ranges), dim3(kThreads), 0, static_cast<hipStream_t>(stream), a);
-    RCN_HIP(hipGetLastError());
+    hipLaunchKernelGGL((k_first_layer<T, W, O>), dim3((unsigned)slabs, (unsigned)ranges), dim3(kThreads), 0, S(stream), a);
+    RC_HIP(-2, hipGetLastError());
     return 0;
 }
 
@@ -209,14 +196,7 @@ int by_format(const Args &a, int wfmt, int ofmt, void *stream) {
 
 }  // namespace
 
-// the hash of the sources this binary was compiled from (__graft_entry__.build passes -DRC_SRC_HASH=<16 hex digits>)
-#ifndef RC_SRC_HASH
-#define RC_SRC_HASH unhashed
-#endif
-#define RCN_STR2(x) #x
-#define RCN_STR(x) RCN_STR2(x)
-static const char k_build_id[] = "rc-build-id:" RCN_STR(RC_SRC_HASH);
-const char *rc_net_build_id(void) { return k_build_id + 12; }
+RC_BUILD_ID(rc_net_build_id)
 
 const char *rc_net_last_error(void) { return t_err; }
 
@@ -234,14 +214,9 @@ int rc_net_first_layer(const uint8_t *code, int64_t n, int64_t code_pitch, int c
     if (!aligned16(code) || !aligned16(wt) || !aligned16(bias) || !aligned16(out) || (out_stride * osz) % 16 != 0)
         return fail("rc_net_first_layer: code, wt, bias, out and every row of out must be 16-byte aligned");
     const int slots = cube_size == 3 ? 20 : 7;
-    if (code_pitch <= 0 || (code_pitch & 15) != 0 || code_pitch * slots >= ((int64_t)1 << 32))
-        return fail("rc_net_first_layer: code_pitch must be a positive multiple of 16 with SLOTS * code_pitch < 2^32");
-    int shift = 63;
-    if (n > code_pitch) {
-        if (code_pitch < 512 || (code_pitch & (code_pitch - 1)) != 0) return fail("rc_net_first_layer: several tiles need a power-of-two code_pitch >= 512");
-        shift = 0;
-        while (((int64_t)1 << shift) < code_pitch) ++shift;
-    }
+    const int shift = tile_shift(code_pitch, n, slots);
+    if (shift == -1) return fail("rc_net_first_layer: code_pitch must be a positive multiple of 16 with SLOTS * code_pitch < 2^32");
+    if (shift < 0) return fail("rc_net_first_layer: several tiles need a power-of-two code_pitch >= 512");
     if (n == 0) return 0;
     Args a{code, wt, bias, out, n, code_pitch, out_stride, (n + kPass - 1) / kPass, 0, shift, hidden, act};
     return cube_size == 3 ? by_format<Net3>(a, wfmt, ofmt, stream) : by_format<Net2>(a, wfmt, ofmt, stream);

@@ -24,6 +24,7 @@
 
 #include "../../include/rubiksearch.h"
 #include "rc_device.h"
+#include "rc_host.h"
 
 using namespace rc;
 
@@ -41,11 +42,6 @@ struct Key {
     static constexpr int KW = (N + 15) / 16;
     static constexpr int sticker(int k) { return T::SIZE == 3 ? (k / 8) * 9 + (k % 8 < 4 ? k % 8 : k % 8 + 1) : k; }
 };
-
-// byte offset of cube b's row 0 in a [tiles][rows][pitch] buffer (pitch = 1 << shift)
-__device__ __forceinline__ int64_t tiled(int64_t b, int64_t pitch, int shift, int rows) {
-    return (b >> shift) * rows * pitch + (b & (pitch - 1));
-}
 
 // ------------------------------------------------------------------------------------- workgroup helpers
 // One word per wave of a 256-thread workgroup: the scratch of block_reduce and ordered_compact, one array per word type.  Both
@@ -243,9 +239,7 @@ __global__ void __launch_bounds__(kWave) k_expand(ExpandArgs a) {
         *reinterpret_cast<uint32_t *>(a.flags + j0 + lo) = (live & ~undo) | (solved << 1);
         Pk<1> cc[T::SLOTS];
         encode<T, 1>(c, cc);                                   // the child's own look-ups: exact for any colouring
-        const __amdgpu_buffer_rsrc_t r = make_srd(a.code + ((int64_t)A_ * a.nbp + tile * a.pitch) * T::SLOTS + col);
-#pragma unroll
-        for (int p = 0; p < T::SLOTS; ++p) bst<1, kAuxCached>(r, lo, p * rs, cc[p]);
+        store_rows<kAuxCached>(make_srd(a.code + ((int64_t)A_ * a.nbp + tile * a.pitch) * T::SLOTS + col), lo, rs, cc);
         uint64_t *kp = a.keys + j0 + lo;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
@@ -473,15 +467,10 @@ __global__ void __launch_bounds__(kWave) k_advance(AdvanceArgs a) {
         for (int q = 0; q < 4; ++q) v |= (uint32_t)a.in[tiled(src[q], a.pitch, a.shift, T::S) + (int64_t)i * a.pitch] << (8 * q);
         s[i].d[0] = v;
     }
-    Pk<1> m[T::A];
     Pk<1> ap;
     ap.d[0] = act;
-    (void)action_masks<T, 1>(ap, m);                           // actions are 0..A by construction
-    Pk<1> o[T::S];
-    apply_move<T, 1>(s, m, o);
-    const __amdgpu_buffer_rsrc_t r = make_srd(a.out + tiled(g0, a.pitch, a.shift, T::S));
-#pragma unroll
-    for (int i = 0; i < T::S; ++i) bst<1, kAuxCached>(r, lo, i * (uint32_t)a.pitch, o[i]);
+    (void)move_rows<T, 1>(s, ap);                              // actions are 0..A by construction
+    store_rows<kAuxCached>(make_srd(a.out + tiled(g0, a.pitch, a.shift, T::S)), lo, (uint32_t)a.pitch, s);
 }
 
 // --------------------------------------------------------------------------------------------- backtrack
@@ -504,43 +493,9 @@ __global__ void __launch_bounds__(256) k_backtrack(const uint16_t *hp, const uin
 }
 
 // ------------------------------------------------------------------------------------------------- host side
-thread_local char t_err[256] = "";
-
-int fail(const char *msg) {
-    snprintf(t_err, sizeof t_err, "%s", msg);
-    return -1;
-}
-int fail(const char *fn, const char *msg) {
-    snprintf(t_err, sizeof t_err, "%s: %s", fn, msg);
-    return -1;
-}
-#define RCS_HIP(call)                                                                               \
-    do {                                                                                            \
-        const hipError_t e_ = (call);                                                               \
-        if (e_ != hipSuccess) {                                                                     \
-            snprintf(t_err, sizeof t_err, "%s: %s", #call, hipGetErrorString(e_));                   \
-            return -2;                                                                              \
-        }                                                                                           \
-    } while (0)
-
-inline hipStream_t S(void *s) { return static_cast<hipStream_t>(s); }
-inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-template <class... P>
-bool any_null(P... p) { return (... || (p == nullptr)); }
-template <class... P>
-bool all_aligned16(P... p) { return (... && aligned16(p)); }
-inline int log2_exact(int64_t v) {
-    int s = 0;
-    while (((int64_t)1 << s) < v) ++s;
-    return s;
-}
-
-template <class F>
-int by_size(int cube_size, F &&f) {
-    if (cube_size == 3) return f(Cube3{});
-    if (cube_size == 2) return f(Cube2{});
-    return fail("cube_size must be 2 or 3");
-}
+// -1: bad argument, -2: a HIP call failed (include/rubiksearch.h)
+inline int fail(const char *msg) { return fail(-1, "%s", msg); }
+inline int fail(const char *fn, const char *msg) { return fail(-1, "%s: %s", fn, msg); }
 
 struct Geo {
     int64_t nb, nbp;
@@ -550,23 +505,19 @@ struct Geo {
 template <class T>
 int geometry(int64_t n_problems, int width, int64_t pitch, Geo &g) {
     if (n_problems < 1 || width < 1 || width > 65536) return fail("need n_problems >= 1 and 1 <= width <= 65536");
-    if (pitch < 512 || (pitch & (pitch - 1)) != 0 || pitch * T::S >= ((int64_t)1 << 32)) return fail("pitch must be a power of two >= 512 with S * pitch < 2^32");
+    if ((g.shift = tile_shift(pitch, INT64_MAX, T::S)) < 0) return fail("pitch must be a power of two >= 512 with S * pitch < 2^32");   // tiled even where one tile would do
     g.nb = n_problems * width;
-    g.nbp = (g.nb + pitch - 1) / pitch * pitch;
-    g.shift = log2_exact(pitch);
+    g.nbp = ceil_div(g.nb, pitch) * pitch;
     if ((int64_t)T::A * g.nbp / 256 > 0x7fffffff) return fail("too many candidates for one launch");
     return 0;
 }
 
 // Where fn's roots lie: one tile (root_pitch >= n, root_pitch % 16 == 0: rshift 63) or power-of-two tiles of root_pitch = 1 << rshift
 template <class T>
-int root_layout(const char *fn, int64_t n, int64_t root_pitch, int &rshift) {
-    rshift = 63;
-    if (root_pitch <= 0 || (root_pitch & 15) != 0 || root_pitch * T::S >= ((int64_t)1 << 32)) return fail(fn, "bad root_pitch");
-    if (n > root_pitch) {
-        if (root_pitch < 512 || (root_pitch & (root_pitch - 1)) != 0) return fail(fn, "several root tiles need a power-of-two pitch >= 512");
-        rshift = log2_exact(root_pitch);
-    }
+int root_shift(const char *fn, int64_t n, int64_t root_pitch, int &rshift) {
+    rshift = tile_shift(root_pitch, n, T::S);
+    if (rshift == -1) return fail(fn, "bad root_pitch");
+    if (rshift < 0) return fail(fn, "several root tiles need a power-of-two pitch >= 512");
     return 0;
 }
 
@@ -580,14 +531,7 @@ int64_t table_slots(int A, int64_t n_problems, int width) { return pow2_slots(2 
 
 }  // namespace
 
-// the hash of the sources this binary was compiled from (__graft_entry__.build passes -DRC_SRC_HASH=<16 hex digits>)
-#ifndef RC_SRC_HASH
-#define RC_SRC_HASH unhashed
-#endif
-#define RCS_STR2(x) #x
-#define RCS_STR(x) RCS_STR2(x)
-static const char k_build_id[] = "rc-build-id:" RCS_STR(RC_SRC_HASH);
-const char *rc_search_build_id(void) { return k_build_id + 12; }
+RC_BUILD_ID(rc_search_build_id)
 
 const char *rc_search_last_error(void) { return t_err; }
 
@@ -604,10 +548,10 @@ int rc_search_init(const uint8_t *roots, int64_t n, int64_t root_pitch, int cube
         if (int rc = geometry<T>(n, width, pitch, g)) return rc;
         if (any_null(roots, beam, last_action, live, active, length, solution)) return fail("rc_search_init: null buffer");
         int rshift;
-        if (int rc = root_layout<T>("rc_search_init", n, root_pitch, rshift)) return rc;
+        if (int rc = root_shift<T>("rc_search_init", n, root_pitch, rshift)) return rc;
         hipLaunchKernelGGL((k_init<T>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, S(stream), roots, n, root_pitch, rshift, beam, pitch,
                            g.shift, width, last_action, live, active, length, solution);
-        RCS_HIP(hipGetLastError());
+        RC_HIP(-2, hipGetLastError());
         return 0;
     });
 }
@@ -622,7 +566,7 @@ int rc_search_expand(const uint8_t *beam, int64_t n, int width, int64_t pitch, i
         if (!all_aligned16(beam, last_action, code, flags, keys)) return fail("rc_search_expand: buffers must be 16-byte aligned");
         const ExpandArgs a{beam, last_action, live, active, code, flags, keys, g.nb, g.nbp, pitch, width, g.shift};
         hipLaunchKernelGGL((k_expand<T>), dim3((unsigned)(g.nbp / kSpan)), dim3(kWave), 0, S(stream), a);
-        RCS_HIP(hipGetLastError());
+        RC_HIP(-2, hipGetLastError());
         return 0;
     });
 }
@@ -643,11 +587,11 @@ int rc_search_select(uint8_t *flags, const uint64_t *keys, const float *scores, 
         const Cands c{flags, keys, scores, live, active, length, solution, static_cast<unsigned long long *>(workspace), (uint64_t)(slots - 1),
                       g.nbp, width};
         const SelectArgs a{c, depth, sel_parent, sel_action, sel_count};
-        RCS_HIP(hipMemsetAsync(workspace, 0xFF, (size_t)slots * 8, S(stream)));       // every slot kEmpty
+        RC_HIP(-2, hipMemsetAsync(workspace, 0xFF, (size_t)slots * 8, S(stream)));       // every slot kEmpty
         hipLaunchKernelGGL((k_insert<T>), dim3((unsigned)((T::A * g.nbp + 255) / 256)), dim3(256), 0, S(stream), c);
-        RCS_HIP(hipGetLastError());
+        RC_HIP(-2, hipGetLastError());
         hipLaunchKernelGGL((k_select<T>), dim3((unsigned)n), dim3(kSelThreads), 0, S(stream), a);
-        RCS_HIP(hipGetLastError());
+        RC_HIP(-2, hipGetLastError());
         return 0;
     });
 }
@@ -668,7 +612,7 @@ int rc_search_advance(const uint8_t *beam_in, uint8_t *beam_out, int64_t n, int 
         const AdvanceArgs a{beam_in, beam_out, sel_parent, sel_action, sel_count, live, last_action, hist_parent, hist_action, depth,
                             g.nb, g.nbp, pitch, width, g.shift, max_depth};
         hipLaunchKernelGGL((k_advance<T>), dim3((unsigned)(g.nbp / kSpan)), dim3(kWave), 0, S(stream), a);
-        RCS_HIP(hipGetLastError());
+        RC_HIP(-2, hipGetLastError());
         return 0;
     });
 }
@@ -683,7 +627,7 @@ int rc_search_backtrack(const uint16_t *hist_parent, const uint8_t *hist_action,
         if (max_depth < 1) return fail("rc_search_backtrack: max_depth must be >= 1");
         hipLaunchKernelGGL(k_backtrack, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, S(stream), hist_parent, hist_action, n, width, g.nbp,
                            T::A, max_depth, length, solution, actions);
-        RCS_HIP(hipGetLastError());
+        RC_HIP(-2, hipGetLastError());
         return 0;
     });
 }
@@ -966,9 +910,7 @@ struct PoolGeo {
 template <class T>
 int pool_geometry(int64_t n, int64_t capacity, int64_t pool_pitch, PoolGeo &g) {
     if (!pool_limits(n, capacity)) return fail(kPoolLimits);
-    if (pool_pitch < 512 || (pool_pitch & (pool_pitch - 1)) != 0 || pool_pitch * T::S >= ((int64_t)1 << 32))
-        return fail("pool_pitch must be a power of two >= 512 with S * pool_pitch < 2^32");
-    g.pshift = log2_exact(pool_pitch);
+    if ((g.pshift = tile_shift(pool_pitch, INT64_MAX, T::S)) < 0) return fail("pool_pitch must be a power of two >= 512 with S * pool_pitch < 2^32");
     g.slots = pow2_slots(2 * n * capacity);
     return 0;
 }
@@ -1002,13 +944,13 @@ int rca_init(const uint8_t *roots, int64_t n, int64_t root_pitch, int cube_size,
             return fail("rca_init: buffers must be 16-byte aligned");
         if (table_bytes < pg.slots * 8) return fail("rca_init: table smaller than rca_workspace_bytes()");
         int rshift;
-        if (int rc = root_layout<T>("rca_init", n, root_pitch, rshift)) return rc;
+        if (int rc = root_shift<T>("rca_init", n, root_pitch, rshift)) return rc;
         const Pool o = make_pool(pool_stickers, pool_keys, pool_parent, pool_action, pool_g, pool_score, pool_prio, pool_state, count, overflow,
                                  table, pg, n, capacity, pool_pitch);
-        RCS_HIP(hipMemsetAsync(table, 0xFF, (size_t)pg.slots * 8, S(stream)));           // every slot kEmpty, once per search
+        RC_HIP(-2, hipMemsetAsync(table, 0xFF, (size_t)pg.slots * 8, S(stream)));           // every slot kEmpty, once per search
         hipLaunchKernelGGL((k_astar_init<T>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, S(stream), roots, n, root_pitch, rshift, o, live,
                            active, length, solution, ended);
-        RCS_HIP(hipGetLastError());
+        RC_HIP(-2, hipGetLastError());
         return 0;
     });
 }
@@ -1029,7 +971,7 @@ int rca_pop(int64_t n, int cube_size, int batch, int64_t capacity, int64_t pool_
         const PopArgs a{pool_stickers, pool_action, pool_prio, pool_state, count, pool_pitch, pg.pshift, (int32_t)capacity,
                         iteration, beam, last_action, live, active, ended, pop_node, pitch, g.shift, batch};
         hipLaunchKernelGGL((k_astar_pop<T>), dim3((unsigned)n), dim3(kSelThreads), 0, S(stream), a);
-        RCS_HIP(hipGetLastError());
+        RC_HIP(-2, hipGetLastError());
         return 0;
     });
 }
@@ -1060,11 +1002,11 @@ int rca_merge(int64_t n, int cube_size, int batch, int64_t pitch, int64_t capaci
         const MergeArgs a{s, make_pool(pool_stickers, pool_keys, pool_parent, pool_action, pool_g, pool_score, pool_prio, pool_state, count, overflow,
                                        table, pg, n, capacity, pool_pitch),
                           iteration, pop_node, ended, weight};
-        RCS_HIP(hipMemsetAsync(scratch, 0xFF, (size_t)sslots * 8, S(stream)));
+        RC_HIP(-2, hipMemsetAsync(scratch, 0xFF, (size_t)sslots * 8, S(stream)));
         hipLaunchKernelGGL((k_insert<T>), dim3((unsigned)((T::A * g.nbp + 255) / 256)), dim3(256), 0, S(stream), s);
-        RCS_HIP(hipGetLastError());
+        RC_HIP(-2, hipGetLastError());
         hipLaunchKernelGGL((k_astar_merge<T>), dim3((unsigned)n), dim3(kSelThreads), 0, S(stream), a);
-        RCS_HIP(hipGetLastError());
+        RC_HIP(-2, hipGetLastError());
         return 0;
     });
 }
@@ -1079,7 +1021,7 @@ int rca_backtrack(int64_t n, int cube_size, int64_t capacity, const int32_t *poo
         if (!all_aligned16(pool_parent, pool_action, length, solution, actions)) return fail("rca_backtrack: buffers must be 16-byte aligned");
         hipLaunchKernelGGL(k_astar_backtrack, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, S(stream), pool_parent, pool_action, n,
                            (int32_t)capacity, T::A, max_length, length, solution, actions);
-        RCS_HIP(hipGetLastError());
+        RC_HIP(-2, hipGetLastError());
         return 0;
     });
 }

@@ -1,5 +1,5 @@
 // rc_sym.h -- the cube symmetries on the device (include/rubiksym.h), the last part of rc_search.hip's translation unit: it uses
-// that file's helpers (fail, RCS_HIP, aligned16, by_size, S) and rc_device.h, and adds the rcs_* entry points to librubiksearch.so.
+// that file's fail, rc_host.h and rc_device.h, and adds the rcs_* entry points to librubiksearch.so.
 // The rule (rc_sym_tables.h): image[i] = relabel[s][ state[ perm[s][i] ] ].  DESIGN.md "Symmetries" has the byte and LDS models.
 //
 //   k_sym_uniform   one symmetry for every cube: the image is a ROW permutation of the tile.  One lane = 8 cubes; output row i is
@@ -20,22 +20,10 @@
 namespace {
 
 constexpr int kSymSpan = 512;                    // cubes per workgroup of both kernels = the smallest tile: never straddles tiles
-constexpr int64_t kSymMall = (int64_t)240 << 20; // what rubikhip.hip counts on of the 256 MiB Infinity Cache (pick_policy)
 
 template <class T> struct SymOf;
 template <> struct SymOf<Cube3> { using type = Sym3; };
 template <> struct SymOf<Cube2> { using type = Sym2; };
-
-// row-traffic policy, chosen like the step kernel's (rubikhip.hip RowPolicy 0 / 1 / 2) from the bytes the launch touches
-template <int POL> struct SymPolicy;
-template <> struct SymPolicy<0> { static constexpr int LD = kAuxCached, ST = kAuxCached; };          // in + out fit the Infinity Cache
-template <> struct SymPolicy<1> { static constexpr int LD = kAuxStreamLoad, ST = kAuxKeepStore; };   // the output alone fits: keep it
-template <> struct SymPolicy<2> { static constexpr int LD = kAuxStreamLoad, ST = kAuxStreamStore; }; // beyond that: stream both
-
-// include/rubikhip.h "State layout", as rubikhip.hip's tile_off: g0 is a multiple of the workgroup span, shift = 63 for one tile
-__device__ __forceinline__ int64_t sym_tile_off(int64_t g0, int64_t pitch, int shift, int rows) {
-    return g0 + (g0 >> shift) * (rows - 1) * pitch;
-}
 
 struct SymArgs {
     const uint8_t *in;
@@ -45,12 +33,6 @@ struct SymArgs {
     int64_t n, pitch_in, pitch_out;
     int sh_in, sh_out;
 };
-
-// 0xff in the bytes of the cubes of dword k of a pack that exist (cube index < n); r = n - n0 > 0
-__device__ __forceinline__ uint32_t sym_valid(int64_t r, int k) {
-    const int64_t rk = r - 4 * k;
-    return rk >= 4 ? 0xffffffffu : rk <= 0 ? 0u : ((1u << (8 * (int)rk)) - 1u);
-}
 
 // ------------------------------------------------------------------------------------------ one symmetry for all
 template <class T>
@@ -63,13 +45,13 @@ template <class T, int POL>
 __global__ void __launch_bounds__(kWave) k_sym_uniform(SymArgs a, SymRow<T> row) {
     constexpr int V = 2;
     static_assert(kWave * 4 * V == kSymSpan);
-    using P = SymPolicy<POL>;
+    using P = RowPolicy<POL>;                      // 0 / 1 / 2 by rc_host.h mall_policy
     const int64_t g0 = (int64_t)blockIdx.x * kSymSpan;
     const uint32_t lo = threadIdx.x * (4 * V);
     const int64_t n0 = g0 + lo;
     if (n0 >= a.n) return;
-    const __amdgpu_buffer_rsrc_t rin = make_srd(a.in + sym_tile_off(g0, a.pitch_in, a.sh_in, T::S));
-    const __amdgpu_buffer_rsrc_t rout = make_srd(a.out + sym_tile_off(g0, a.pitch_out, a.sh_out, T::S));
+    const __amdgpu_buffer_rsrc_t rin = make_srd(a.in + tile_off(g0, a.pitch_in, a.sh_in, T::S));
+    const __amdgpu_buffer_rsrc_t rout = make_srd(a.out + tile_off(g0, a.pitch_out, a.sh_out, T::S));
     const uint32_t pi = (uint32_t)a.pitch_in, po = (uint32_t)a.pitch_out;
     if (n0 + 4 * V <= a.n) {
         // every load before the first store, as the step kernel does: a store between two loads would order them (the compiler
@@ -84,7 +66,7 @@ __global__ void __launch_bounds__(kWave) k_sym_uniform(SymArgs a, SymRow<T> row)
         for (int i = 0; i < T::S; ++i) bst<V, P::ST>(rout, lo, i * po, perm<V>(row.rel[1], row.rel[0], img[i]));
     } else {                                                                                 // the ragged last pack: pad columns keep their bytes
         Pk<V> keep;
-        RC_V keep.d[k] = sym_valid(a.n - n0, k);
+        RC_V keep.d[k] = pack_valid(a.n - n0, k);
         sfor<T::S>([&](auto ic) {
             constexpr int i = decltype(ic)::value;
             const uint32_t src = (row.perm[i / 4] >> (8 * (i % 4))) & 0xffu;
@@ -124,7 +106,7 @@ constexpr int kSymThreads = kSymSpan / 4;        // 128: one lane = one pack of 
 template <class T, int MODE, int POL>
 __global__ void __launch_bounds__(kSymThreads) k_sym_cubes(SymArgs a) {
     using Y = typename SymOf<T>::type;
-    using P = SymPolicy<POL>;
+    using P = RowPolicy<POL>;                      // 0 / 1 / 2 by rc_host.h mall_policy
     constexpr int PW = Y::PW, K = Y::K;
     __shared__ uint32_t s_st[T::S * kSymSpan / 4];    // [S][512] sticker bytes: row i of the lane's pack is dword i * 128 + tid
     __shared__ uint32_t s_perm[K * PW];
@@ -136,11 +118,11 @@ __global__ void __launch_bounds__(kSymThreads) k_sym_cubes(SymArgs a) {
     const int64_t g0 = (int64_t)blockIdx.x * kSymSpan, n0 = g0 + lo;
     for (uint32_t t = tid; t < K * PW; t += kSymThreads) s_perm[t] = dev.perm[t];
     for (uint32_t t = tid; t < K * 2; t += kSymThreads) s_rel[t] = dev.rel[t];
-    const uint32_t valid = n0 < a.n ? sym_valid(a.n - n0, 0) : 0u;
+    const uint32_t valid = n0 < a.n ? pack_valid(a.n - n0, 0) : 0u;
     if (valid) {
         // stickers are 0..5: the mask keeps whatever else a buffer holds (pad columns, a caller's garbage) inside the 8-entry
         // look-ups and the packed byte comparisons below
-        const __amdgpu_buffer_rsrc_t rin = make_srd(a.in + sym_tile_off(g0, a.pitch_in, a.sh_in, T::S));
+        const __amdgpu_buffer_rsrc_t rin = make_srd(a.in + tile_off(g0, a.pitch_in, a.sh_in, T::S));
         const uint32_t pi = (uint32_t)a.pitch_in;
 #pragma unroll
         for (int i = 0; i < T::S; ++i) s_st[i * (kSymSpan / 4) + tid] = bld<1, P::LD>(rin, lo, i * pi).d[0] & valid & 0x07070707u;
@@ -205,9 +187,11 @@ __global__ void __launch_bounds__(kSymThreads) k_sym_cubes(SymArgs a) {
         r1[q] = s_rel[2 * sq + 1];
         po4[q] = sq * PW;
     }
-    const __amdgpu_buffer_rsrc_t rout = make_srd(a.out + sym_tile_off(g0, a.pitch_out, a.sh_out, T::S));
+    const __amdgpu_buffer_rsrc_t rout = make_srd(a.out + tile_off(g0, a.pitch_out, a.sh_out, T::S));
     const uint32_t po = (uint32_t)a.pitch_out;
     const bool full = valid == 0xffffffffu;
+    Pk<1> keep;
+    keep.d[0] = valid;
     uint32_t pd[4] = {0, 0, 0, 0};
     sfor<T::S>([&](auto ic) {
         constexpr int i = decltype(ic)::value;
@@ -223,24 +207,11 @@ __global__ void __launch_bounds__(kSymThreads) k_sym_cubes(SymArgs a) {
         for (int q = 0; q < 4; ++q) t[q] = __builtin_amdgcn_perm(r1[q], r0[q], w);
         Pk<1> img;
         img.d[0] = sym_pick(t);
-        if (full) bst<1, P::ST>(rout, lo, i * po, img);
-        else {                                                               // the ragged last pack: pad columns keep their bytes
-            const uint32_t old = bld<1, kAuxCached>(rout, lo, i * po).d[0];
-            img.d[0] = (img.d[0] & valid) | (old & ~valid);
-            bst<1, kAuxCached>(rout, lo, i * po, img);
-        }
+        store_row<1, P::ST>(rout, lo, i * po, img, full, keep);                // the ragged last pack: pad columns keep their bytes
     });
 }
 
 // ------------------------------------------------------------------------------------------------- host side
-// include/rubikhip.h "State layout" (rubikhip.hip tile_shift): the shift for sym_tile_off, or -1 if the pitch is bad
-inline int sym_tile_shift(int64_t pitch, int64_t n, int rows) {
-    if (pitch <= 0 || (pitch & 15) != 0 || pitch * rows >= ((int64_t)1 << 32)) return -1;
-    if (n <= pitch) return 63;
-    if (pitch < 512 || (pitch & (pitch - 1)) != 0) return -1;
-    return log2_exact(pitch);
-}
-
 // bytes from the buffer's start to the end of the last pack a kernel touches (packs of 8 cubes at most; pitch % 16 == 0)
 inline int64_t sym_extent(int64_t n, int64_t pitch, int shift, int rows) {
     const int64_t last = ((n + 7) & ~(int64_t)7) - 1;
@@ -249,10 +220,6 @@ inline int64_t sym_extent(int64_t n, int64_t pitch, int shift, int rows) {
 }
 
 inline bool sym_overlap(const uint8_t *a, int64_t na, const uint8_t *b, int64_t nb) { return a < b + nb && b < a + na; }
-
-inline int sym_policy(int64_t in_bytes, int64_t out_bytes) {
-    return in_bytes + out_bytes <= kSymMall ? 0 : out_bytes <= kSymMall ? 1 : 2;
-}
 
 template <class T>
 int sym_host_tables(uint8_t *perm, uint8_t *relabel, uint8_t *amap, uint8_t *inverse, uint8_t *compose) {
@@ -265,39 +232,34 @@ int sym_host_tables(uint8_t *perm, uint8_t *relabel, uint8_t *amap, uint8_t *inv
     return 0;
 }
 
-int sym_fail(const char *fn, const char *what) {
-    snprintf(t_err, sizeof t_err, "%s: %s", fn, what);
-    return -1;
-}
-
 // the checks rcs_sym_apply and rcs_sym_canonical share; fills the layout fields of `a`
 template <class T>
 int sym_check(const char *fn, SymArgs &a, bool need_out) {
-    if (a.n < 0) return sym_fail(fn, "n_cubes is negative");
-    if (!a.in || !aligned16(a.in)) return sym_fail(fn, "in is NULL or not 16-byte aligned");
-    if ((a.sh_in = sym_tile_shift(a.pitch_in, a.n, T::S)) < 0)
-        return sym_fail(fn, "bad pitch_in: need pitch % 16 == 0 and pitch >= n_cubes, or a power-of-two tile >= 512, and S * pitch < 2^32");
-    if (need_out && !a.out) return sym_fail(fn, "out is NULL");
+    if (a.n < 0) return fail(fn, "n_cubes is negative");
+    if (!a.in || !aligned16(a.in)) return fail(fn, "in is NULL or not 16-byte aligned");
+    if ((a.sh_in = tile_shift(a.pitch_in, a.n, T::S)) < 0)
+        return fail(fn, "bad pitch_in: need pitch % 16 == 0 and pitch >= n_cubes, or a power-of-two tile >= 512, and S * pitch < 2^32");
+    if (need_out && !a.out) return fail(fn, "out is NULL");
     if (!a.out) return 0;
-    if (!aligned16(a.out)) return sym_fail(fn, "out is not 16-byte aligned");
-    if ((a.sh_out = sym_tile_shift(a.pitch_out, a.n, T::S)) < 0)
-        return sym_fail(fn, "bad pitch_out: need pitch % 16 == 0 and pitch >= n_cubes, or a power-of-two tile >= 512, and S * pitch < 2^32");
-    if (a.in == a.out) return sym_fail(fn, "in == out: the image is not computed in place");
+    if (!aligned16(a.out)) return fail(fn, "out is not 16-byte aligned");
+    if ((a.sh_out = tile_shift(a.pitch_out, a.n, T::S)) < 0)
+        return fail(fn, "bad pitch_out: need pitch % 16 == 0 and pitch >= n_cubes, or a power-of-two tile >= 512, and S * pitch < 2^32");
+    if (a.in == a.out) return fail(fn, "in == out: the image is not computed in place");
     if (a.n > 0 && sym_overlap(a.in, sym_extent(a.n, a.pitch_in, a.sh_in, T::S), a.out, sym_extent(a.n, a.pitch_out, a.sh_out, T::S)))
-        return sym_fail(fn, "in and out overlap");
+        return fail(fn, "in and out overlap");
     return 0;
 }
 
 template <class T, int MODE>
 int sym_launch_cubes(const SymArgs &a, hipStream_t st) {
-    const int64_t blocks = (a.n + kSymSpan - 1) / kSymSpan;
-    if (blocks > 0x7fffffff) return fail("too many cubes for one launch");
+    const int64_t blocks = ceil_div(a.n, kSymSpan);
+    RC_GRID(blocks);
     const dim3 g((unsigned)blocks), b(kSymThreads);
-    const int pol = sym_policy(a.n * T::S, a.out ? a.n * T::S : 0);
+    const int pol = mall_policy(a.n * T::S, a.out ? a.n * T::S : 0);
     if (pol == 0) hipLaunchKernelGGL((k_sym_cubes<T, MODE, 0>), g, b, 0, st, a);
     else if (pol == 1) hipLaunchKernelGGL((k_sym_cubes<T, MODE, 1>), g, b, 0, st, a);
     else hipLaunchKernelGGL((k_sym_cubes<T, MODE, 2>), g, b, 0, st, a);
-    RCS_HIP(hipGetLastError());
+    RC_HIP(-2, hipGetLastError());
     return 0;
 }
 
@@ -319,21 +281,21 @@ int rcs_sym_apply(const uint8_t *in, uint8_t *out, int64_t n, int64_t pitch_in, 
         using Y = typename SymOf<T>::type;
         SymArgs a{in, out, sym, nullptr, bad, n, pitch_in, pitch_out, 63, 63};
         if (int rc = sym_check<T>(fn, a, true)) return rc;
-        if (sym && !aligned16(sym)) return sym_fail(fn, "sym is not 16-byte aligned");
-        if (!sym && (sym_uniform < 0 || sym_uniform >= Y::K)) return sym_fail(fn, "sym_uniform is outside 0..K-1");
+        if (sym && !aligned16(sym)) return fail(fn, "sym is not 16-byte aligned");
+        if (!sym && (sym_uniform < 0 || sym_uniform >= Y::K)) return fail(fn, "sym_uniform is outside 0..K-1");
         if (n == 0) return 0;
         if (sym) return sym_launch_cubes<T, 0>(a, S(stream));
         SymRow<T> row;
         memcpy(row.perm, Y::perm_dw[sym_uniform], sizeof row.perm);
         memcpy(row.rel, Y::relabel_dw[sym_uniform], sizeof row.rel);
-        const int64_t blocks = (n + kSymSpan - 1) / kSymSpan;
-        if (blocks > 0x7fffffff) return fail("too many cubes for one launch");
+        const int64_t blocks = ceil_div(n, kSymSpan);
+        RC_GRID(blocks);
         const dim3 g((unsigned)blocks), b(kWave);
-        const int pol = sym_policy(n * T::S, n * T::S);
+        const int pol = mall_policy(n * T::S, n * T::S);
         if (pol == 0) hipLaunchKernelGGL((k_sym_uniform<T, 0>), g, b, 0, S(stream), a, row);
         else if (pol == 1) hipLaunchKernelGGL((k_sym_uniform<T, 1>), g, b, 0, S(stream), a, row);
         else hipLaunchKernelGGL((k_sym_uniform<T, 2>), g, b, 0, S(stream), a, row);
-        RCS_HIP(hipGetLastError());
+        RC_HIP(-2, hipGetLastError());
         return 0;
     });
 }
@@ -345,7 +307,7 @@ int rcs_sym_canonical(const uint8_t *in, int64_t n, int64_t pitch_in, int cube_s
         using T = decltype(t);
         SymArgs a{in, out, nullptr, sym_out, nullptr, n, pitch_in, pitch_out, 63, 63};
         if (int rc = sym_check<T>(fn, a, false)) return rc;
-        if (!sym_out || !aligned16(sym_out)) return sym_fail(fn, "sym_out is NULL or not 16-byte aligned");
+        if (!sym_out || !aligned16(sym_out)) return fail(fn, "sym_out is NULL or not 16-byte aligned");
         if (n == 0) return 0;
         return sym_launch_cubes<T, 1>(a, S(stream));
     });

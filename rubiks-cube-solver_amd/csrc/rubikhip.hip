@@ -23,7 +23,9 @@
 //   k_facade_step     CubeEnv.step / a whole move list for ONE cube, results into host-mapped memory
 //   k_facade_expand   key + 12 child keys + solved flags (+ dense one-hots) of ONE cube    mcts.py:83-113
 //   k_read_status     atomic read-and-clear of the per-device status word
-//   k_cubies / k_from_cubies   sticker rows <-> cubie bytes (piece, orientation), the legality status byte and the perfect indices
+//   k_cubies / k_from_cubies   sticker rows <-> cubie bytes (piece, orientation), the legality status byte and the perfect indices (rc_cubies.h)
+//   k_episode_end     episode counters and the masked re-scramble (rc_episode.h)
+// Host plumbing (errors, RC_HIP, tile_shift, by_size, ...) is rc_host.h's; tile addressing and RowPolicy are rc_device.h's.
 #include <hip/hip_runtime.h>
 
 #include <atomic>
@@ -35,6 +37,7 @@
 
 #include "../../include/rubikhip.h"
 #include "rc_device.h"
+#include "rc_host.h"
 
 using namespace rc;
 
@@ -49,15 +52,6 @@ namespace {
 constexpr int kWave = 64;
 __device__ uint32_t g_status;  // RC_STATUS_* bits, per device (one code object instance per device)
 
-// Tiled structure-of-arrays addressing (include/rubikhip.h "State layout"): cube n of a buffer
-// with `rows` rows lives in tile n / pitch; tiles follow each other, [tile][row][pitch].
-// `shift` = log2(pitch) when the buffer has several tiles, 63 when it has one (then tile = 0 and
-// any pitch % 16 == 0 works).  g0 is a wave-uniform cube index that is a multiple of the wave's
-// span (<= 512 cubes: 8 per lane at most), so a wave never straddles tiles (multi-tile pitch is a multiple of 512 = kMinTile).
-__device__ __forceinline__ int64_t tile_off(int64_t g0, int64_t pitch, int shift, int rows) {
-    return g0 + (g0 >> shift) * (rows - 1) * pitch;
-}
-
 // ------------------------------------------------------------------------------ fill
 template <class T>
 __global__ void __launch_bounds__(kWave) k_fill_solved(uint8_t *base, int64_t n, int64_t pitch, int shift) {
@@ -67,7 +61,7 @@ __global__ void __launch_bounds__(kWave) k_fill_solved(uint8_t *base, int64_t n,
     const __amdgpu_buffer_rsrc_t r = make_srd(base + tile_off(g0, pitch, shift, T::S));
     const uint32_t rs = (uint32_t)pitch;
 #pragma unroll
-    for (int s = 0; s < T::S; ++s) bst<2, kAuxCached>(r, lo, s * rs, splat<2>((uint32_t)(s / T::FACE) * 0x01010101u));
+    for (int s = 0; s < T::S; ++s) bst<2, kAuxCached>(r, lo, s * rs, solved_row<T, 2>(s));
 }
 
 // ------------------------------------------------------------------------------ step
@@ -97,28 +91,6 @@ __device__ __forceinline__ void store_reward(float *reward, int64_t n0, int64_t 
             if (n0 + j < n) reward[n0 + j] = reward_of(dn.d[j >> 2], j & 3);
     }
 }
-
-// Row-traffic policy of the step kernel (aux bits in rc_device.h):
-//   POL 0  everything default-cached: the launch's working set fits the 256 MiB Infinity Cache;
-//   POL 1  inputs streamed (nt), outputs written through but kept (sc0 sc1): the next launch reads what this one
-//          wrote and the output alone still fits the Infinity Cache (state ping-pong of 2^22 cubes);
-//   POL 2  inputs streamed, outputs streamed (sc0 sc1 nt): beyond that;
-//   POL 3  state rows default-cached, side outputs streamed: the STATE fits the Infinity Cache but state + code + reward
-//          would not (in-place steps of 2^22 cubes with the fused code, ping-pong of 2^21).
-// SIDE = the outputs nobody re-reads in the next launch (compact code, done, reward): under POL 1 they are streamed past
-// the Infinity Cache so that they do not push the kept state rows out of it (226 MB of state + 84 MB of code would not fit).
-#ifndef RC_SIDE_AUX_POL1
-#define RC_SIDE_AUX_POL1 kAuxStreamStore
-#endif
-template <int POL> struct RowPolicy;
-template <> struct RowPolicy<0> { static constexpr int LD = kAuxCached, ST = kAuxCached, SIDE = kAuxCached; };
-template <> struct RowPolicy<1> { static constexpr int LD = kAuxStreamLoad, ST = kAuxKeepStore, SIDE = RC_SIDE_AUX_POL1; };
-template <> struct RowPolicy<2> { static constexpr int LD = kAuxStreamLoad, ST = kAuxStreamStore, SIDE = kAuxStreamStore; };
-template <> struct RowPolicy<3> { static constexpr int LD = kAuxCached, ST = kAuxCached, SIDE = kAuxStreamStore; };
-// POL 4 (rc_apply_moves_ws beyond the Infinity Cache): state rows streamed both ways, the side outputs -- the compact code the front
-// writer reads back in the very next launch -- written through and KEPT.  Streamed past the cache instead, the code comes back from
-// HBM with a miss latency per front workgroup: the two-launch route drops from 0.89 to 0.52 of peak at 2^21 cubes.
-template <> struct RowPolicy<4> { static constexpr int LD = kAuxStreamLoad, ST = kAuxStreamStore, SIDE = kAuxKeepStore; };
 
 // One lane = 4*V consecutive cubes.  MOVE: apply actions; STORE: write the state rows;
 // CODE: write the compact code rows.  FULL: every pack of the wave lies
@@ -630,7 +602,7 @@ __global__ void __launch_bounds__(kWave) k_adi(AdiArgs a) {
     if (w0 >= a.n_walks) return;
     Pk<V> s[T::S];
 #pragma unroll
-    for (int i = 0; i < T::S; ++i) s[i] = splat<V>((uint32_t)(i / T::FACE) * 0x01010101u);
+    for (int i = 0; i < T::S; ++i) s[i] = solved_row<T, V>(i);
     WalkRng rng[4 * V];
     if (a.actions_in == nullptr) {
 #pragma unroll
@@ -1180,37 +1152,8 @@ __global__ void __launch_bounds__(256) k_search_pack(const uint8_t *__restrict__
 __global__ void k_read_status(uint32_t *host_word) { *host_word = atomicExch(&g_status, 0u); }
 
 // ------------------------------------------------------------------------- host side
-thread_local char t_err[256] = "";
-
-int fail(int code, const char *fmt, const char *detail = "") {
-    snprintf(t_err, sizeof t_err, fmt, detail);
-    return code;
-}
-#define RC_HIP(call)                                                              \
-    do {                                                                          \
-        hipError_t e_ = (call);                                                   \
-        if (e_ != hipSuccess) return fail(RC_EHIP, #call ": %s", hipGetErrorString(e_)); \
-    } while (0)
-
-inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+static_assert(RC_EINVAL == kEinval, "rc_host.h: by_size and RC_GRID refuse with this library's RC_EINVAL");
 inline bool bad_pitch(int64_t pitch, int64_t n) { return pitch < n || (pitch & 15) != 0; }  // single-tile buffers
-// state / code buffers may be tiled: one tile (pitch >= n, pitch % 16 == 0) or several
-// (pitch a power of two >= kMinTile = 512, the widest wave span).  Returns the shift for tile_off, or -1 if the pitch is bad.
-// Row offsets inside a tile are 32-bit scalar offsets of buffer instructions: rows * pitch < 2^32
-// (a single tile of more than 79 M 3x3x3 cubes has to be split into tiles).
-constexpr int64_t kMinTile = 512;
-inline int tile_shift(int64_t pitch, int64_t n, int rows = 54) {
-    if (pitch <= 0 || (pitch & 15) != 0 || pitch * rows >= ((int64_t)1 << 32)) return -1;
-    if (n <= pitch) return 63;
-    if (pitch < kMinTile || (pitch & (pitch - 1)) != 0) return -1;
-    int sh = 0;
-    while (((int64_t)1 << sh) < pitch) ++sh;
-    return sh;
-}
-inline hipStream_t S(void *s) { return static_cast<hipStream_t>(s); }
-inline bool grid_ok(int64_t blocks) { return blocks > 0 && blocks <= 0x7fffffff; }
-#define RC_GRID(blocks) \
-    do { if (!grid_ok(blocks)) return fail(RC_EINVAL, "too many cubes for one launch%s"); } while (0)
 
 // rc_init bookkeeping: every launching entry point returns RC_ENODEV until rc_init(device) has succeeded for the CURRENT device
 // (a plain-C caller that skips it would otherwise see a raw HIP launch error, or run on a device that is not gfx950).
@@ -1223,13 +1166,6 @@ int need_init() {
     return RC_OK;
 }
 #define RC_NEED_INIT() do { if (int rc_ = need_init()) return rc_; } while (0)
-
-template <class F>
-int by_size(int cube_size, F &&f) {
-    if (cube_size == 3) return f(Cube3{});
-    if (cube_size == 2) return f(Cube2{});
-    return fail(RC_EINVAL, "cube_size must be 2 or 3%s");  // NotImplementedError, cube_env.py:44
-}
 
 // The twin of by_size for the dense one-hot formats: f gets Fmt<E>{} of fmt's element type (fmt is one of RC_FMT_U8 .. RC_FMT_BF16).
 template <class E>
@@ -1285,7 +1221,7 @@ int pick_v(int64_t n, const Variant &v) {
     if (v.units == 1 || v.units == 2) return v.units;
     return n >= (int64_t)1 << 18 ? 2 : 1;
 }
-constexpr int64_t kMallBytes = (int64_t)240 << 20;   // what we count on of the 256 MiB Infinity Cache
+// The step kernel's pick (RowPolicy 0..4 of rc_device.h): rc_host.h's three-way rule, and before it the two cases its side outputs add.
 int pick_policy(int64_t in_bytes, int64_t out_bytes, bool in_place, int64_t side_bytes, const Variant &v) {
     if (v.tens == 1) return 2;
     if (v.tens == 2) return 0;
@@ -1294,14 +1230,11 @@ int pick_policy(int64_t in_bytes, int64_t out_bytes, bool in_place, int64_t side
     const int64_t touched = in_place ? in_bytes : in_bytes + out_bytes;
     if (touched + side_bytes <= kMallBytes) return 0;   // resident: default-cached (1M cubes run out of the Infinity Cache)
     if (touched <= kMallBytes) return 3;                // the state is resident, its side outputs (code, reward, done) stream past it
-    if (!in_place && out_bytes > 0 && out_bytes <= kMallBytes) return 1;   // stream the input, keep the output for the next launch
-    return 2;
+    return out_bytes > 0 ? mall_policy(in_bytes, out_bytes) : 2;   // stream the input; keep the output for the next launch if it fits (in place: it does not)
 }
 // bytes of the outputs no later launch of the env loop reads back: compact code, done flags, reward
 template <class T>
 int64_t side_bytes(int64_t n, bool code, bool done, bool reward) { return n * ((code ? T::SLOTS : 0) + (done ? 1 : 0) + (reward ? 4 : 0)); }
-
-inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 // Dense writer form.  100000s digit of `variant`: 1 -> 64-cube tiles, 2 -> 256-cube tiles (256-thread workgroups), 3 -> the wide
 // form (3x3x3 only).  Default: wide from 2^17 cubes (3x3x3), 256-cube tiles for 2x2x2 batches of that size, else 64-cube tiles
@@ -1417,7 +1350,7 @@ int launch_code_to_dense(const uint8_t *code, int64_t n, int64_t code_pitch, int
             else if (p.lds) launch_front<T, E, true>(code, n, code_pitch, sh, out, st, p);
             else launch_front<T, E, false>(code, n, code_pitch, sh, out, st, p);
         } else return fail(RC_EINVAL, "the wide and front writers are 3x3x3 only%s");
-        RC_HIP(hipGetLastError());
+        RC_HIP(RC_EHIP, hipGetLastError());
         return RC_OK;
     });
 }
@@ -1435,7 +1368,7 @@ int launch_family_to_dense(const uint8_t *fam, int64_t n, int64_t pitch, int sh,
         using E = typename F::type;
         hipLaunchKernelGGL((k_code_to_dense_front<T, E, F::fronts, F::lds, true>), dim3((unsigned)p.grid_x, (unsigned)p.grid_y), dim3(p.block), 0, st, fam, n, pitch, sh,
                            static_cast<E *>(onehot), p.per_xcd, p.per_front, fb);
-        RC_HIP(hipGetLastError());
+        RC_HIP(RC_EHIP, hipGetLastError());
         return RC_OK;
     });
 }
@@ -1494,7 +1427,7 @@ int launch_step(const StepArgs &a, hipStream_t st, const StepPlan &p) {
     else if (p.pol == 2) hipLaunchKernelGGL((k_step<T, V, MOVE, MOVE, CODE, 2, kStepBlock>), g, b, 0, st, a);
     else if (p.pol == 1) hipLaunchKernelGGL((k_step<T, V, MOVE, MOVE, CODE, 1, kStepBlock>), g, b, 0, st, a);
     else hipLaunchKernelGGL((k_step<T, V, MOVE, MOVE, CODE, 0, kStepBlock>), g, b, 0, st, a);
-    RC_HIP(hipGetLastError());
+    RC_HIP(RC_EHIP, hipGetLastError());
     return RC_OK;
 }
 template <class T, bool MOVE, int TILE>
@@ -1503,7 +1436,7 @@ int launch_step_dense(const StepArgs &a, void *onehot, int fmt, hipStream_t st, 
     return by_fmt(fmt, [&](auto e) {
         using E = typename decltype(e)::type;
         hipLaunchKernelGGL((k_step_dense<T, E, MOVE, MOVE, TILE>), dim3((unsigned)p.grid_x), dim3(p.block), 0, st, a, static_cast<E *>(onehot));
-        RC_HIP(hipGetLastError());
+        RC_HIP(RC_EHIP, hipGetLastError());
         return RC_OK;
     });
 }
@@ -1658,7 +1591,7 @@ int launch_expand(const ExpandArgs &a, hipStream_t st, const ExpandPlan &p) {
     else if (p.v == 2) hipLaunchKernelGGL((k_expand<T, 2, false>), g, b, 0, st, a);
     else if (p.code) hipLaunchKernelGGL((k_expand<T, 1, true>), g, b, 0, st, a);
     else hipLaunchKernelGGL((k_expand<T, 1, false>), g, b, 0, st, a);
-    RC_HIP(hipGetLastError());
+    RC_HIP(RC_EHIP, hipGetLastError());
     return RC_OK;
 }
 
@@ -1669,7 +1602,7 @@ int launch_adi(const AdiArgs &a, hipStream_t st, const AdiPlan &p) {
     if (p.family) hipLaunchKernelGGL((k_adi<T, V, true, true>), g, b, 0, st, a);      // (adi_common: no codes beside the family record)
     else if (p.code) hipLaunchKernelGGL((k_adi<T, V, true>), g, b, 0, st, a);
     else hipLaunchKernelGGL((k_adi<T, V, false>), g, b, 0, st, a);
-    RC_HIP(hipGetLastError());
+    RC_HIP(RC_EHIP, hipGetLastError());
     return RC_OK;
 }
 
@@ -1680,32 +1613,24 @@ extern "C" {
 
 int rc_version(void) { return 600; }
 
-// the hash of the sources this binary was compiled from (__graft_entry__.build passes -DRC_SRC_HASH=<16 hex digits>); a plain
-// `hipcc -c` of this file still compiles and reports "unhashed", which the Python binding refuses as stale
-#ifndef RC_SRC_HASH
-#define RC_SRC_HASH unhashed
-#endif
-#define RC_STR2(x) #x
-#define RC_STR(x) RC_STR2(x)
-static const char k_build_id[] = "rc-build-id:" RC_STR(RC_SRC_HASH);
-const char *rc_build_id(void) { return k_build_id + 12; }
+RC_BUILD_ID(rc_build_id)
 
 const char *rc_last_error(void) { return t_err; }
 
 int rc_init(int device) {
     int count = 0, prev = 0;
-    RC_HIP(hipGetDeviceCount(&count));
+    RC_HIP(RC_EHIP, hipGetDeviceCount(&count));
     if (device < 0 || device >= count) return fail(RC_ENODEV, "no such HIP device%s");
     hipDeviceProp_t prop;
-    RC_HIP(hipGetDeviceProperties(&prop, device));
+    RC_HIP(RC_EHIP, hipGetDeviceProperties(&prop, device));
     if (strncmp(prop.gcnArchName, "gfx950", 6) != 0) return fail(RC_ENODEV, "librubikhip is built for gfx950 only, device is %s", prop.gcnArchName);
     // clear the device's status word; the caller's current device is left as it was
-    RC_HIP(hipGetDevice(&prev));
-    RC_HIP(hipSetDevice(device));
+    RC_HIP(RC_EHIP, hipGetDevice(&prev));
+    RC_HIP(RC_EHIP, hipSetDevice(device));
     uint32_t zero = 0;
     const hipError_t e = hipMemcpyToSymbol(HIP_SYMBOL(g_status), &zero, sizeof zero);
-    RC_HIP(hipSetDevice(prev));
-    RC_HIP(e);
+    RC_HIP(RC_EHIP, hipSetDevice(prev));
+    RC_HIP(RC_EHIP, e);
     if (device < 256) g_inited[device >> 6].fetch_or((uint64_t)1 << (device & 63), std::memory_order_release);
     return RC_OK;
 }
@@ -1735,7 +1660,7 @@ int rc_fill_solved(uint8_t *stp, int64_t n, int64_t pitch, int cube_size, void *
         const int64_t blocks = (n + kWave * 8 - 1) / (kWave * 8);
         RC_GRID(blocks);
         hipLaunchKernelGGL((k_fill_solved<T>), dim3((unsigned)blocks), dim3(kWave), 0, S(stream), stp, n, pitch, sh);
-        RC_HIP(hipGetLastError());
+        RC_HIP(RC_EHIP, hipGetLastError());
         return RC_OK;
     });
 }
@@ -1769,7 +1694,7 @@ static int step_common(const uint8_t *in, uint8_t *out, const uint8_t *actions, 
                 const uintptr_t w0 = reinterpret_cast<uintptr_t>(workspace), q0 = reinterpret_cast<uintptr_t>(q);
                 return q != nullptr && bytes > 0 && q0 < w0 + (uintptr_t)p.ws_need && w0 < q0 + (uintptr_t)bytes;
             };
-            const auto state_bytes = [&](int64_t pitch) { return (n <= pitch ? 1 : (n + pitch - 1) / pitch) * T::S * pitch; };
+            const auto state_bytes = [&](int64_t pitch) { return tiles_of(n, pitch) * T::S * pitch; };
             const int64_t esize = by_fmt(fmt, [](auto e) { return decltype(e)::size; });
             if (hits(in, state_bytes(pitch_in)) || (store && hits(out, state_bytes(pitch_out))) || hits(actions, n) || hits(reward, 4 * n) ||
                 hits(done, n) || hits(onehot, n * T::R * T::C * esize))
@@ -1825,7 +1750,7 @@ int rc_scramble_from(const uint8_t *src, uint8_t *stp, int64_t n, int64_t pitch,
         const int64_t blocks = (n + kWave * 4 - 1) / (kWave * 4);
         RC_GRID(blocks);
         hipLaunchKernelGGL((k_scramble<T>), dim3((unsigned)blocks), dim3(kWave), 0, S(stream), a);
-        RC_HIP(hipGetLastError());
+        RC_HIP(RC_EHIP, hipGetLastError());
         return RC_OK;
     });
 }
@@ -1844,11 +1769,11 @@ int rc_search_pack(const uint8_t *leaf_code, const uint8_t *child_code, const ui
     if (n == 0) return RC_OK;
     return by_size(cube_size, [&](auto t) {
         using T = decltype(t);
-        const int64_t blocks = (n + 255) / 256, tiles = n <= pitch ? 1 : (n + pitch - 1) / pitch;
+        const int64_t blocks = (n + 255) / 256, tiles = tiles_of(n, pitch);
         RC_GRID(blocks);
         hipLaunchKernelGGL((k_search_pack<T>), dim3((unsigned)blocks, T::A + 1), dim3(256), 0, S(stream), leaf_code, child_code, child_solved, n, pitch, sh, tiles,
                            leaf_out, child_out, solved_out);
-        RC_HIP(hipGetLastError());
+        RC_HIP(RC_EHIP, hipGetLastError());
         return RC_OK;
     });
 }
@@ -1877,13 +1802,13 @@ int rc_legacy_scramble_actions_ex(const uint32_t *seeds, const int32_t *counts, 
         const int limit = lim ? lim : kMtStreamMax;
         if (cube_size == 3) hipLaunchKernelGGL((k_legacy_actions_stream<12>), g, b, 0, S(stream), seeds, counts, count_uniform, kmax, n, actions_out, pitch, limit);
         else hipLaunchKernelGGL((k_legacy_actions_stream<6>), g, b, 0, S(stream), seeds, counts, count_uniform, kmax, n, actions_out, pitch, limit);
-        RC_HIP(hipGetLastError());
+        RC_HIP(RC_EHIP, hipGetLastError());
     }
     const int64_t chunks = (waves + 3) / 4;
     const dim3 g((unsigned)(streamed ? (chunks < 1024 ? chunks : 1024) : waves)), b(kWave);
     if (cube_size == 3) hipLaunchKernelGGL((k_legacy_actions<12>), g, b, 0, S(stream), seeds, counts, count_uniform, kmax, n, actions_out, pitch, streamed ? 1 : 0);
     else hipLaunchKernelGGL((k_legacy_actions<6>), g, b, 0, S(stream), seeds, counts, count_uniform, kmax, n, actions_out, pitch, streamed ? 1 : 0);
-    RC_HIP(hipGetLastError());
+    RC_HIP(RC_EHIP, hipGetLastError());
     return RC_OK;
 }
 
@@ -1962,7 +1887,7 @@ int rc_expand_children_ex(const uint8_t *in, int64_t n, int64_t pitch_in, int cu
     return by_size(cube_size, [&](auto t) {
         using T = decltype(t);
         const ExpandPlan p = plan_expand<T>(n, children != nullptr, child_code != nullptr, v);
-        const ExpandArgs a{in, n, pitch_in, children, child_solved, child_code, pitch_out, n <= pitch_out ? 1 : (n + pitch_out - 1) / pitch_out,
+        const ExpandArgs a{in, n, pitch_in, children, child_solved, child_code, pitch_out, tiles_of(n, pitch_out),
                            p.parts, sh_in, sh_out};
         return launch_expand<T>(a, S(stream), p);
     });
@@ -1991,7 +1916,7 @@ static int adi_common(uint64_t seed, uint64_t stream_id, int64_t walk_offset, in
         if (depth > 0xffff) return fail(RC_EINVAL, "rc_adi_generate: depth must be below 65536%s");
         const AdiPlan p = plan_adi<T>(n_walks, depth, children != nullptr, parent_code || child_code || family, family != nullptr,
                                       children || child_code || child_solved, v);
-        AdiArgs a{seed, stream_id, walk_offset, n_walks, pitch, n_walks <= pitch ? 1 : (n_walks + pitch - 1) / pitch, depth,
+        AdiArgs a{seed, stream_id, walk_offset, n_walks, pitch, tiles_of(n_walks, pitch), depth,
                   p.parts, sh, actions_in, actions_out, parents, parent_code, children, child_code, child_solved, family, p.segs, {}};
         memcpy(a.seg_lo, p.seg_lo, sizeof a.seg_lo);
         return p.v == 2 ? launch_adi<T, 2>(a, S(stream), p) : launch_adi<T, 1>(a, S(stream), p);
@@ -2039,7 +1964,7 @@ int rc_onehot_from_family_depths(const uint8_t *family, int64_t n, int64_t pitch
     if (block_stride < n) return fail(RC_EINVAL, "rc_onehot_from_family: block_stride must be >= n_cubes%s");
     if (n_depths < 0 || n_depths > 5041) return fail(RC_EINVAL, "rc_onehot_from_family: n_depths must be in 0..5041%s");
     if (n == 0 || n_depths == 0) return RC_OK;
-    const int64_t tiles = n <= pitch ? 1 : (n + pitch - 1) / pitch;
+    const int64_t tiles = tiles_of(n, pitch);
     const FamilyBlocks fb{block_stride, tiles * kFamily<Cube3>.nf * pitch, (int64_t)(Cube3::A + 1) * block_stride};   // + bytes of one depth's record / cubes of one depth's blocks
     return launch_family_to_dense<Cube3>(family, n, pitch, sh, onehot, fmt, fb, S(stream), plan_family_to_dense<Cube3>(n, fmt, n_depths));
 }
@@ -2056,7 +1981,7 @@ static int launch_targets(const TargetArgs &t, int n_depths, int cube_size, void
     if (cube_size == 3) hipLaunchKernelGGL((k_adi_targets<12>), g, b, 0, S(stream), t);
     else if (cube_size == 2) hipLaunchKernelGGL((k_adi_targets<6>), g, b, 0, S(stream), t);
     else return fail(RC_EINVAL, "cube_size must be 2 or 3%s");
-    RC_HIP(hipGetLastError());
+    RC_HIP(RC_EHIP, hipGetLastError());
     return RC_OK;
 }
 
@@ -2153,7 +2078,7 @@ int rc_facade_steps(uint8_t *stp, int64_t pitch, int cube_size, const uint8_t *a
             memcpy(fa.a, actions + done, (size_t)m);
             done += m;
             hipLaunchKernelGGL((k_facade_step<T>), dim3(1), dim3(kWave), 0, S(stream), stp, (uint32_t)pitch, fa, dev_out, done == n_actions ? seq : 0u);
-            RC_HIP(hipGetLastError());
+            RC_HIP(RC_EHIP, hipGetLastError());
         } while (done < n_actions);
         return RC_OK;
     });
@@ -2175,7 +2100,7 @@ static int facade_wait(uint8_t *host_out, uint32_t seq, void *stream, const char
         if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) == seq) return RC_OK;
         __builtin_ia32_pause();
     }
-    RC_HIP(hipStreamSynchronize(S(stream)));
+    RC_HIP(RC_EHIP, hipStreamSynchronize(S(stream)));
     if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) == seq) return RC_OK;
     return fail(RC_EHIP, "%s: the result never reached host_out (is it host-mapped pinned memory?)", who);
 }
@@ -2195,7 +2120,7 @@ int rc_facade_expand(const uint8_t *stp, int64_t pitch, int cube_size, uint8_t *
     const int rc = by_size(cube_size, [&](auto t) {
         using T = decltype(t);
         hipLaunchKernelGGL((k_facade_expand<T>), dim3(1), dim3(kWave), 0, S(stream), stp, (uint32_t)pitch, dev_out, seq, dense);
-        RC_HIP(hipGetLastError());
+        RC_HIP(RC_EHIP, hipGetLastError());
         return RC_OK;
     });
     if (rc != RC_OK || !wait) return rc;
@@ -2270,256 +2195,19 @@ int rc_read_status(uint32_t *status, void *stream) {
     // one atomic read-and-clear on the device (bits set by kernels still running on OTHER streams are neither lost nor
     // reported early: they show in a later read); the word travels through a pinned, host-mapped scratch word
     static thread_local uint32_t *host_word = nullptr;
-    if (!host_word) RC_HIP(hipHostMalloc(reinterpret_cast<void **>(&host_word), sizeof(uint32_t), hipHostMallocMapped | hipHostMallocPortable));
+    if (!host_word) RC_HIP(RC_EHIP, hipHostMalloc(reinterpret_cast<void **>(&host_word), sizeof(uint32_t), hipHostMallocMapped | hipHostMallocPortable));
     *host_word = 0xffffffffu;
     hipLaunchKernelGGL(k_read_status, dim3(1), dim3(1), 0, S(stream), host_word);
-    RC_HIP(hipGetLastError());
-    RC_HIP(hipStreamSynchronize(S(stream)));
+    RC_HIP(RC_EHIP, hipGetLastError());
+    RC_HIP(RC_EHIP, hipStreamSynchronize(S(stream)));
     *status = *host_word;
     return RC_OK;
 }
 
 }  // extern "C"
 
-// ================================================================ cubie coordinates (include/rubikhip.h "Cubie coordinates", rcc_*)
-//   k_cubies        S sticker rows in, per cube: SLOTS cubie bytes, the status byte, and (INDEX) the two permutation / orientation
-//                   indices.  One lane = one pack of 4 * V cubes, everything in packed bytes (rc_device.h cubies_of); the indices
-//                   leave the packed domain, 4 * V scalar results per lane, and exist only in the INDEX instantiations.
-//   k_from_cubies   the inverse: SLOTS cubie rows in, S sticker rows out (rc_device.h stickers_of).
-// Both: raw buffer row access, whole packs; the ragged last pack of a batch merges with what the output rows hold, so pad columns
-// keep their bytes.
-namespace {
-
-struct CubieArgs {
-    const uint8_t *st;
-    int64_t n, pitch;
-    int sh;
-    uint8_t *cubies;
-    int64_t cubie_pitch;
-    int sh_c;
-    uint8_t *status;
-    uint32_t *corner_index;
-    uint64_t *edge_index;
-};
-
-// 0xff in the bytes of dword k of a pack whose cubes exist (r = cubes of the pack inside the batch)
-__device__ __forceinline__ uint32_t pack_valid(int64_t r, int k) {
-    const int64_t rk = r - 4 * k;
-    return rk >= 4 ? 0xffffffffu : rk <= 0 ? 0u : ((1u << (8 * (int)rk)) - 1u);
-}
-// a whole pack of one row, or (the ragged last pack) only the bytes of the cubes that exist
-template <int V, int AUX>
-__device__ __forceinline__ void store_row(__amdgpu_buffer_rsrc_t r, uint32_t lo, uint32_t so, Pk<V> v, bool full, Pk<V> keep) {
-    if (full) bst<V, AUX>(r, lo, so, v);
-    else bst<V, kAuxCached>(r, lo, so, sel(keep, v, bld<V, kAuxCached>(r, lo, so)));
-}
-
-template <class T, int V, bool INDEX, bool STREAM>
-__global__ void __launch_bounds__(kWave) k_cubies(CubieArgs a) {
-    constexpr int LD = STREAM ? kAuxStreamLoad : kAuxCached, ST = STREAM ? kAuxStreamStore : kAuxCached;
-    const int64_t g0 = (int64_t)blockIdx.x * (kWave * 4 * V);
-    const uint32_t lo = threadIdx.x * (4 * V);
-    const int64_t n0 = g0 + lo;
-    if (n0 >= a.n) return;
-    const bool full = n0 + 4 * V <= a.n;
-    Pk<V> s[T::S];
-    {
-        const __amdgpu_buffer_rsrc_t r = make_srd(a.st + tile_off(g0, a.pitch, a.sh, T::S));
-        const uint32_t rs = (uint32_t)a.pitch;
-#pragma unroll
-        for (int i = 0; i < T::S; ++i) s[i] = bld<V, LD>(r, lo, i * rs);
-    }
-    Cubies<T, V> c;
-    cubies_of<T, V, INDEX>(s, c);
-    if (a.cubies) {
-        const __amdgpu_buffer_rsrc_t r = make_srd(a.cubies + tile_off(g0, a.cubie_pitch, a.sh_c, T::SLOTS));
-        const uint32_t rs = (uint32_t)a.cubie_pitch;
-        Pk<V> keep;
-        RC_V keep.d[k] = pack_valid(a.n - n0, k);
-#pragma unroll
-        for (int p = 0; p < T::SLOTS; ++p) store_row<V, ST>(r, lo, p * rs, c.code[p], full, keep);
-    }
-    if (a.status) st_tail<V>(a.status, n0, a.n, c.status);
-    if constexpr (INDEX) {
-        uint32_t ci[4 * V], el[4 * V], eo[4 * V];
-        sfor<4 * V>([&](auto jc) {
-            constexpr int j = decltype(jc)::value, w = j >> 2, sft = 8 * (j & 3);
-            const auto byte = [&](const Pk<V> &p) { return (p.d[w] >> sft) & 0xffu; };
-            const bool legal = byte(c.status) == 0;
-            uint32_t lehmer = 0, oris = 0;
-            sfor<T::NC>([&](auto qc) {                                           // sum_q lt[q] * (NC - 1 - q)!
-                constexpr int q = decltype(qc)::value;
-                lehmer = lehmer * (uint32_t)(T::NC - q) + byte(c.lt[q]);
-            });
-            sfor<T::NC - 1>([&](auto qc) {                                       // sum_{q < NC - 1} ori[q] * 3^q
-                constexpr int q = T::NC - 2 - decltype(qc)::value;
-                oris = oris * 3u + byte(c.ori[q]);
-            });
-            constexpr uint32_t pow3 = T::NC == 8 ? 2187u : 729u;                // 3^(NC - 1)
-            ci[j] = legal ? lehmer * pow3 + oris : 0xffffffffu;
-            lehmer = 0, oris = 0;
-            sfor<T::NE>([&](auto qc) {
-                constexpr int q = decltype(qc)::value;
-                lehmer = lehmer * (uint32_t)(T::NE - q) + byte(c.lt[T::NC + q]);
-            });
-            sfor<(T::NE > 0 ? T::NE - 1 : 0)>([&](auto qc) {
-                constexpr int q = decltype(qc)::value;
-                oris |= byte(c.ori[T::NC + q]) << q;
-            });
-            el[j] = legal ? (lehmer << 11) | oris : 0xffffffffu;                 // edge_index = lehmer * 2^11 + oris: low, high word
-            eo[j] = legal ? lehmer >> 21 : 0xffffffffu;
-        });
-        if (a.corner_index) {
-            if (full) {
-#pragma unroll
-                for (int k = 0; k < V; ++k) {
-                    const u32x4 u = {ci[4 * k], ci[4 * k + 1], ci[4 * k + 2], ci[4 * k + 3]};
-                    *reinterpret_cast<u32x4 *>(a.corner_index + n0 + 4 * k) = u;
-                }
-            } else {
-#pragma unroll
-                for (int j = 0; j < 4 * V; ++j)
-                    if (n0 + j < a.n) a.corner_index[n0 + j] = ci[j];
-            }
-        }
-        if constexpr (T::NE > 0) {
-            if (a.edge_index) {
-                if (full) {
-#pragma unroll
-                    for (int k = 0; k < 2 * V; ++k) {
-                        const u32x4 u = {el[2 * k], eo[2 * k], el[2 * k + 1], eo[2 * k + 1]};
-                        *reinterpret_cast<u32x4 *>(a.edge_index + n0 + 2 * k) = u;
-                    }
-                } else {
-#pragma unroll
-                    for (int j = 0; j < 4 * V; ++j)
-                        if (n0 + j < a.n) a.edge_index[n0 + j] = ((uint64_t)eo[j] << 32) | el[j];
-                }
-            }
-        }
-    }
-}
-
-struct FromCubieArgs {
-    const uint8_t *cubies;
-    int64_t n, cubie_pitch;
-    int sh_c;
-    uint8_t *st;
-    int64_t pitch;
-    int sh;
-    uint8_t *bad;
-};
-
-template <class T, int V>
-__global__ void __launch_bounds__(kWave) k_from_cubies(FromCubieArgs a) {
-    const int64_t g0 = (int64_t)blockIdx.x * (kWave * 4 * V);
-    const uint32_t lo = threadIdx.x * (4 * V);
-    const int64_t n0 = g0 + lo;
-    if (n0 >= a.n) return;
-    const bool full = n0 + 4 * V <= a.n;
-    Pk<V> code[T::SLOTS], s[T::S];
-    {
-        const __amdgpu_buffer_rsrc_t r = make_srd(a.cubies + tile_off(g0, a.cubie_pitch, a.sh_c, T::SLOTS));
-        const uint32_t rs = (uint32_t)a.cubie_pitch;
-#pragma unroll
-        for (int p = 0; p < T::SLOTS; ++p) code[p] = bld<V, kAuxCached>(r, lo, p * rs);
-    }
-    const Pk<V> bad = stickers_of<T, V>(code, s);
-    if (a.bad && any_bad<V>(bad, n0, a.n)) *a.bad = 1;                            // the idea of RC_STATUS_BAD_ACTION: a flag, no trap
-    const __amdgpu_buffer_rsrc_t r = make_srd(a.st + tile_off(g0, a.pitch, a.sh, T::S));
-    const uint32_t rs = (uint32_t)a.pitch;
-    Pk<V> keep;
-    RC_V keep.d[k] = pack_valid(a.n - n0, k);
-#pragma unroll
-    for (int i = 0; i < T::S; ++i) store_row<V, kAuxCached>(r, lo, i * rs, s[i], full, keep);
-}
-
-// Pack width: 8 cubes per lane from 2^18 cubes on the 2x2x2, as the step kernel; 4 always on the 3x3x3, where 8 cubes' 54 sticker rows,
-// 20 cubie bytes, pieces and orientations do not fit 256 VGPRs (the V = 2 build of the index form spilled 48..136 bytes per lane).
-template <class T>
-int cubies_v(int64_t n) { return T::SIZE == 2 ? pick_v(n, Variant{}) : 1; }
-
-template <class T, int V, bool INDEX>
-int launch_cubies(const CubieArgs &a, hipStream_t st, bool stream_rows) {
-    const int64_t blocks = (a.n + kWave * 4 * V - 1) / (kWave * 4 * V);
-    RC_GRID(blocks);
-    const dim3 g((unsigned)blocks), b(kWave);
-    if (stream_rows) hipLaunchKernelGGL((k_cubies<T, V, INDEX, true>), g, b, 0, st, a);
-    else hipLaunchKernelGGL((k_cubies<T, V, INDEX, false>), g, b, 0, st, a);
-    RC_HIP(hipGetLastError());
-    return RC_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int rcc_cubies(const uint8_t *stp, int64_t n, int64_t pitch, int cube_size, uint8_t *cubies, int64_t cubie_pitch, uint8_t *status,
-               uint32_t *corner_index, uint64_t *edge_index, void *stream) {
-    RC_NEED_INIT();
-    const auto bad = [](const char *what) { return fail(RC_EINVAL, "rcc_cubies: %s", what); };
-    if (cube_size != 2 && cube_size != 3) return bad("cube_size must be 2 or 3");
-    if (n < 0) return bad("n_cubes is negative");
-    if (!stp || !aligned16(stp)) return bad("st is NULL or not 16-byte aligned");
-    const int sh = tile_shift(pitch, n), sh_c = cubies ? tile_shift(cubie_pitch, n, 20) : 63;
-    if (sh < 0) return bad("pitch: need pitch % 16 == 0 and pitch >= n_cubes, or a power-of-two tile >= 512");
-    if (!cubies && !status && !corner_index && !edge_index) return bad("nothing to write: cubies, status, corner_index and edge_index are all NULL");
-    if (cubies && !aligned16(cubies)) return bad("cubies is not 16-byte aligned");
-    if (sh_c < 0) return bad("cubie_pitch: need pitch % 16 == 0 and pitch >= n_cubes, or a power-of-two tile >= 512");
-    if (status && !aligned16(status)) return bad("status is not 16-byte aligned");
-    if (corner_index && !aligned16(corner_index)) return bad("corner_index is not 16-byte aligned");
-    if (edge_index && cube_size == 2) return bad("edge_index must be NULL for cube_size 2 (the 2x2x2 has no edges)");
-    if (edge_index && !aligned16(edge_index)) return bad("edge_index is not 16-byte aligned");
-    if (n == 0) return RC_OK;
-    const CubieArgs a{stp, n, pitch, sh, cubies, cubie_pitch, sh_c, status, corner_index, edge_index};
-    const bool index = corner_index || edge_index;
-    return by_size(cube_size, [&](auto t) {
-        using T = decltype(t);
-        const bool stream_rows = n * (T::S + (cubies ? T::SLOTS : 0) + (status ? 1 : 0) + (corner_index ? 4 : 0) + (edge_index ? 8 : 0)) > kMallBytes;
-        if constexpr (T::SIZE == 2)
-            if (cubies_v<T>(n) == 2) return index ? launch_cubies<T, 2, true>(a, S(stream), stream_rows) : launch_cubies<T, 2, false>(a, S(stream), stream_rows);
-        return index ? launch_cubies<T, 1, true>(a, S(stream), stream_rows) : launch_cubies<T, 1, false>(a, S(stream), stream_rows);
-    });
-}
-
-int rcc_from_cubies(const uint8_t *cubies, int64_t n, int64_t cubie_pitch, int cube_size, uint8_t *stp, int64_t pitch, uint8_t *badp,
-                    void *stream) {
-    RC_NEED_INIT();
-    const auto bad = [](const char *what) { return fail(RC_EINVAL, "rcc_from_cubies: %s", what); };
-    if (cube_size != 2 && cube_size != 3) return bad("cube_size must be 2 or 3");
-    if (n < 0) return bad("n_cubes is negative");
-    if (!cubies || !aligned16(cubies)) return bad("cubies is NULL or not 16-byte aligned");
-    const int sh_c = tile_shift(cubie_pitch, n, 20), sh = tile_shift(pitch, n);
-    if (sh_c < 0) return bad("cubie_pitch: need pitch % 16 == 0 and pitch >= n_cubes, or a power-of-two tile >= 512");
-    if (!stp || !aligned16(stp)) return bad("st is NULL or not 16-byte aligned");
-    if (sh < 0) return bad("pitch: need pitch % 16 == 0 and pitch >= n_cubes, or a power-of-two tile >= 512");
-    if (!badp) return bad("bad is NULL");
-    if (n == 0) return RC_OK;
-    const FromCubieArgs a{cubies, n, cubie_pitch, sh_c, stp, pitch, sh, badp};
-    return by_size(cube_size, [&](auto t) {
-        using T = decltype(t);
-        const int v = pick_v(n, Variant{});
-        const int64_t blocks = (n + kWave * 4 * v - 1) / (kWave * 4 * v);
-        RC_GRID(blocks);
-        if (v == 2) hipLaunchKernelGGL((k_from_cubies<T, 2>), dim3((unsigned)blocks), dim3(kWave), 0, S(stream), a);
-        else hipLaunchKernelGGL((k_from_cubies<T, 1>), dim3((unsigned)blocks), dim3(kWave), 0, S(stream), a);
-        RC_HIP(hipGetLastError());
-        return RC_OK;
-    });
-}
-
-int rcc_tables(int cube_size, uint8_t *corner_cw, uint8_t *edge_facelets, uint8_t *corner_colours, uint8_t *edge_colours) {
-    return by_size(cube_size, [&](auto t) {
-        using T = decltype(t);
-        if (corner_cw) memcpy(corner_cw, T::ccw, (size_t)T::NC * 3);
-        if (corner_colours) memcpy(corner_colours, T::ccol, (size_t)T::NC * 3);
-        if (edge_facelets && T::NE) memcpy(edge_facelets, T::edef, (size_t)T::NE * 2);
-        if (edge_colours && T::NE) memcpy(edge_colours, T::ecol, (size_t)T::NE * 2);
-        return RC_OK;
-    });
-}
-
-}  // extern "C"
+// the rcc_* section of include/rubikhip.h: cubie coordinates and the legality test
+#include "rc_cubies.h"
 
 // the rcx_* extension (include/rubikepisode.h): episode bookkeeping and the masked re-scramble
 #include "rc_episode.h"

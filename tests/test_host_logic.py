@@ -221,6 +221,35 @@ def test_dispatch_fixture_replays():
     assert ops_seen >= {(op, refused) for op in range(1, 6) for refused in (False, True)}
 
 
+def test_refusal_fixture_replays():
+    """Every call of tests/golden/refusals.txt (make_refusals.py: the search, A*, symmetry and net entry points with pitches, sizes,
+    pointers and arguments of their own that the host checks stop before any HIP call) returns the recorded code and leaves the
+    WHOLE recorded error text: the shared layout rule and error plumbing of csrc/rc_host.h answer as each library always did."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("make_refusals", os.path.join(ROOT, "tests", "golden", "make_refusals.py"))
+    gen = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(gen)
+    entries = gen.entry_points()
+    lines = open(os.path.join(ROOT, "tests", "golden", "refusals.txt")).read().splitlines()
+    assert len(lines) > 200 and [line.split("\t")[0] for line in lines] == list(dict.fromkeys(gen.queries()))   # the generator's calls, all of them
+    fns, wrong = set(), []
+
+    def replay():                                                  # on a thread of its own: the error text is thread-local, this thread's stays as it was
+        for line in lines:
+            query, rc, text = line.split("\t")
+            got = gen.call(entries, query)
+            fns.add(query.split(" ")[0])
+            if got != (int(rc), text):
+                wrong.append((query, rc, text, got))
+    import threading
+    t = threading.Thread(target=replay)
+    t.start()
+    t.join()
+    assert not wrong, (len(wrong), wrong[:5])
+    assert fns == {"rc_search_init", "rc_search_expand", "rc_search_select", "rc_search_advance", "rc_search_backtrack", "rca_init", "rca_pop",
+                   "rca_merge", "rca_backtrack", "rcs_sym_apply", "rcs_sym_canonical", "rc_net_first_layer"}
+
+
 def test_no_cpu_fallback_without_gpu():
     """Compute entry points refuse host tensors / a missing device instead of falling back."""
     from rubiks_cube_solver_amd import _lib, ops
