@@ -121,7 +121,11 @@ int rc_search_backtrack(const uint16_t *hist_parent, const uint8_t *hist_action,
  *                         Only the first C - count of them fit; the rest are dropped and overflow[p] is set and stays set; the
  *                         problem goes on with the open nodes it has.
  *           A known state is never re-opened and its g never lowered: DeepCubeA's re-opening rule is deliberately left out.  With
- *           B = 1, weight = 1 and a consistent heuristic the result is still optimal; beyond that no optimality is claimed.
+ *           B = 1, weight = 1 and a consistent heuristic the result is optimal unless a state is first reached by the longer of two
+ *           paths whose parents tie in prio (the newer, deeper parent is popped first and the state keeps the larger g): never under an
+ *           exact heuristic, which walks one geodesic; with the corner table of the rcp_* section and these four calls alone, 3 of 500
+ *           7-move 3x3x3 cubes came out 2 moves long.  rcp_relax below is the missing step, as a call of its own after rca_merge.  Beyond
+ *           that no optimality is claimed.
  *   Every result follows from this rule and never from timing: equal keys within an iteration resolve to the lowest c
  *   (atomicCAS + atomicMin in the scratch table), and the persistent table only ever receives keys it does not hold.
  */
@@ -164,6 +168,65 @@ int rca_merge(int64_t n_problems, int cube_size, int batch, int64_t pitch, int64
  * all no-ops where length <= 0 or length > max_length.  Follows pool_parent from solution. */
 int rca_backtrack(int64_t n_problems, int cube_size, int64_t capacity, const int32_t *pool_parent, const uint8_t *pool_action,
                   const int32_t *length, const int32_t *solution, uint8_t *actions, int max_length, void *stream);
+
+/* ======================================================================================================================
+ * Corner pattern database (DESIGN.md "Corner pattern database"): the rcp_* entry points.  An exact distance table over the corner
+ * states: the whole answer on the 2x2x2 (God's algorithm), the classical admissible lower bound on the 3x3x3.
+ *
+ * THE RULE.  Corner state = (piece[q], ori[q]) for the NC = 8 | 7 corner slots of include/rubikhip.h "Cubie coordinates" (rcc_*);
+ * its index is that section's corner_index, below N = 88 179 840 | 3 674 160.  Move a acts on it as
+ *     piece'[q] = piece[src[a][q]]        ori'[q] = (ori[src[a][q]] + twist[a][q]) mod 3
+ * where 3 * src[a][q] + twist[a][q] is the corner byte of slot q after move a on the solved cube (rcp_tables).
+ * table[i] (uint8, N bytes) = the least number of the env's moves that take corner state i to the solved corners; table[0] = 0 is
+ * the solved state's, and no entry stays 0xFF after a build.  h = table[corner_index] never exceeds a cube's true distance and has
+ * its parity (every quarter turn flips the corner permutation's parity).
+ * Legal, for rcp_lookup and rcp_score_keys, concerns the CORNER state alone: every corner sticker is a colour 0..5, the three stickers
+ * of the 2x2x2's DLB cubie are home, every corner slot names a piece, no piece twice, the ori sum to 0 mod 3.  Edges and centres of a
+ * 3x3x3 are not looked at.  Conventions as above: caller-owned device memory, stream-ordered, nothing allocated, -1 before any launch
+ * on a bad argument, 16-byte alignment and no more, pad columns untouched.  `bytes` is the size of `table` and must be >= N.
+ */
+
+/* N, the bytes of a table; -1 for a cube_size other than 2 | 3.  Host only. */
+int64_t rcp_table_bytes(int cube_size);
+
+/* The library's own move tables, uint8 [A][NC] each (either may be NULL).  Host only. */
+int rcp_tables(int cube_size, uint8_t *src, uint8_t *twist);
+
+/* Build, level by level.  begin: every entry 0xFF, table[0] = 0.  level: every entry that is still 0xFF and has a neighbour (one move
+ * away) at `depth` becomes depth + 1; *count (ONE device uint32, zeroed by the call) receives how many did.  A lane writes only the
+ * entries it owns and compares what it reads with `depth` alone, so the result does not depend on scheduling.  The caller runs
+ * depth = 0, 1, .. until a level reports 0.  0 <= depth < 254. */
+int rcp_build_begin(uint8_t *table, int64_t bytes, int cube_size, void *stream);
+int rcp_build_level(uint8_t *table, int64_t bytes, int cube_size, int depth, uint32_t *count, void *stream);
+
+/* index uint32 [n] -> cubie rows in the rcc_* layout ([tiles][SLOTS][cubie_pitch], rcc_from_cubies turns them into stickers).  The
+ * corners are those of the index.  On the 3x3x3 every edge is home and unflipped, except that the last two edge slots hold each other's
+ * pieces when the corner permutation is odd: the cube is then reachable (rcc status 0) and rcc_cubies returns the index.  An index >= N
+ * cannot raise on the device: that cube is written solved and *bad (one device byte the caller zeroes and reads, required) is set. */
+int rcp_unrank(const uint32_t *index, int64_t n, int cube_size, uint8_t *cubies, int64_t cubie_pitch, uint8_t *bad, void *stream);
+
+/* dist[c] (uint8 [n_cubes]) = table[corner_index] of cube c of a tiled sticker buffer (pitch as rcc_cubies' st); 0xFF for a cube whose
+ * corners are not legal, for which nothing is read from the table. */
+int rcp_lookup(const uint8_t *st, int64_t n_cubes, int64_t pitch, int cube_size, const uint8_t *table, int64_t bytes, uint8_t *dist,
+               void *stream);
+
+/* scores[j] (float [A][NBp]) = -(float)table[corner_index] for EVERY slot j of rc_search_expand's key array at (n_problems, width,
+ * pitch), the index taken from the 3-bit stickers packed in the key.  A key that names no legal corner state -- the unwritten slots of
+ * dead problems hold arbitrary bits -- scores -255 and reads nothing from the table. */
+int rcp_score_keys(const uint64_t *keys, int64_t n_problems, int width, int64_t pitch, int cube_size, const uint8_t *table, int64_t bytes,
+                   float *scores, void *stream);
+
+/* Relax, the step the A* rule above leaves out; call it after rca_merge of the same iteration (same arguments), before `iteration`
+ * advances.  Per active problem, every candidate that is VALID and not RCA_NEW names a state the pool holds.  Where that node is OPEN
+ * and g(parent) + 1 of the candidate is below the node's g, the node takes the least such g, from the candidate with the lowest c among
+ * those that offer it: pool_g = that g, pool_parent = pop_node of the candidate's slot, pool_action = its action,
+ * pool_prio = pool_score - weight * g (two roundings, as in merge).  CLOSED nodes, the stickers, keys, scores and the table are not
+ * written.  With it, B = 1, weight = 1 and a consistent heuristic (the corner table) the search is A* proper: the first solved child
+ * ends an optimal solution.  search.astar_search runs it for front="table" only; the net fronts keep the rule above. */
+int rcp_relax(int64_t n_problems, int cube_size, int batch, int64_t pitch, int64_t capacity, float weight, const uint8_t *flags,
+              const uint64_t *keys, const int32_t *live, const uint8_t *active, const int32_t *pop_node, const uint64_t *pool_keys,
+              int32_t *pool_parent, uint8_t *pool_action, int32_t *pool_g, const float *pool_score, float *pool_prio,
+              const uint8_t *pool_state, const int32_t *count, const void *table, int64_t table_bytes, void *stream);
 
 #ifdef __cplusplus
 }

@@ -7,6 +7,8 @@ Drop-in surface for the env path of SUNGBEOMCHOI/Rubiks-Cube-Solver:
   get_env_config      (utils.py:162-186)
   CodeNet             the reference's DeepCube (model.py:7-45) evaluated from compact codes: no dense one-hot, HIP first layer
   ops                 batched operator layer (assets/py333.py:211-246)
+  CornerTable         exact distances of the corner states on the device (pattern.py): God's algorithm on the 2x2x2, the admissible corner
+                      bound on the 3x3x3; search.* take it with front="table"
   get_cubies, RCC_*   the cube as pieces: (piece, orientation) bytes, the legality status bits, perfect indices (ops.cubies / from_cubies)
   py333               the same operators under the reference's names, one cube per call
   py222               the six names cube_env.py:8 imports from the file the reference does not ship (2x2x2, one cube per call)
@@ -16,13 +18,13 @@ from .tables import (ACTION_NAMES, RCC_BAD_COLOUR, RCC_BAD_FIXED, RCC_BAD_PIECE,
                      RCC_TWIST, get_cubies, get_env_config, get_tables)
 
 __all__ = ["get_env_config", "get_tables", "get_cubies", "ACTION_NAMES", "RCC_BAD_COLOUR", "RCC_BAD_FIXED", "RCC_BAD_PIECE", "RCC_DUP_PIECE",
-           "RCC_TWIST", "RCC_FLIP", "RCC_PARITY", "RCC_NAMES", "ops", "make_env", "CubeEnv", "VecCubeEnv", "TensorReplayBuffer", "CodeNet"]
+           "RCC_TWIST", "RCC_FLIP", "RCC_PARITY", "RCC_NAMES", "ops", "make_env", "CubeEnv", "VecCubeEnv", "TensorReplayBuffer", "CodeNet", "CornerTable"]
 
 
 def __getattr__(name):  # torch-dependent parts load lazily
     import importlib
 
-    if name in ("ops", "_lib", "vec_env", "cube_env", "adi", "mcts_batched", "rollout", "dist", "py333", "py222", "replay", "search", "codenet"):
+    if name in ("ops", "_lib", "vec_env", "cube_env", "adi", "mcts_batched", "rollout", "dist", "py333", "py222", "replay", "search", "codenet", "pattern"):
         return importlib.import_module(f"{__name__}.{name}")
     if name == "VecCubeEnv":
         return importlib.import_module(f"{__name__}.vec_env").VecCubeEnv
@@ -30,6 +32,8 @@ def __getattr__(name):  # torch-dependent parts load lazily
         return importlib.import_module(f"{__name__}.replay").TensorReplayBuffer
     if name == "CodeNet":
         return importlib.import_module(f"{__name__}.codenet").CodeNet
+    if name == "CornerTable":
+        return importlib.import_module(f"{__name__}.pattern").CornerTable
     if name in ("CubeEnv", "make_env"):
         return getattr(importlib.import_module(f"{__name__}.cube_env"), name)
     raise AttributeError(name)

@@ -1115,4 +1115,148 @@ __device__ __forceinline__ Pk<V> stickers_of(const Pk<V> (&code)[T::SLOTS], Pk<V
     return bad;
 }
 
+// ------------------------------------------------------------------------ corner coordinates
+// include/rubiksearch.h "Corner pattern database" (rcp_*).  Two forms of one corner state:
+//   packed   Corners: piece / ori / Lehmer digit of every corner slot, one cube per byte, read out of sticker colours (corners_of);
+//   scalar   CornerCoord: one cube, nibble q of `piece` / `ori` = slot q -- what the index space is walked in (corner_unrank, corner_move,
+//            corner_rank): a move is a compile-time shuffle of nibbles, rank and unrank are NC steps on a bit set / nibble list.
+template <class T>
+struct CornerSpace {
+    static constexpr uint32_t POW3 = T::NC == 8 ? 2187u : 729u;          // 3^(NC - 1)
+    static constexpr uint32_t FACT = T::NC == 8 ? 40320u : 5040u;        // NC!
+    static constexpr uint32_t N = FACT * POW3;                           // 88 179 840 | 3 674 160
+};
+
+template <class T, int V>
+struct Corners {
+    Pk<V> ori[T::NC];      // 0 where the slot names no piece
+    Pk<V> lt[T::NC];       // #{r > q : piece[r] < piece[q]}
+    Pk<V> bad;             // 0xff in the bytes of the cubes whose corners are no legal corner state
+};
+
+// The corner half of cubies_of, and nothing else: cc[q][k] = the colour at rc_tables.h ccw[q][k] (any byte), `fixed` = non-zero in
+// the bytes of the cubes whose 2x2x2 DLB stickers differ from solved (0 on the 3x3x3).  It exists beside cubies_of because the table
+// look-ups need 24 of the 54 sticker rows of a 3x3x3 and none of the 66 edge-pair compares: reading the full 20-slot form would load
+// 2.25 x the bytes and spend most of its instructions on edges, whose troubles are not the corner state's.  (cubies_of itself stays as
+// it is: librubikhip's kernels are built from it.)  bad <=> RCC_BAD_COLOUR on a corner (or 2x2x2 fixed) sticker, RCC_BAD_FIXED (2x2x2),
+// a corner slot that reads 0xFF, a repeated corner piece, or RCC_TWIST.
+template <class T, int V>
+__device__ __forceinline__ void corners_of(Pk<V> (&cc)[T::NC][3], Pk<V> fixed, Corners<T, V> &c) {
+    Pk<V> piece[T::NC];
+    Pk<V> trouble = fixed;                                                // any bit: illegal
+    sfor<T::NC>([&](auto qc) {
+        constexpr int q = decltype(qc)::value;
+        sfor<3>([&](auto kc) { cc[q][decltype(kc)::value] = clean_colour(cc[q][decltype(kc)::value]); });
+        const RowMasks<V> m = row_masks(cc[q][1]);
+        const Pk<V> pc = lut_exact<T, V, 0>(cc[q][0], m);                 // piece * 4 + ori, 0xff: no cubie shows (c0, c1)
+        const Pk<V> third = lut_exact<T, V, 1>(cc[q][0], m);
+        const Pk<V> no = signmask(nonzero7(third ^ cc[q][2]) | pc);       // a mirror image, a colour above 5, or 0xff
+        Pk<V> pp;
+        RC_V pp.d[k] = (pc.d[k] >> 2) & 0x3f3f3f3fu;
+        piece[q] = sel(no, splat<V>((uint32_t)(0x40 + q) * 0x01010101u), pp);
+        c.ori[q] = andn(pc & 0x03030303u, no);
+        trouble = trouble | no;
+    });
+    Pk<V> twice = splat<V>(0);
+    sfor<T::NC>([&](auto qc) {
+        constexpr int q = decltype(qc)::value;
+        Pk<V> cnt = splat<V>(0);
+        sfor<T::NC - q - 1>([&](auto rc) {
+            constexpr int r = q + 1 + decltype(rc)::value;
+            RC_V {
+                const uint32_t ge = (piece[q].d[k] | 0x80808080u) - piece[r].d[k];   // bit 7: piece[q] >= piece[r] (cubies_of)
+                const uint32_t le = (piece[r].d[k] | 0x80808080u) - piece[q].d[k];
+                twice.d[k] |= ge & le;
+                cnt.d[k] += (~le >> 7) & 0x01010101u;
+            }
+        });
+        c.lt[q] = cnt;
+    });
+    Pk<V> twist = splat<V>(0);
+    sfor<T::NC>([&](auto qc) { RC_V twist.d[k] += c.ori[decltype(qc)::value].d[k]; });
+    RC_V twist.d[k] = (twist.d[k] & 0x03030303u) + ((twist.d[k] >> 2) & 0x07070707u);    // 4 = 1 mod 3; at most 16 -> at most 7
+    twist = perm<V>(0x10001010u, 0x00101000u, twist);                     // non-zero where the sum is not 0, 3 or 6
+    c.bad = signmask(nonzero7(trouble | (twice & 0x80808080u) | twist));
+}
+
+// corner_index of cube J of a pack (include/rubikhip.h "Cubie coordinates"), all-ones where the cube's corners are not legal
+template <class T, int V, int J>
+__device__ __forceinline__ uint32_t corner_index_of(const Corners<T, V> &c) {
+    constexpr int w = J >> 2, sft = 8 * (J & 3);
+    const auto byte = [&](const Pk<V> &p) { return (p.d[w] >> sft) & 0xffu; };
+    uint32_t lehmer = 0, oris = 0;
+    sfor<T::NC>([&](auto qc) {
+        constexpr int q = decltype(qc)::value;
+        lehmer = lehmer * (uint32_t)(T::NC - q) + byte(c.lt[q]);
+    });
+    sfor<T::NC - 1>([&](auto qc) {
+        constexpr int q = T::NC - 2 - decltype(qc)::value;
+        oris = oris * 3u + byte(c.ori[q]);
+    });
+    return byte(c.bad) ? 0xffffffffu : lehmer * CornerSpace<T>::POW3 + oris;
+}
+
+struct CornerCoord {
+    uint32_t piece, ori;   // nibble q: the piece in corner slot q, its orientation
+};
+
+// idx < CornerSpace<T>::N (the caller checks)
+template <class T>
+__device__ __forceinline__ CornerCoord corner_unrank(uint32_t idx) {
+    uint32_t lehmer = idx / CornerSpace<T>::POW3, o = idx - lehmer * CornerSpace<T>::POW3, sum = 0;
+    CornerCoord c{0u, 0u};
+    sfor<T::NC - 1>([&](auto qc) {
+        constexpr int q = decltype(qc)::value;
+        const uint32_t d = o % 3u;
+        o /= 3u;
+        c.ori |= d << (4 * q);
+        sum += d;
+    });
+    c.ori |= ((3u - sum % 3u) % 3u) << (4 * (T::NC - 1));                 // the last corner closes the twist
+    uint32_t dig[T::NC];
+    sfor<T::NC>([&](auto qc) {                                           // lehmer = sum_q dig[q] * (NC - 1 - q)!
+        constexpr int q = T::NC - 1 - decltype(qc)::value;
+        dig[q] = lehmer % (uint32_t)(T::NC - q);
+        lehmer /= (uint32_t)(T::NC - q);
+    });
+    uint32_t list = T::NC == 8 ? 0x76543210u : 0x06543210u;              // the unused pieces, ascending from nibble 0
+    sfor<T::NC>([&](auto qc) {
+        constexpr int q = decltype(qc)::value;
+        const uint32_t sh = 4u * dig[q], low = (1u << sh) - 1u;           // dig[q] <= 7: sh <= 28
+        c.piece |= ((list >> sh) & 15u) << (4 * q);
+        list = (list & low) | ((list >> 4) & ~low);
+    });
+    return c;
+}
+
+template <class T>
+__device__ __forceinline__ uint32_t corner_rank(CornerCoord c) {
+    uint32_t unused = (1u << T::NC) - 1u, lehmer = 0, oris = 0;
+    sfor<T::NC>([&](auto qc) {
+        constexpr int q = decltype(qc)::value;
+        const uint32_t p = (c.piece >> (4 * q)) & 15u;
+        lehmer = lehmer * (uint32_t)(T::NC - q) + (uint32_t)__popc(unused & ((1u << p) - 1u));
+        unused &= ~(1u << p);
+    });
+    sfor<T::NC - 1>([&](auto qc) {
+        constexpr int q = T::NC - 2 - decltype(qc)::value;
+        oris = oris * 3u + ((c.ori >> (4 * q)) & 3u);
+    });
+    return lehmer * CornerSpace<T>::POW3 + oris;
+}
+
+// move A_ (rc_tables.h cmove_src / cmove_twist): piece'[q] = piece[src], ori'[q] = (ori[src] + twist) mod 3
+template <class T, int A_>
+__device__ __forceinline__ CornerCoord corner_move(CornerCoord c) {
+    CornerCoord r{0u, 0u};
+    sfor<T::NC>([&](auto qc) {
+        constexpr int q = decltype(qc)::value;
+        constexpr int src = T::cmove_src[A_][q], tw = T::cmove_twist[A_][q];
+        r.piece |= ((c.piece >> (4 * src)) & 15u) << (4 * q);
+        const uint32_t o = ((c.ori >> (4 * src)) & 3u) + (uint32_t)tw;
+        r.ori |= (o >= 3u ? o - 3u : o) << (4 * q);
+    });
+    return r;
+}
+
 }  // namespace rc

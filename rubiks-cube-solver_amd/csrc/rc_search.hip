@@ -1026,5 +1026,407 @@ int rca_backtrack(int64_t n, int cube_size, int64_t capacity, const int32_t *poo
     });
 }
 
+// =========================================================================================== corner pattern database
+// The rcp_* entry points (include/rubiksearch.h "Corner pattern database", DESIGN.md "Corner pattern database"), on rc_device.h's
+// corner coordinates (corners_of / corner_index_of: stickers -> index; corner_unrank / corner_move / corner_rank: the index space).
+//
+//   k_pdb_level    one lane per table entry, PULL: an entry that is still 0xFF unranks itself, ranks its A neighbours and becomes
+//                  depth + 1 iff one of them holds `depth`.  A lane writes its own entry only; a neighbour another lane is writing
+//                  meanwhile reads 0xFF or depth + 1, neither of which is `depth`: the table after a level does not depend on timing
+//   k_pdb_unrank   index -> cubie rows, 4 cubes per lane (one dword per row; the ragged last pack byte by byte)
+//   k_pdb_lookup   the 24 corner sticker rows (+ the 3 fixed ones of the 2x2x2) -> dist, 4 cubes per lane
+//   k_pdb_score    4 consecutive key slots per lane -> their corner stickers as packed bytes -> scores
+// THE GUARD.  Every table address of these kernels is formed in table_at() below and nowhere else: it compares the index with the
+// compile-time table size N (the host has checked bytes >= N) before the load.  corner_index_of gives all-ones for an illegal corner
+// state, which fails that test like any other index >= N; the build's neighbour indices pass through it too.
+namespace {
+
+template <class T>
+__device__ __forceinline__ uint32_t table_at(const uint8_t *table, uint32_t idx) {
+    return idx < CornerSpace<T>::N ? (uint32_t)table[idx] : 0xFFu;       // THE GUARD: no load for an index outside the table
+}
+
+template <class T>
+__global__ void __launch_bounds__(256) k_pdb_level(uint8_t *table, uint32_t depth, uint32_t *count) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    bool set = false;
+    if (table_at<T>(table, i) == 0xFFu && i < CornerSpace<T>::N) {       // past N table_at reads nothing and says 0xFF
+        const CornerCoord c = corner_unrank<T>(i);
+        sfor<T::A>([&](auto ac) {
+            constexpr int A_ = decltype(ac)::value;
+            if (!set) set = table_at<T>(table, corner_rank<T>(corner_move<T, A_>(c))) == depth;
+        });
+        if (set) table[i] = (uint8_t)(depth + 1u);                       // the lane's own entry
+    }
+    const unsigned long long bal = __ballot(set);
+    if ((threadIdx.x & 63) == 0 && bal) atomicAdd(count, (uint32_t)__popcll(bal));
+}
+
+struct UnrankArgs {
+    const uint32_t *index;
+    int64_t n;
+    uint8_t *cubies;
+    int64_t pitch;
+    int sh;
+    uint8_t *bad;
+};
+
+template <class T>
+__global__ void __launch_bounds__(256) k_pdb_unrank(UnrankArgs a) {
+    const int64_t n0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
+    if (n0 >= a.n) return;
+    const bool full = n0 + 4 <= a.n;
+    uint32_t idx[4] = {0u, 0u, 0u, 0u};
+    if (full) {
+        const u32x4 u = *reinterpret_cast<const u32x4 *>(a.index + n0);
+        idx[0] = u[0]; idx[1] = u[1]; idx[2] = u[2]; idx[3] = u[3];
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (n0 + j < a.n) idx[j] = a.index[n0 + j];
+    }
+    uint32_t row[T::SLOTS] = {};
+    bool bad = false;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const bool ok = idx[j] < CornerSpace<T>::N;
+        bad = bad || !ok;
+        const uint32_t ix = ok ? idx[j] : 0u;                             // out of range: the solved cube
+        const CornerCoord c = corner_unrank<T>(ix);
+        sfor<T::NC>([&](auto qc) {
+            constexpr int q = decltype(qc)::value;
+            row[q] |= (((c.piece >> (4 * q)) & 15u) * 3u + ((c.ori >> (4 * q)) & 3u)) << (8 * j);
+        });
+        if constexpr (T::NE > 0) {
+            // the permutation's parity = the parity of its inversion count = that of the sum of the Lehmer digits
+            uint32_t lehmer = ix / CornerSpace<T>::POW3, odd = 0;
+            sfor<T::NC>([&](auto qc) {
+                constexpr uint32_t radix = 1 + decltype(qc)::value;
+                odd ^= lehmer % radix;
+                lehmer /= radix;
+            });
+            odd &= 1u;
+            sfor<T::NE>([&](auto ec) {
+                constexpr int e = decltype(ec)::value;
+                // an odd corner permutation needs an odd edge permutation: the last two edges trade places
+                const uint32_t piece = e >= T::NE - 2 ? (uint32_t)e ^ (odd & (uint32_t)(((T::NE - 2) ^ (T::NE - 1)))) : (uint32_t)e;
+                row[T::NC + e] |= (2u * piece) << (8 * j);
+            });
+        }
+    }
+    if (bad) *a.bad = 1;                                                  // every writer stores the same byte
+    uint8_t *dst = a.cubies + (a.sh >= 63 ? n0 : tiled(n0, a.pitch, a.sh, T::SLOTS));   // n0 % 4 == 0, pitch % 16 == 0: one tile, dword aligned
+    if (full) {
+#pragma unroll
+        for (int q = 0; q < T::SLOTS; ++q) *reinterpret_cast<uint32_t *>(dst + (int64_t)q * a.pitch) = row[q];
+    } else {
+#pragma unroll
+        for (int q = 0; q < T::SLOTS; ++q)
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (n0 + j < a.n) dst[(int64_t)q * a.pitch + j] = (uint8_t)(row[q] >> (8 * j));   // pad columns keep their bytes
+    }
+}
+
+// the 4 distances of a pack as bytes
+template <class T>
+__device__ __forceinline__ void pack_distances(const Corners<T, 1> &c, const uint8_t *table, uint32_t (&d)[4]) {
+    sfor<4>([&](auto jc) {
+        constexpr int j = decltype(jc)::value;
+        d[j] = table_at<T>(table, corner_index_of<T, 1, j>(c));
+    });
+}
+
+struct LookupArgs {
+    const uint8_t *st;
+    int64_t n, pitch;
+    int sh;
+    const uint8_t *table;
+    uint8_t *dist;
+};
+
+template <class T>
+__global__ void __launch_bounds__(kWave) k_pdb_lookup(LookupArgs a) {
+    const int64_t g0 = (int64_t)blockIdx.x * kSpan;
+    const uint32_t lo = threadIdx.x * 4;
+    const int64_t n0 = g0 + lo;
+    if (n0 >= a.n) return;
+    const __amdgpu_buffer_rsrc_t r = make_srd(a.st + tile_off(g0, a.pitch, a.sh, T::S));
+    const uint32_t rs = (uint32_t)a.pitch;
+    Pk<1> cc[T::NC][3], fixed = splat<1>(0);
+    sfor<T::NC>([&](auto qc) {
+        constexpr int q = decltype(qc)::value;
+        sfor<3>([&](auto kc) {
+            constexpr int k = decltype(kc)::value;
+            cc[q][k] = bld<1, kAuxCached>(r, lo, (uint32_t)T::ccw[q][k] * rs);
+        });
+    });
+    if constexpr (T::SIZE == 2)
+        sfor<T::NFIX>([&](auto fc) {
+            constexpr int i = T::fixed[decltype(fc)::value];
+            fixed = fixed | (bld<1, kAuxCached>(r, lo, (uint32_t)i * rs) ^ solved_row<T, 1>(i));
+        });
+    Corners<T, 1> c;
+    corners_of<T, 1>(cc, fixed, c);
+    uint32_t d[4];
+    pack_distances<T>(c, a.table, d);
+    Pk<1> out;
+    out.d[0] = d[0] | (d[1] << 8) | (d[2] << 16) | (d[3] << 24);
+    st_tail<1>(a.dist, n0, a.n, out);
+}
+
+// where sticker i sits in a key: Key<T>::sticker's inverse (i is no centre)
+template <class T>
+constexpr int key_pos(int i) { return T::SIZE == 3 ? (i / 9) * 8 + (i % 9 < 4 ? i % 9 : i % 9 - 1) : i; }
+
+template <class T>
+__global__ void __launch_bounds__(256) k_pdb_score(const uint64_t *keys, int64_t total, const uint8_t *table, float *scores) {
+    using K = Key<T>;
+    const int64_t j0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;     // total % 4 == 0: a pack is whole or absent
+    if (j0 >= total) return;
+    uint64_t w[K::KW][4];
+#pragma unroll
+    for (int x = 0; x < K::KW; ++x)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) w[x][j] = keys[(int64_t)x * total + j0 + j];
+    const auto colour = [&](auto ic) {                                    // sticker i of the 4 slots as packed bytes
+        constexpr int kk = key_pos<T>(decltype(ic)::value);
+        static_assert(K::sticker(kk) == decltype(ic)::value);
+        Pk<1> p;
+        p.d[0] = 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) p.d[0] |= (uint32_t)((w[kk / 16][j] >> (3 * (kk % 16))) & 7u) << (8 * j);
+        return p;
+    };
+    Pk<1> cc[T::NC][3], fixed = splat<1>(0);
+    sfor<T::NC>([&](auto qc) {
+        constexpr int q = decltype(qc)::value;
+        sfor<3>([&](auto kc) {
+            constexpr int k = decltype(kc)::value;
+            cc[q][k] = colour(std::integral_constant<int, T::ccw[q][k]>{});
+        });
+    });
+    if constexpr (T::SIZE == 2)
+        sfor<T::NFIX>([&](auto fc) {
+            constexpr int i = T::fixed[decltype(fc)::value];
+            fixed = fixed | (colour(std::integral_constant<int, i>{}) ^ solved_row<T, 1>(i));
+        });
+    Corners<T, 1> c;
+    corners_of<T, 1>(cc, fixed, c);
+    uint32_t d[4];
+    pack_distances<T>(c, table, d);
+    typedef float f32x4 __attribute__((ext_vector_type(4)));
+    const f32x4 s = {-(float)d[0], -(float)d[1], -(float)d[2], -(float)d[3]};
+    *reinterpret_cast<f32x4 *>(scores + j0) = s;
+}
+
+// ---- rcp_relax: the step the A* rule leaves out, for an admissible table.  After rca_merge of an iteration, a VALID candidate that
+// is not NEW names a state the pool knows.  If that node is still OPEN and the candidate reaches it by fewer moves, the node takes
+// the candidate's g, parent, action and the prio that follows.  One workgroup per problem, three phases over the candidates
+// c = tid + 256 r, each ending on a barrier, so that the winner among several candidates for one node is (least g, then least c) by
+// rule: A lowers pool_g with atomicMin and marks the node (parent = INT_MIN, the same store from every writer); B: the candidates
+// whose g the node now holds bid -(c + 2) into the marked parent with atomicMax; C: the one whose bid stands writes the node.
+// Only this problem's workgroup touches this problem's nodes, and nothing inserts into the table meanwhile: it is read-only here.
+struct RelaxArgs {
+    Cands s;                      // flags, keys, live, active, nbp, width; the rest unused
+    Pool o;                       // keys, parent, action, g, score, prio, state, count, table; the rest unused
+    const int32_t *pop_node;
+    float weight;
+};
+
+template <class T>
+__global__ void __launch_bounds__(kSelThreads) k_pdb_relax(RelaxArgs a) {
+    using K = Key<T>;
+    const Cands &s = a.s;
+    const Pool &o = a.o;
+    const int64_t p = blockIdx.x;
+    const int tid = threadIdx.x;
+    if (!s.active[p]) return;                                  // ended in this iteration's pop or merge: nothing to improve
+    const int64_t g0 = p * o.cap;
+    const uint32_t M = (uint32_t)min(max(s.live[p], 0), s.width) * T::A;
+    const int32_t count = min(max(o.count[p], 1), o.cap);
+    constexpr int32_t kMark = INT32_MIN;
+    // the OPEN node of this problem that holds candidate c's key and the g the candidate offers; -1: none, or nothing to gain
+    const auto target = [&](uint32_t c, int32_t &newg) -> int64_t {
+        const int64_t j = cand_j<T>(s, p, c);
+        const uint8_t f = s.flags[j];
+        if (!(f & RC_SEARCH_VALID) || (f & RCA_NEW)) return -1;
+        const int32_t par = min(max(a.pop_node[p * s.width + c / T::A], 0), count - 1);
+        newg = o.g[g0 + par] + 1;                              // the parent is CLOSED: its g does not move
+        uint64_t k[K::KW];
+        load_key<T>(s, j, k);
+        for (uint64_t h = slot_of<T>(k, p, o.tmask);; h = (h + 1) & o.tmask) {
+            const uint64_t v = o.table[h];
+            if (v == kEmpty) return -1;
+            if ((int64_t)v >= g0 && (int64_t)v < g0 + count && node_has_key<T>(o, (int64_t)v, k)) return o.state[v] == kOpen ? (int64_t)v : -1;
+        }
+    };
+    for (uint32_t c = tid; c < M; c += kSelThreads) {          // A
+        int32_t newg;
+        const int64_t v = target(c, newg);
+        if (v >= 0 && atomicMin(&o.g[v], newg) > newg) o.parent[v] = kMark;
+    }
+    __syncthreads();
+    for (uint32_t c = tid; c < M; c += kSelThreads) {          // B
+        int32_t newg;
+        const int64_t v = target(c, newg);
+        if (v >= 0 && o.g[v] == newg && o.parent[v] < -1) atomicMax(&o.parent[v], -(int32_t)c - 2);
+    }
+    __syncthreads();
+    for (uint32_t c = tid; c < M; c += kSelThreads) {          // C
+        int32_t newg;
+        const int64_t v = target(c, newg);
+        if (v < 0 || o.parent[v] != -(int32_t)c - 2) continue;
+        o.parent[v] = min(max(a.pop_node[p * s.width + c / T::A], 0), count - 1);
+        o.action[v] = (uint8_t)(c % T::A);
+        o.prio[v] = __fsub_rn(o.score[v], __fmul_rn(a.weight, (float)newg));
+    }
+}
+
+// a table operand: present, 16-byte aligned, and large enough for every index below N
+template <class T>
+int table_arg(const char *fn, const void *table, int64_t bytes) {
+    if (!table || !aligned16(table)) return fail(fn, "table is NULL or not 16-byte aligned");
+    if (bytes < (int64_t)CornerSpace<T>::N) return fail(fn, "bytes is smaller than rcp_table_bytes()");
+    return 0;
+}
+
+}  // namespace
+
+int64_t rcp_table_bytes(int cube_size) {
+    return cube_size == 3 ? (int64_t)CornerSpace<Cube3>::N : cube_size == 2 ? (int64_t)CornerSpace<Cube2>::N : -1;
+}
+
+int rcp_tables(int cube_size, uint8_t *src, uint8_t *twist) {
+    return by_size(cube_size, [&](auto t) {
+        using T = decltype(t);
+        if (src) memcpy(src, T::cmove_src, (size_t)T::A * T::NC);
+        if (twist) memcpy(twist, T::cmove_twist, (size_t)T::A * T::NC);
+        return 0;
+    });
+}
+
+int rcp_build_begin(uint8_t *table, int64_t bytes, int cube_size, void *stream) {
+    return by_size(cube_size, [&](auto t) {
+        using T = decltype(t);
+        if (int rc = table_arg<T>("rcp_build_begin", table, bytes)) return rc;
+        RC_HIP(-2, hipMemsetAsync(table, 0xFF, (size_t)CornerSpace<T>::N, S(stream)));
+        RC_HIP(-2, hipMemsetAsync(table, 0, 1, S(stream)));              // corner_index(solved) = 0
+        return 0;
+    });
+}
+
+int rcp_build_level(uint8_t *table, int64_t bytes, int cube_size, int depth, uint32_t *count, void *stream) {
+    return by_size(cube_size, [&](auto t) {
+        using T = decltype(t);
+        if (int rc = table_arg<T>("rcp_build_level", table, bytes)) return rc;
+        if (depth < 0 || depth >= 254) return fail("rcp_build_level: depth must be in 0..253");
+        if (!count || !aligned16(count)) return fail("rcp_build_level: count is NULL or not 16-byte aligned");
+        RC_HIP(-2, hipMemsetAsync(count, 0, 4, S(stream)));
+        hipLaunchKernelGGL((k_pdb_level<T>), dim3((CornerSpace<T>::N + 255u) / 256u), dim3(256), 0, S(stream), table, (uint32_t)depth, count);
+        RC_HIP(-2, hipGetLastError());
+        return 0;
+    });
+}
+
+int rcp_unrank(const uint32_t *index, int64_t n, int cube_size, uint8_t *cubies, int64_t cubie_pitch, uint8_t *bad, void *stream) {
+    return by_size(cube_size, [&](auto t) {
+        using T = decltype(t);
+        if (n < 0) return fail("rcp_unrank: n is negative");
+        if (!index || !aligned16(index)) return fail("rcp_unrank: index is NULL or not 16-byte aligned");
+        if (!cubies || !aligned16(cubies)) return fail("rcp_unrank: cubies is NULL or not 16-byte aligned");
+        const int sh = tile_shift(cubie_pitch, n, T::SLOTS);
+        if (sh < 0) return fail("rcp_unrank: cubie_pitch: need pitch % 16 == 0 and pitch >= n, or a power-of-two tile >= 512");
+        if (!bad) return fail("rcp_unrank: bad is NULL");
+        if (n == 0) return 0;
+        const int64_t blocks = ceil_div(n, 1024);
+        if (!grid_ok(blocks)) return fail("rcp_unrank: too many cubes for one launch");
+        const UnrankArgs a{index, n, cubies, cubie_pitch, sh, bad};
+        hipLaunchKernelGGL((k_pdb_unrank<T>), dim3((unsigned)blocks), dim3(256), 0, S(stream), a);
+        RC_HIP(-2, hipGetLastError());
+        return 0;
+    });
+}
+
+int rcp_lookup(const uint8_t *stp, int64_t n, int64_t pitch, int cube_size, const uint8_t *table, int64_t bytes, uint8_t *dist,
+               void *stream) {
+    return by_size(cube_size, [&](auto t) {
+        using T = decltype(t);
+        if (n < 0) return fail("rcp_lookup: n_cubes is negative");
+        if (!stp || !aligned16(stp)) return fail("rcp_lookup: st is NULL or not 16-byte aligned");
+        const int sh = tile_shift(pitch, n, T::S);
+        if (sh < 0) return fail("rcp_lookup: pitch: need pitch % 16 == 0 and pitch >= n_cubes, or a power-of-two tile >= 512");
+        if (int rc = table_arg<T>("rcp_lookup", table, bytes)) return rc;
+        if (!dist || !aligned16(dist)) return fail("rcp_lookup: dist is NULL or not 16-byte aligned");
+        if (n == 0) return 0;
+        const int64_t blocks = ceil_div(n, kSpan);
+        if (!grid_ok(blocks)) return fail("rcp_lookup: too many cubes for one launch");
+        const LookupArgs a{stp, n, pitch, sh, table, dist};
+        hipLaunchKernelGGL((k_pdb_lookup<T>), dim3((unsigned)blocks), dim3(kWave), 0, S(stream), a);
+        RC_HIP(-2, hipGetLastError());
+        return 0;
+    });
+}
+
+int rcp_score_keys(const uint64_t *keys, int64_t n, int width, int64_t pitch, int cube_size, const uint8_t *table, int64_t bytes,
+                   float *scores, void *stream) {
+    return by_size(cube_size, [&](auto t) {
+        using T = decltype(t);
+        Geo g;
+        if (int rc = geometry<T>(n, width, pitch, g)) return rc;
+        if (!keys || !aligned16(keys)) return fail("rcp_score_keys: keys is NULL or not 16-byte aligned");
+        if (int rc = table_arg<T>("rcp_score_keys", table, bytes)) return rc;
+        if (!scores || !aligned16(scores)) return fail("rcp_score_keys: scores is NULL or not 16-byte aligned");
+        const int64_t total = (int64_t)T::A * g.nbp;                       // a multiple of 512
+        hipLaunchKernelGGL((k_pdb_score<T>), dim3((unsigned)ceil_div(total, 1024)), dim3(256), 0, S(stream), keys, total, table, scores);
+        RC_HIP(-2, hipGetLastError());
+        return 0;
+    });
+}
+
+int rcp_relax(int64_t n, int cube_size, int batch, int64_t pitch, int64_t capacity, float weight, const uint8_t *flags, const uint64_t *keys,
+              const int32_t *live, const uint8_t *active, const int32_t *pop_node, const uint64_t *pool_keys, int32_t *pool_parent,
+              uint8_t *pool_action, int32_t *pool_g, const float *pool_score, float *pool_prio, const uint8_t *pool_state, const int32_t *count,
+              const void *table, int64_t table_bytes, void *stream) {
+    return by_size(cube_size, [&](auto t) {
+        using T = decltype(t);
+        Geo g;
+        if (int rc = geometry<T>(n, batch, pitch, g)) return rc;
+        if (!pool_limits(n, capacity)) return fail(kPoolLimits);
+        if (!(weight >= 0.0f) || weight > 3.0e38f) return fail("rcp_relax: weight must be finite and >= 0");
+        if (any_null(flags, keys, live, active, pop_node, pool_keys, pool_parent, pool_action, pool_g, pool_score, pool_prio, pool_state, count, table))
+            return fail("rcp_relax: null buffer");
+        if (!all_aligned16(flags, keys, live, active, pop_node, pool_keys, pool_parent, pool_action, pool_g, pool_score, pool_prio, pool_state, count,
+                           table))
+            return fail("rcp_relax: buffers must be 16-byte aligned");
+        const int64_t slots = pow2_slots(2 * n * capacity);
+        if (table_bytes < slots * 8) return fail("rcp_relax: table smaller than rca_workspace_bytes()");
+        RelaxArgs a{};
+        a.s.flags = const_cast<uint8_t *>(flags);              // read only here
+        a.s.keys = keys;
+        a.s.live = live;
+        a.s.active = const_cast<uint8_t *>(active);
+        a.s.nbp = g.nbp;
+        a.s.width = batch;
+        a.o.keys = const_cast<uint64_t *>(pool_keys);
+        a.o.parent = pool_parent;
+        a.o.action = pool_action;
+        a.o.g = pool_g;
+        a.o.score = const_cast<float *>(pool_score);
+        a.o.prio = pool_prio;
+        a.o.state = const_cast<uint8_t *>(pool_state);
+        a.o.count = const_cast<int32_t *>(count);
+        a.o.table = static_cast<unsigned long long *>(const_cast<void *>(table));
+        a.o.tmask = (uint64_t)(slots - 1);
+        a.o.np = n * capacity;
+        a.o.cap = (int32_t)capacity;
+        a.pop_node = pop_node;
+        a.weight = weight;
+        hipLaunchKernelGGL((k_pdb_relax<T>), dim3((unsigned)n), dim3(kSelThreads), 0, S(stream), a);
+        RC_HIP(-2, hipGetLastError());
+        return 0;
+    });
+}
+
 // the cube symmetries (include/rubiksym.h): the rcs_* entry points of this library
 #include "rc_sym.h"

@@ -10,6 +10,9 @@ The solutions are read back from the history by rc_search_backtrack at the end.
 
 front="codes" (opt-in; DESIGN.md "Net front") replaces the second line: rc_net_first_layer sums the first layer's rows straight from
 the candidate codes into a [chunk, H1] buffer, and the rest of the encoder and the value head run on that; no dense one-hot exists.
+front="table" (DESIGN.md "Corner pattern database") replaces it by ONE launch and no net: the `model` is a pattern.CornerTable and
+rcp_score_keys writes scores = -table[corner index] from the candidate keys.  In astar_search it also adds rcp_relax after rca_merge (an
+open node reached again by fewer moves takes the lower g): with batch = 1 and weight = 1 the table-guided search is A* proper.
 
 astar_search / AStarPlan (DESIGN.md "A* search"): batch-weighted A* around the same expand and score.  Per cube a persistent node pool
 with an exact hash set; an iteration is rca_pop (the B best open nodes -> the beam), rc_search_expand, the score above, rca_merge (the
@@ -25,6 +28,7 @@ from ._search_lib import check
 from .tables import get_env_config
 
 MAX_WIDTH = 65536
+FRONTS = ("dense", "codes", "table")
 KEY_WORDS = {3: 3, 2: 2}
 
 
@@ -44,9 +48,9 @@ class BeamPlan:
     def __init__(self, n_problems, cube_size, width, max_depth, device, dtype=torch.float32, dense_budget_bytes=1 << 30, front="dense",
                  hidden=None):
         """front="codes": `hidden` = H1, the width of the net's first layer; the plan then holds a [chunk, H1] buffer of `dtype` instead of
-        the dense one-hot, sized by the same dense_budget_bytes rule."""
-        if front not in ("dense", "codes"):
-            raise ValueError(f"front must be 'dense' or 'codes', got {front!r}")
+        the dense one-hot, sized by the same dense_budget_bytes rule.  front="table": neither buffer exists; score() takes a CornerTable."""
+        if front not in FRONTS:
+            raise ValueError(f"front must be 'dense', 'codes' or 'table', got {front!r}")
         if front == "codes" and (hidden is None or dtype not in (torch.float32, torch.bfloat16)):
             raise ValueError("front='codes' needs hidden = the first layer's width and a float32 or bfloat16 model "
                              f"(the kernel takes no other format), got hidden = {hidden}, dtype = {dtype}")
@@ -80,8 +84,11 @@ class BeamPlan:
         L = _search_lib.search_lib()
         self.workspace = torch.empty(int(L.rc_search_workspace_bytes(self.cs, self.P, self.W)), dtype=torch.uint8, device=dev)
         self.dtype = dtype
-        row_bytes = (self.R * self.C if front == "dense" else int(hidden)) * torch.empty((), dtype=dtype).element_size()
         total = A * nbp
+        if front == "table":
+            self.chunk = total
+            return
+        row_bytes = (self.R * self.C if front == "dense" else int(hidden)) * torch.empty((), dtype=dtype).element_size()
         self.chunk = min(total, max(self.pitch, int(dense_budget_bytes) // row_bytes // self.pitch * self.pitch))
         if front == "dense":
             self.dense = torch.empty((self.chunk, self.R, self.C), dtype=dtype, device=dev)
@@ -106,6 +113,8 @@ class BeamPlan:
         """scores = model(dense one-hot)[0][:, 0] for every candidate, one forward per chunk (chunks start on tile boundaries)."""
         if self.front == "codes":
             return self.score_codes(model)
+        if self.front == "table":
+            return self.score_table(model)
         total, flat = self.A * self.nbp, self.scores.view(-1)
         for j0 in range(0, total, self.chunk):
             m = min(self.chunk, total - j0)
@@ -139,6 +148,11 @@ class BeamPlan:
             t0 = j0 // self.pitch
             flat[j0:j0 + m].copy_(net.value_codes(self.code[t0:t0 + m // self.pitch], m, out=self.hidden)[:, 0])
 
+    def score_table(self, table):
+        """scores = -table[corner index] of every candidate KEY: one rcp_score_keys launch over all A * NBp slots, no net."""
+        _check_table(table, self.cs, self.keys.device)
+        table.score_keys(self.keys, self.P, self.W, self.pitch, self.scores)
+
     def select(self):
         check(_search_lib.search_lib().rc_search_select(ptr(self.flags), ptr(self.keys), ptr(self.scores), self.P, self.W, self.pitch, self.cs,
                                                         ptr(self.live), ptr(self.active), ptr(self.length), ptr(self.solution), ptr(self.depth),
@@ -165,11 +179,29 @@ class BeamPlan:
         self.depth.add_(1)
 
 
+def _check_table(table, cube_size, device=None):
+    """front="table": the ValueErrors of a `model` that is no CornerTable of this cube size on this device (before any launch; the
+    device is looked at last, and only where one is given)."""
+    from .pattern import CornerTable
+    if not isinstance(table, CornerTable):
+        raise ValueError(f"front='table' scores with a pattern.CornerTable in the model position, got {type(table).__name__}")
+    if table.cube_size != cube_size:
+        raise ValueError(f"front='table': the table is a {table.cube_size}x{table.cube_size}x{table.cube_size}'s, the cubes are "
+                         f"{cube_size}x{cube_size}x{cube_size}")
+    if device is not None and table.device != device:
+        raise ValueError(f"front='table': the table is on {table.device}, the cubes on {device}")
+
+
 def _net_front(model, front, env):
-    """(model, dtype, hidden) a plan scores the cubes of `env` with: for front="codes" the model's CodeNet and its H1."""
+    """(model, dtype, hidden) a plan scores the cubes of `env` with: for front="codes" the model's CodeNet and its H1; for
+    front="table" the CornerTable itself (scores are float32, there is no net)."""
+    if front not in FRONTS:
+        raise ValueError(f"front must be 'dense', 'codes' or 'table', got {front!r}")
+    if front == "table":
+        _check_table(model, env.cube_size)                     # what needs no device first: the env's stickers are not touched yet
+        _check_table(model, env.cube_size, env.stickers.device)
+        return model, torch.float32, None
     from .adi import _module_dtype
-    if front not in ("dense", "codes"):
-        raise ValueError(f"front must be 'dense' or 'codes', got {front!r}")
     if front == "dense":
         return model, _module_dtype(model), None
     from .codenet import CodeNet
@@ -317,6 +349,16 @@ class AStarPlan:
                                     ptr(self.iteration), ptr(self.pop_node), *self._pool(), ptr(self.count), ptr(self.overflow),
                                     ptr(self.table), self.table.numel(), ptr(b.workspace), b.workspace.numel(), stream_ptr(self.dev)))
 
+    def relax(self):
+        """rcp_relax (front="table" only): an OPEN node that this iteration's candidates reach by fewer moves takes the lower g, the new
+        parent and the prio that follows -- what makes the table-guided search A* proper (include/rubiksearch.h)."""
+        from ._pattern_lib import pattern_lib
+        b = self.beam
+        check(pattern_lib().rcp_relax(self.P, self.cs, self.B, b.pitch, self.C, self.weight, ptr(b.flags), ptr(b.keys), ptr(b.live),
+                                      ptr(b.active), ptr(self.pop_node), ptr(self.keys), ptr(self.parent), ptr(self.action), ptr(self.g),
+                                      ptr(self.node_score), ptr(self.prio), ptr(self.state), ptr(self.count), ptr(self.table),
+                                      self.table.numel(), stream_ptr(self.dev)))
+
     def backtrack(self, max_length):
         """actions uint8 [max_length, P] (kept as self.actions): the solutions' moves, then the no-op."""
         from ._astar_lib import astar_lib
@@ -332,6 +374,8 @@ class AStarPlan:
         self.expand()
         self.score(model)
         self.merge()
+        if self.beam.front == "table":
+            self.relax()
         self.iteration.add_(1)
 
 
@@ -355,7 +399,9 @@ def astar_search(model, env, batch, max_iterations, *, weight=1.0, capacity=None
     (ties: the newer node), expands them, scores the children with the value head as beam_search does (front as there) and appends the
     states the pool has not seen; a cube is solved at the first iteration a child is solved.  capacity: nodes per cube, default
     astar_capacity(...) (pool and table under POOL_BUDGET_BYTES); a full pool drops new states and sets overflow.  "All cubes done"
-    is checked on the host every `sync_every` iterations.  graph=True replays one iteration as a hipGraph (one capture, after a warm-up
+    is checked on the host every `sync_every` iterations.  front="table" (a pattern.CornerTable as the model) adds rcp_relax to every
+    iteration: an open node reached again by fewer moves takes the lower g, so that with batch = 1 and weight = 1 the solution is optimal
+    under the table's admissible bound; the net fronts keep the rule as it is.  graph=True replays one iteration as a hipGraph (one capture, after a warm-up
     iteration on a side stream); the results equal the eager run's.
 
     Returns dict(solved bool [P], length int32 [P] (0: the root was solved, -1: not solved), actions uint8 [L, P] with
@@ -408,6 +454,8 @@ def beam_search_symmetric(model, env, width, max_depth, symmetries="rotations", 
     latter mapped back as well."""
     from .tables import get_symmetries
     from .vec_env import VecCubeEnv
+    if beam_kwargs.get("front") == "table":
+        _check_table(model, env.cube_size)                     # before the images are built on the device
     P, cs, dev = env.num_envs, env.cube_size, env.device
     y = get_symmetries(cs)
     idx = symmetry_indices(symmetries, cs)
@@ -456,6 +504,8 @@ def beam_solve_percentage(model, cube_size, sample_scramble_count, sample_cube_c
                           graph=False, front="dense"):
     """rollout.solve_percentage with the beam search as the solver: for scramble_count = 1..sample_scramble_count, the percentage
     of the sample_cube_count cubes (seeds i * 10, train.py:180) solved within max_depth.  All (k, seed) pairs run as ONE batch."""
+    if front == "table":
+        _check_table(model, cube_size)                         # before the cubes are scrambled on the device
     return _solve_percentage(lambda env: beam_search(model, env, width, max_depth, graph=graph, front=front), cube_size,
                              sample_scramble_count, sample_cube_count, device, seeds)
 
@@ -465,5 +515,7 @@ def astar_solve_percentage(model, cube_size, sample_scramble_count, sample_cube_
                            weight=1.0, capacity=None, graph=False, front="dense"):
     """beam_solve_percentage with astar_search as the solver: for scramble_count = 1..sample_scramble_count, the percentage of the
     sample_cube_count cubes (seeds i * 10, train.py:180) solved within max_iterations.  All (k, seed) pairs run as ONE batch."""
+    if front == "table":
+        _check_table(model, cube_size)                         # before the cubes are scrambled on the device
     return _solve_percentage(lambda env: astar_search(model, env, batch, max_iterations, weight=weight, capacity=capacity, graph=graph,
                                                       front=front), cube_size, sample_scramble_count, sample_cube_count, device, seeds)

@@ -518,3 +518,12 @@ def get_cubies(cube_size: int) -> CubieTables:
     return CubieTables(cube_size=n, nc=nc, ne=ne, corner_cw=cw, edge_facelets=t.edge_defs.copy(), corner_colours=ccol, edge_colours=ecol,
                        fixed=np.flatnonzero(~moved).astype(np.uint8), solved=t.solved, corner_pair=cpair, corner_third=cthird, edge_pair=epair,
                        corner_sticker=cstick, edge_sticker=estick)
+
+
+def get_corner_moves(cube_size: int):
+    """(src, twist) uint8 [A][NC]: how a move acts on the corner state (piece[q], ori[q]) of the cubie rule above (include/rubiksearch.h
+    "Corner pattern database"): piece'[q] = piece[src[a][q]], ori'[q] = (ori[src[a][q]] + twist[a][q]) mod 3, where 3 * src[a][q] +
+    twist[a][q] is the corner byte of slot q after move a on the solved cube (moves gather: state[perm[a]])."""
+    t, cb = get_tables(cube_size), get_cubies(cube_size)
+    cub = cb.cubies(t.solved[t.perm.astype(np.int64)])[0][:, :cb.nc]
+    return (cub // 3).astype(np.uint8), (cub % 3).astype(np.uint8)

@@ -233,6 +233,11 @@ class VecCubeEnv:
         """uint8 [N]: 0 where the cube can be reached from solved by the env's moves, else the RCC_* bits that say why not."""
         return ops.cubies(self.stickers, self.num_envs, self.cube_size, cubies=False)["status"]
 
+    def corner_distance(self, table):
+        """uint8 [N]: the exact distance of every cube's CORNER state from a pattern.CornerTable (one rcp_lookup launch) -- the optimal
+        solution length on the 2x2x2, an admissible lower bound with the right parity on the 3x3x3; 0xFF for illegal corners."""
+        return table.distance(self)
+
     def from_cubies(self, cubies):
         """Set every cube from its cubie bytes: [N, SLOTS] rows (host or device) or a tiled cubie tensor as cubies() returns it.  The
         assembly need not be legal (legality() tells); a byte that names no (piece, orientation) raises ValueError and the env keeps
