@@ -773,6 +773,15 @@ __global__ void __launch_bounds__(kSelThreads) k_astar_pop(PopArgs a) {
     if (tid == 0) a.live[p] = (int32_t)min(npop, B);
 }
 
+// prio = score - weight * g as TWO roundings, never an fma: numpy float32 bit for bit.  HIP's __fmul_rn / __fsub_rn are the plain
+// operators, which the compiler contracted into one v_fma_f32 once they were inlined next to each other; the pragma takes the
+// permission to contract from the two operations of this function, wherever it is inlined.
+__device__ __forceinline__ float prio_of(float score, float weight, int32_t g) {
+#pragma clang fp contract(off)
+    const float prod = weight * (float)g;
+    return score - prod;
+}
+
 struct MergeArgs {
     Cands s;                      // the iteration's candidates and the scratch table k_insert filled
     Pool o;
@@ -869,7 +878,7 @@ __global__ void __launch_bounds__(kSelThreads) k_astar_merge(MergeArgs a) {
             o.action[gid] = (uint8_t)(c % T::A);
             o.g[gid] = g;
             o.score[gid] = sc;
-            o.prio[gid] = __fsub_rn(sc, __fmul_rn(a.weight, (float)g));   // two roundings, never an fma: numpy float32 bit for bit
+            o.prio[gid] = prio_of(sc, a.weight, g);
             o.state[gid] = kOpen;
             table_put(o, slot_of<T>(k, p, o.tmask), gid);
         });
@@ -1279,7 +1288,7 @@ __global__ void __launch_bounds__(kSelThreads) k_pdb_relax(RelaxArgs a) {
         if (v < 0 || o.parent[v] != -(int32_t)c - 2) continue;
         o.parent[v] = min(max(a.pop_node[p * s.width + c / T::A], 0), count - 1);
         o.action[v] = (uint8_t)(c % T::A);
-        o.prio[v] = __fsub_rn(o.score[v], __fmul_rn(a.weight, (float)newg));
+        o.prio[v] = prio_of(o.score[v], a.weight, newg);
     }
 }
 

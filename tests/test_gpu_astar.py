@@ -35,10 +35,11 @@ def bits(a):
 class Pair:
     """An AStarPlan and the restatement on the same roots, every buffer pre-filled with the same bytes on both sides."""
 
-    def __init__(self, cs, scr, B, C, weight=1.0, model=None, front="dense", dtype=torch.float32):
+    def __init__(self, cs, scr, B, C, weight=1.0, model=None, front="dense", dtype=torch.float32, relax=False):
+        """relax: the restatement is tests/pattern_ref.py's Relaxed and iterate() runs rcp_relax as a fourth stage after merge."""
         S = search_mod()
         self.cube = cube = beam_ref.Cube(cs)
-        self.cs, self.P, self.B, self.C, self.model = cs, len(scr), B, C, model
+        self.cs, self.P, self.B, self.C, self.model, self.relax = cs, len(scr), B, C, model, relax
         self.env = env_of(cs, scr)
         hidden = None
         if front == "codes":
@@ -52,7 +53,9 @@ class Pair:
         plan.beam.beams[0].fill_(BEAM_FILL)
         plan.beam.last_action.fill_(BEAM_FILL)
         roots = cube.scramble(scr)
-        self.ref = ref = R.AStar(cube, roots, B, C, weight)
+        if relax:
+            from tests import pattern_ref
+        self.ref = ref = (pattern_ref.relaxed_class() if relax else R.AStar)(cube, roots, B, C, weight)
         for name in ("pop_node",):
             getattr(ref, name).view(np.uint8)[:] = FILL
         ref.beam[:], ref.last_action[:] = BEAM_FILL, BEAM_FILL
@@ -96,8 +99,9 @@ class Pair:
         fl = self.plan.beam.flags.cpu().numpy()
         return {p: fl[:, p * self.B:p * self.B + int(self.ref.live[p])].T.reshape(-1).copy() for p in self.ref.cand}, fl
 
-    def iterate(self, write_scores=None):
-        """One iteration on both sides, compared after every stage.  write_scores(pair) overwrites plan.beam.scores instead of the model."""
+    def iterate(self, write_scores=None, before_relax=None):
+        """One iteration on both sides, compared after every stage.  write_scores(pair) overwrites plan.beam.scores instead of the model;
+        before_relax(pair) runs between merge and relax."""
         plan, ref = self.plan, self.ref
         plan.pop()
         ref.pop()
@@ -127,6 +131,17 @@ class Pair:
             blk = want[:, p * self.B:p * self.B + live]
             blk |= (mask.reshape(live, self.cube.A).T.astype(np.uint8) * R.NEW)
         assert (after == want).all()
+        self.new_masks = new
+        if self.relax:                                                      # the fourth stage: what it may not write keeps its bytes
+            if before_relax is not None:
+                before_relax(self)
+            held = {k: getattr(plan.beam, k).clone() for k in ("flags", "keys", "scores")} | {"table": plan.table.clone()}
+            plan.relax()
+            ref.relax(new)
+            self.compare("relax")
+            for k, was in held.items():
+                now = plan.table if k == "table" else getattr(plan.beam, k)
+                assert torch.equal(now.view(torch.uint8), was.view(torch.uint8)), ("relax wrote", k)
         plan.iteration.add_(1)
 
     def finish(self):
@@ -192,6 +207,21 @@ def test_written_score_modes(mode):
             pair.iterate(hard_writer(mode, seed=10 + mode))
         pair.finish()
         assert (pair.ref.count > B).all()                                   # the radix select had more open nodes than B to choose from
+
+
+@pytest.mark.parametrize("cs", [2, 3])
+def test_merge_priority_is_two_roundings(cs):
+    """prio = score - weight * g with the product rounded before the difference.  Weight 0.7 (its product with 3 needs 26 bits) and
+    scores a few ulps below -3: for many of the new nodes ONE rounding gives other bits -- counted here in float64, which holds the
+    product of two float32 exactly -- so a multiply-subtract that k_astar_merge's compiler contracted into an fma shows."""
+    from tests.pattern_ref import prio_rounded_once
+    pair = Pair(cs, scrambles(cs, [9, 10, 11], seed=2), 16, 800, weight=0.7)    # B >= 12: the third iteration makes nodes at g = 3
+    for _ in range(4):
+        pair.iterate(hard_writer(2, seed=cs))
+    ref = pair.ref
+    made = (np.arange(ref.C)[None, :] < ref.count[:, None]).reshape(-1) & (ref.parent >= 0)      # every node but the roots
+    once = prio_rounded_once(ref.score[made], 0.7, ref.g[made])
+    assert (ref.g[made] >= 3).any() and (bits(once) != bits(ref.prio[made])).any()
 
 
 @pytest.mark.parametrize("cs,B", [(2, 1), (2, 4), (3, 1), (3, 64)])

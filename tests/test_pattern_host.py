@@ -129,6 +129,56 @@ def test_corner_index_of_the_restatement(oracle):
             assert (cb.cubies(e)[1] != 0).all() and (R.corner_index(3, e) == want).all()
 
 
+# ------------------------------------------------------------------------------------------------------------ the relax scenario
+def scenario_roots(case):
+    from tests import beam_ref
+    from tests.test_gpu_search import scrambles
+    return beam_ref.Cube(case.cs).scramble(scrambles(case.cs, R.scenario_depths(case.P), seed=R.SEEDS[case.cs]))
+
+
+@pytest.mark.parametrize("case", R.scenario_cases(max_P=5), ids=R.case_id)
+def test_relax_scenario_reaches_its_cases(case):
+    """"Flood, lift, re-open" (tests/pattern_ref.py) on the restatement alone, at every point of tests/test_gpu_relax.py with P <= 5:
+    the case each point exists for occurs -- contested nodes, ties on g, winners that are not the lowest c, offers from different
+    strides, winners at c >= 256, dropped NEW candidates and their duplicates, a priority an fma would round otherwise."""
+    st = R.run_scenario(case, scenario_roots(case))
+    R.check_reached(case, st)
+    if (case.P, case.B, case.weight, case.C) == (3, 64, 1.0, 1 + 64 * (11 if case.cs == 3 else 5) * 8):
+        # one problem of three is deep here; with three deep roots the counters are three times these
+        want = {(3, True): (533, 63, 28, 36, 18, 7, 354, 0), (3, False): (626, 88, 88, 0, 0, 11, 412, 0),
+                (2, True): (248, 19, 0, 19, 11, 1, 78, 0), (2, False): (293, 28, 28, 0, 0, 1, 97, 0)}[case.cs, case.jitter]
+        assert tuple(st.counters().values()) == want
+
+
+def test_relaxed_step_is_merge_then_relax():
+    """The split restatement: relaxed_step (merge, then relax as a stage of its own) leaves what the inherited rule leaves wherever
+    nothing is relaxed, and a node it lowers holds the least g, then the least c, of its offers."""
+    from tests import astar_ref, beam_ref
+    case = R.Case(3, 3, 4, 1 + 4 * 11 * 8, 1.0, None, True)
+    cube, roots = beam_ref.Cube(3), scenario_roots(case)
+    st, plain = R.relaxed_class()(cube, roots, 4, case.C), astar_ref.AStar(cube, roots, 4, case.C)
+    for _ in range(6):
+        R.relaxed_step(st, lambda states: np.zeros(len(states), np.float32))
+        plain.pop(), plain.expand()
+        plain.merge(R.zero_scores(plain))
+    assert st.relaxed == 0
+    for name in ("g", "parent", "action", "prio", "state", "count", "pop_node", "live", "active"):
+        assert (getattr(st, name) == getattr(plain, name)).all(), name
+    R.doctor(st)
+    before = st.g.copy()
+    R.relaxed_step(st, lambda states: np.zeros(len(states), np.float32))
+    low = np.flatnonzero(st.g < before)
+    assert len(low) == st.relaxed > 0
+    p = 2                                                                    # the deep root
+    par = st.pop_node[p * 4 + st.cand[p]["i"]]
+    for gid in low:
+        n = gid - p * case.C
+        offers = sorted((int(st.g[p * case.C + par[c]]) + 1, int(c)) for c in range(len(par))
+                        if st.cand[p]["valid"][c] and st.known[p][st.cand[p]["keys"][:, c].tobytes()] == n)
+        g, c = offers[0]
+        assert (st.g[gid], st.parent[gid], st.action[gid]) == (g, par[c], st.cand[p]["a"][c]) and st.prio[gid] == np.float32(-g)
+
+
 # ------------------------------------------------------------------------------------------------------------ python errors
 def test_argument_errors_come_before_any_device_use():
     """front="table" and the CornerTable constructor: every ValueError with a device name torch does not know, an env without stickers,
