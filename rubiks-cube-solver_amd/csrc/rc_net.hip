@@ -156,8 +156,10 @@ __global__ void __launch_bounds__(kThreads) k_first_layer(Args a) {
                 acc[0] = acc[0] + f.x; acc[1] = acc[1] + f.y; acc[2] = acc[2] + f.z; acc[3] = acc[3] + f.w;
             }
             if (a.act == RC_NET_ACT_ELU) {
+                // acc > 0 ? acc : expm1f(acc) of the header, where expm1f(-0) is -0.  The device's expm1f answers +0 there, so zeros of
+                // both signs take the identity branch (>=, not >); a NaN fails the comparison and stays a NaN through expm1f.
 #pragma unroll
-                for (int j = 0; j < kV; ++j) acc[j] = acc[j] > 0.0f ? acc[j] : expm1f(acc[j]);
+                for (int j = 0; j < kV; ++j) acc[j] = acc[j] >= 0.0f ? acc[j] : expm1f(acc[j]);
             }
             const int64_t g = g0 + st;
             if (g < a.n && col_ok) store4(static_cast<O *>(a.out) + g * a.out_stride + col, acc);

@@ -7,6 +7,7 @@ communication is reporting (a barrier and a MAX / SUM of scalars), done here.
 """
 from __future__ import annotations
 
+import atexit
 import os
 
 # RCCL and tensor sharing between processes need dmabuf IPC on this driver stack.  The variable is read when the HIP
@@ -58,7 +59,17 @@ def init(backend=None, device=None):
         if backend == "nccl" and device is not None:
             kw["device_id"] = device
         dist.init_process_group(backend, **kw)
+        # a group left alive until the interpreter is torn down still owns running threads (gloo's workers, the store's socket):
+        # now and then one of them outlives its std::thread object and the rank dies in std::terminate ("terminate called without
+        # an active exception", SIGABRT) AFTER its work was done.  The group this function made is closed in order instead.
+        atexit.register(shutdown)
     return rank, ws, local
+
+
+def shutdown():
+    """Destroy the default process group if there is one (idempotent; registered at exit by init for the group it created)."""
+    if dist.is_available() and dist.is_initialized():
+        dist.destroy_process_group()
 
 
 def barrier():

@@ -1,6 +1,7 @@
 """numpy restatement of the net front (include/rubiknet.h, rubiks-cube-solver_amd/codenet.py): the first layer as a sum of table rows in
-slot order, bf16 rounding with integer operations, and the reference's net in float64.  Test infrastructure only; the row mapping is
-written out here independently of codenet.onehot_index."""
+slot order, ELU in float64 with the set of inputs whose result it fixes bit for bit and a band for the others, bf16 rounding with
+integer operations, and the reference's net in float64.  Test infrastructure only; the row mapping is written out here independently
+of codenet.onehot_index."""
 from __future__ import annotations
 
 import numpy as np
@@ -10,21 +11,25 @@ N_CODES = {3: 24, 2: 21}
 ROWS = {3: 480, 2: 147}
 
 
-def row_index(cube_size, codes):
-    """codes [n, SLOTS] -> k [n, SLOTS]: the flat index of the dense one-hot's 1 (include/rubikhip.h "One-hot formats")."""
+def row_index(cube_size, codes, clamp=False):
+    """codes [n, SLOTS] -> k [n, SLOTS]: the flat index of the dense one-hot's 1 (include/rubikhip.h "One-hot formats").  clamp: a code
+    byte at or above N_CODES counts as the largest code, N_CODES - 1 (include/rubiknet.h); without it such a byte is the caller's error."""
     c = np.asarray(codes).astype(np.int64)
+    if clamp:
+        c = np.minimum(c, N_CODES[cube_size] - 1)
+    assert ((c >= 0) & (c < N_CODES[cube_size])).all()
     s = np.arange(SLOTS[cube_size], dtype=np.int64)[None, :]
     if cube_size == 3:
         return s * 24 + c
     return (c // 3) * 21 + s * 3 + c % 3
 
 
-def first_layer(cube_size, codes, wt, bias=None):
+def first_layer(cube_size, codes, wt, bias=None, clamp=False):
     """float32 [n, H]: acc = bias (or +0), then acc = acc + wt[k(s, code_s)] for s = 0 .. SLOTS-1 in this order, every addition one
-    float32 operation.  wt float32 [R * C, H] (bf16 weights widened by the caller), bias float32 [H] or None."""
+    float32 operation.  wt float32 [R * C, H] (bf16 weights widened by the caller), bias float32 [H] or None; clamp as in row_index."""
     wt = np.asarray(wt)
     assert wt.dtype == np.float32 and wt.shape[0] == ROWS[cube_size]
-    k = row_index(cube_size, codes)
+    k = row_index(cube_size, codes, clamp)
     if bias is None:
         acc = np.zeros((len(k), wt.shape[1]), np.float32)
     else:
@@ -38,8 +43,8 @@ def first_layer(cube_size, codes, wt, bias=None):
 
 def bf16_bits(x):
     """float32 -> bf16 bit patterns (uint16), round to nearest even with integer operations; a NaN stays a NaN."""
-    u = np.ascontiguousarray(x, np.float32).view(np.uint32).astype(np.uint64)
-    r = ((u + 0x7FFF + ((u >> 16) & 1)) >> 16).astype(np.uint16)
+    u = np.ascontiguousarray(x, np.float32).view(np.uint32)
+    r = ((u + (np.uint32(0x7FFF) + ((u >> 16) & 1))) >> 16).astype(np.uint16)        # wraps only for a NaN, replaced below
     nan = (u & 0x7FFFFFFF) > 0x7F800000
     return np.where(nan, ((u >> 16) | 0x40).astype(np.uint16), r)
 
@@ -60,6 +65,139 @@ def same_bits(got, want):
         gn, wn = (got & 0x7FFF) > 0x7F80, (want & 0x7FFF) > 0x7F80
         gb, wb = got, want
     return bool((gn == wn).all() and (gb[~wn] == wb[~wn]).all())
+
+
+def ulps(got, exact):
+    """|got - exact| in units of the float32 spacing at |exact| (float64 arithmetic)."""
+    e32 = np.abs(exact).astype(np.float32)
+    return np.abs(got.astype(np.float64) - exact) / np.spacing(np.maximum(e32, np.float32(0))).astype(np.float64)
+
+
+def elu_exact(x):
+    """float64 x > 0 ? x : expm1(x) of a float32 array (alpha = 1)."""
+    x = np.asarray(x)
+    assert x.dtype == np.float32
+    x = x.astype(np.float64)
+    with np.errstate(invalid="ignore", over="ignore"):                 # expm1 of the positives is computed and dropped
+        return np.where(x > 0, x, np.expm1(x))
+
+
+def elu_fixed(x):
+    """Where the reference fixes every bit of the result: x > 0 (x itself), +0 -> +0, -0 -> -0, +inf, -inf -> -1, NaN -> NaN.  That is
+    every input but the negative finite ones; there float32(elu_exact(x)) is exact."""
+    x = np.asarray(x)
+    return ~((x < 0) & np.isfinite(x))
+
+
+def elu_bounds(x, T):
+    """float32 lo, hi: float32(exact -+ T ulp), ulp the float32 spacing at |exact| as in ulps().  A float32 result within T ulps of
+    the exact value lies in [lo, hi] (rounding is monotonic).  Where elu_fixed(x), lo = hi = float32(exact): no band."""
+    exact = elu_exact(x)
+    with np.errstate(invalid="ignore", over="ignore"):
+        ulp = np.spacing(np.maximum(np.abs(exact).astype(np.float32), np.float32(0))).astype(np.float64)
+        lo, hi = (exact - T * ulp).astype(np.float32), (exact + T * ulp).astype(np.float32)
+    fixed = elu_fixed(x)
+    e32 = exact.astype(np.float32)
+    return np.where(fixed, e32, lo), np.where(fixed, e32, hi)
+
+
+def _bf16_nan(bits):
+    return (bits & 0x7FFF) > 0x7F80
+
+
+def _bf16_order(bits):
+    """bf16 bit patterns -> integers ordered like the values; -0 sorts directly below +0."""
+    b = np.asarray(bits, np.uint16).astype(np.int32)
+    return np.where(b & 0x8000, -(b & 0x7FFF) - 1, b & 0x7FFF)
+
+
+def bf16_between(bits, lo, hi):
+    """(inside, pinned) for bf16 bit patterns `bits` and float32 ends lo <= hi: inside = bf16_bits(lo) <= bits <= bf16_bits(hi) as ordered
+    values, which a correctly rounded float32 in [lo, hi] must satisfy since rounding is monotonic (a NaN end admits only a NaN);
+    pinned = the two ends round to the same bf16, so the reference alone fixes the result and inside means equal."""
+    bits = np.asarray(bits)
+    assert bits.dtype == np.uint16
+    bl, bh = bf16_bits(lo).reshape(bits.shape), bf16_bits(hi).reshape(bits.shape)
+    nl, nh, nb = _bf16_nan(bl), _bf16_nan(bh), _bf16_nan(bits)
+    k = _bf16_order(bits)
+    inside = (_bf16_order(bl) <= k) & (k <= _bf16_order(bh)) & ~nb
+    return np.where(nl | nh, nl & nh & nb, inside), (bl == bh) | (nl & nh)
+
+
+def elu_check(x, got, T):
+    """A device result against the reference alone -> (wrong, neg, err, pinned).  x float32: the restated pre-activation; got: float32,
+    or bf16 bit patterns (uint16), of act(x) rounded once.  wrong: the elements the reference rejects,
+    float32   where elu_fixed(x): not bit-equal to float32(elu_exact(x)) (a NaN matches any NaN); else more than T ulps from elu_exact(x)
+    bf16      where elu_fixed(x): not bit-equal to bf16_bits of the exact value; else outside bf16_between(got, *elu_bounds(x, T)),
+              which is "not equal" where the band's ends coincide
+    neg = ~elu_fixed(x); err: |got - exact| on neg in float32 ulps; pinned: on neg, where the band's ends coincide (None for float32)."""
+    x, got = np.asarray(x), np.asarray(got)
+    assert x.dtype == np.float32 and got.shape == x.shape
+    neg = ~elu_fixed(x)
+    xf, gf = x[~neg], got[~neg]
+    want = elu_exact(xf).astype(np.float32)                            # exact: x, +-0, +inf, -1, NaN
+    xn, gn = x[neg], got[neg]
+    exact = elu_exact(xn)
+    wrong = np.zeros(x.shape, bool)
+    if got.dtype == np.float32:
+        a, b = np.isnan(gf), np.isnan(want)
+        wrong[~neg] = (a != b) | (~b & (gf.view(np.uint32) != want.view(np.uint32)))
+        with np.errstate(invalid="ignore"):
+            err = ulps(gn, exact)
+            wrong[neg] = ~(err <= T)                                   # a NaN is far
+        return wrong, neg, err, None
+    assert got.dtype == np.uint16
+    wb = bf16_bits(want)
+    a, b = _bf16_nan(gf), _bf16_nan(wb)
+    wrong[~neg] = (a != b) | (~b & (gf != wb))
+    lo, hi = elu_bounds(xn, T)
+    inside, pinned = bf16_between(gn, lo, hi)
+    wrong[neg] = ~inside | (pinned & (gn != bf16_bits(lo)))
+    with np.errstate(invalid="ignore"):
+        err = ulps(bf16_to_f32(gn), exact)
+    return wrong, neg, err, pinned
+
+
+def elu_wrong(x, got, T):
+    return elu_check(x, got, T)[0]
+
+
+def mild_table(rng, rows, hidden):
+    """float32 [rows, hidden] and a bias for the ELU tests: N(0, 1) * 10^{-3..0}, so that about half of the sums fall in (-20, 0);
+    0.2 % of the entries are the special values of the exact tests' table; column 3 is -0 with bias -0."""
+    w = (rng.standard_normal((rows, hidden)) * 10.0 ** rng.integers(-3, 1, (rows, hidden))).astype(np.float32)
+    special = np.array([0.0, -0.0, np.inf, -np.inf, np.nan, 1e-40, -3e-42, 3.4e38, -3.4e38], np.float32)
+    hit = rng.random((rows, hidden)) < 0.002
+    w[hit] = special[rng.integers(0, len(special), int(hit.sum()))]
+    b = (rng.standard_normal(hidden) * 10.0 ** rng.integers(-3, 1, hidden)).astype(np.float32)
+    w[:, 3], b[3] = -0.0, -0.0
+    return w, b
+
+
+def elu_sweep():
+    """4096 float32 inputs of ELU placed exactly: 3000 points of [-20, 0], negative denormals and tiny normals, positives over the whole
+    range, +-0, +-inf, NaN, -87, -88.8, -104, -1e30; the rest +0.  As the bias over a table of -0 rows it is the sum itself."""
+    sweep = np.concatenate([np.linspace(-20, 0, 3000).astype(np.float32), -np.logspace(-45, -30, 500).astype(np.float32),
+                            -np.logspace(-30, -1, 500).astype(np.float32), np.logspace(-45, 38, 80).astype(np.float32),
+                            np.array([0.0, -0.0, np.inf, -np.inf, np.nan, -87.0, -88.8, -104.0, -1e30], np.float32)])
+    return np.concatenate([sweep, np.zeros(4096 - len(sweep), np.float32)])
+
+
+def elu_case(cube_size, cube, n, hidden, use_bias, bf16, seed, sweep=False):
+    """One input of the ELU tests -> (codes [n, SLOTS], table float32, bias float32 or None, x = first_layer of them).  The table is
+    mild_table's, or with sweep rows of -0 under the bias elu_sweep() (hidden = 4096); bf16: table and bias rounded once to bf16 and
+    widened again, as the device holds them."""
+    rng = np.random.default_rng(seed)
+    codes = cube.codes(random_states(cube, n, rng))
+    if sweep:
+        assert hidden == 4096 and use_bias
+        w, b = np.full((ROWS[cube_size], hidden), -0.0, np.float32), elu_sweep()
+    else:
+        w, b = mild_table(rng, ROWS[cube_size], hidden)
+    if bf16:
+        w, b = bf16_to_f32(bf16_bits(w)), bf16_to_f32(bf16_bits(b))
+    b = b if use_bias else None
+    return codes, w, b, first_layer(cube_size, codes, w, b)
 
 
 def tiled_codes(codes, pitch):

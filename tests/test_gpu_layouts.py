@@ -619,7 +619,7 @@ def test_carved_search_stages(ops, L, cs):
 
 
 @pytest.mark.parametrize("cs", C.CUBE_SIZES)
-@pytest.mark.parametrize("fmts", [(4, 4), (5, 5)], ids=["f32", "bf16"])
+@pytest.mark.parametrize("fmts", [(4, 4), (5, 5), (4, 5), (5, 4)], ids=["f32", "bf16", "f32_to_bf16", "bf16_to_f32"])
 def test_carved_net_first_layer(L, cs, fmts):
     """rc_net_first_layer with codes, weights, bias and output carved: bit-equal to the slot-order sum of tests/net_ref.py."""
     import beam_ref

@@ -605,6 +605,25 @@ def test_dist_init_refuses_legacy_ipc_for_nccl(monkeypatch):
     assert not d.dist.is_initialized()
 
 
+def test_dist_init_closes_its_group_at_exit(monkeypatch):
+    """dist.init registers dist.shutdown for the group it creates (a rank that leaves a gloo group to interpreter teardown now and
+    then aborts in std::terminate after its work is done, which made the multi-rank tests here fail about once in ten runs);
+    shutdown without a group does nothing, so bench.py's own destroy_process_group before it is fine."""
+    from rubiks_cube_solver_amd import dist as d
+    made, hooks = [], []
+    monkeypatch.setenv("WORLD_SIZE", "2")
+    monkeypatch.setenv("RANK", "1")
+    monkeypatch.setenv("MASTER_ADDR", "127.0.0.1")               # init's setdefault then changes nothing that outlives this test
+    monkeypatch.setattr(d.dist, "init_process_group", lambda backend, **kw: made.append(backend))
+    monkeypatch.setattr(d.atexit, "register", hooks.append)
+    assert d.init(backend="gloo")[:2] == (1, 2) and made == ["gloo"] and hooks == [d.shutdown]
+    assert not d.dist.is_initialized()
+    d.shutdown()
+    d.shutdown()
+    monkeypatch.setenv("WORLD_SIZE", "1")
+    assert d.init(backend="gloo")[:2] == (1, 1) and made == ["gloo"] and hooks == [d.shutdown]      # one process: no group, no hook
+
+
 def test_eight_rank_streams_and_shards(tmp_path):
     """BASELINE config 4's world size (8 ranks) on CPU over gloo: eight contiguous shards that tile the batch, eight RNG streams
     that are each the oracle's (seed, stream_id = rank) stream and pairwise different, SUM / MAX reductions over all eight.

@@ -1,5 +1,6 @@
 """The net front without a GPU: librubiknet.so's ABI and build id, the code -> one-hot index table, what CodeNet refuses, and the
-restatement (tests/net_ref.py) against the dense first layer."""
+restatement (tests/net_ref.py) against the dense first layer; its ELU checkers accept an honest float32 ELU rounded once and reject
+six wrong ones."""
 import os
 import re
 import sys
@@ -112,6 +113,128 @@ def test_codenet_table_follows_the_weight_in_the_same_storage():
     assert float(net.weight_t.abs().sum()) == 0 and net.weight_t.data_ptr() == at
     net._sync()                                                                  # nothing changed: nothing copied
     assert net._seen[0] == m.encoder_net[1].weight._version
+
+
+def test_row_index_clamps_an_out_of_range_byte_to_the_largest_code():
+    for cs in (3, 2):
+        SL, N = net_ref.SLOTS[cs], net_ref.N_CODES[cs]
+        codes = np.tile(np.arange(256)[:, None], (1, SL))
+        k = net_ref.row_index(cs, codes, clamp=True)
+        assert (k[:N] == net_ref.row_index(cs, codes[:N])).all() and (k[N:] == k[N - 1]).all()
+        assert k.min() == 0 and k.max() == net_ref.ROWS[cs] - 1 and len(np.unique(k)) == net_ref.ROWS[cs]
+        with pytest.raises(AssertionError):
+            net_ref.row_index(cs, codes[:N + 1])
+
+
+ELU_SHAPES = [(7, 8, False), (1, 120, False), (513, 136, False), (7, 4096, True)]      # n, hidden, the sweep
+
+
+def _elu_inputs(cs, bf16):
+    cube = beam_ref.Cube(cs)
+    return [net_ref.elu_case(cs, cube, n, hidden, True, bf16, 3000 + 100 * cs + i, sweep)[3] for i, (n, hidden, sweep) in enumerate(ELU_SHAPES)]
+
+
+def _elu32(x):
+    """float32 expm1 of the float32 sum.  torch's on the CPU: it stays below 1 ulp, while numpy's float32 expm1 reaches 2.3 ulp near
+    -0.011 and would not be an honest stand-in at T = 2."""
+    import torch
+    x = np.ascontiguousarray(x, np.float32)
+    return np.where(x > 0, x, torch.expm1(torch.from_numpy(x)).numpy())
+
+
+def _bits(y):
+    return np.ascontiguousarray(y, np.float32).view(np.uint32)
+
+
+def _honest(x):
+    y = _elu32(x)
+    return y, net_ref.bf16_bits(y)
+
+
+def _elu_of_the_rounded_sum(x):                                             # (a)
+    return None, net_ref.bf16_bits(_elu32(net_ref.bf16_to_f32(net_ref.bf16_bits(x))))
+
+
+def _rounded_twice(x):                                                      # (b) to 16 significand bits, then to bf16's 8
+    u = _bits(_elu32(x)).astype(np.uint64)
+    mid = (((u + 0x7F + ((u >> 8) & 1)) >> 8) << 8).astype(np.uint32).view(np.float32)
+    return None, np.where(np.isnan(x), net_ref.bf16_bits(_elu32(x)), net_ref.bf16_bits(mid))
+
+
+def _truncated(x):                                                          # (c)
+    return None, (_bits(_elu32(x)) >> 16).astype(np.uint16)
+
+
+def _minus_zero_lost(x):                                                    # (d)
+    y = _elu32(x)
+    y[y == 0] = 0.0
+    return y, net_ref.bf16_bits(y)
+
+
+def _denormal_flushed(x):                                                   # (e) the sign survives, as flush-to-zero hardware has it
+    y = _elu32(x)
+    y[(y < 0) & (y > -np.finfo(np.float32).tiny)] = -0.0
+    return y, net_ref.bf16_bits(y)
+
+
+def _minus_inf_kept(x):                                                     # (f)
+    y = _elu32(x)
+    y[np.isneginf(x)] = -np.inf
+    return y, net_ref.bf16_bits(y)
+
+
+MUTANTS = [_elu_of_the_rounded_sum, _rounded_twice, _truncated, _minus_zero_lost, _denormal_flushed, _minus_inf_kept]
+
+
+@pytest.mark.parametrize("bf16", [False, True], ids=["f32_table", "bf16_table"])
+@pytest.mark.parametrize("cs", [3, 2])
+def test_elu_checkers_accept_the_restatement_and_reject_six_mutants(cs, bf16):
+    """net_ref.elu_wrong at T = 2 on the device test's inputs (mild tables of 7 x 8, 1 x 120 and 513 x 136, and the sweep): float32
+    expm1 of the float32 sum, rounded once, passes in both output formats.  Rejected: (a) ELU of the bf16-rounded sum, (b) a second
+    rounding through 16 significand bits, (c) truncation, (d) -0 answered +0, (e) a negative denormal flushed, (f) -inf kept.
+    (a) is caught even on the two smallest shapes and on more than 5 % of the large one's negative elements (a bf16 rounding of
+    the sum moves it by up to 2^-9 of itself, the result by about as much, against a band a few 2^-24 wide); the band's ends
+    coincide for more than 99.9 % of them, so there the reference alone fixes the bf16 result."""
+    T = 2.0
+    xs = _elu_inputs(cs, bf16)
+    for x in xs:
+        y, b = _honest(x)
+        assert not net_ref.elu_wrong(x, y, T).any() and not net_ref.elu_wrong(x, b, T).any()
+    big = xs[2]
+    neg = ~net_ref.elu_fixed(big)
+    assert ((big > -20) & (big < 0)).sum() >= 10000
+    pinned = net_ref.bf16_between(_honest(big)[1], *net_ref.elu_bounds(big, T))[1]
+    assert pinned[neg].mean() > 0.999
+    union = np.concatenate([x.reshape(-1) for x in xs])
+    tiny = np.finfo(np.float32).tiny
+    assert np.isnan(union).any() and np.isposinf(union).any() and np.isneginf(union).any() and (np.signbit(union) & (union == 0)).any()
+    assert ((union < 0) & (union > -tiny)).any() and ((union < -88) & np.isfinite(union)).any()
+    for mutant in MUTANTS:
+        caught32, caught16 = 0, []
+        for x in xs:
+            y, b = mutant(x)
+            caught16.append(int(net_ref.elu_wrong(x, b, T).sum()))
+            caught32 += 0 if y is None else int(net_ref.elu_wrong(x, y, T).sum())
+        print(f"{cs} bf16 table {bf16} {mutant.__name__}: rejected bf16 elements per input {caught16}, float32 elements {caught32}")
+        assert sum(caught16) > 0, mutant.__name__
+        if mutant in MUTANTS[3:]:
+            assert caught32 > 0, mutant.__name__
+        if mutant is _elu_of_the_rounded_sum:
+            assert caught16[0] >= 2 and caught16[1] >= 2 and caught16[2] > 0.05 * neg.sum(), caught16
+
+
+def test_bf16_between_orders_the_bit_patterns_like_the_values():
+    v = np.array([-np.inf, -3.0, -1.0, -1e-40, -0.0, 0.0, 1e-40, 1.0, 3.0, np.inf], np.float32)
+    bits = net_ref.bf16_bits(v)
+    for i in range(len(v)):
+        for j in range(i, len(v)):
+            inside, pinned = net_ref.bf16_between(bits, np.full(len(v), v[i]), np.full(len(v), v[j]))
+            assert (inside == ((np.arange(len(v)) >= i) & (np.arange(len(v)) <= j))).all() and (pinned == (i == j)).all()
+    nan = np.full(1, np.nan, np.float32)
+    inside, pinned = net_ref.bf16_between(net_ref.bf16_bits(nan), nan, nan)
+    assert inside.all() and pinned.all()
+    assert not net_ref.bf16_between(net_ref.bf16_bits(nan), -np.ones(1, np.float32), np.full(1, np.inf, np.float32))[0].any()
+    assert not net_ref.bf16_between(net_ref.bf16_bits(np.ones(1, np.float32)), nan, nan)[0].any()
 
 
 @pytest.mark.parametrize("cs", [3, 2])
