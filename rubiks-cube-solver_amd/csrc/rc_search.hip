@@ -492,10 +492,33 @@ __global__ void __launch_bounds__(256) k_backtrack(const uint16_t *hp, const uin
     }
 }
 
+// --------------------------------------------------------------------------------------------------- fills
+// The launchers clear their tables with these and not with hipMemsetAsync.  Observed on an MI355X with torch 2.10's HIP runtime
+// 7.0.51831 (ROCm 7.2.0 installed), torch.cuda.graph on a side stream: a captured hipMemsetAsync(p, 0xFF, n) replays with other
+// bytes -- all 0x00 for 3.6 MB, a mix of 0x00 and stale values for 64 KiB, with or without a kernel node in front of it;
+// tools/probe_graph_memset.py shows it with the runtime call alone.  rcp_build_begin captured on its own then left a zeroed table and
+// rc_search_select's table was never empty, so k_insert probed for ever (tests/test_gpu_stream_order.py).  Why the runtime does this
+// is not known here; a kernel node replays as launched.  The probe says whether a later runtime lets the memset come back.
+// p[0 .. n16) = 16 bytes of the 32-bit pattern v each, the first word of all `first`.
+__global__ void __launch_bounds__(256) k_fill16(uint4 *p, int64_t n16, uint32_t v, uint32_t first) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n16) p[i] = make_uint4(i == 0 ? first : v, v, v, v);
+}
+__global__ void k_store32(uint32_t *p, uint32_t v) { *p = v; }
+
 // ------------------------------------------------------------------------------------------------- host side
 // -1: bad argument, -2: a HIP call failed (include/rubiksearch.h)
 inline int fail(const char *msg) { return fail(-1, "%s", msg); }
 inline int fail(const char *fn, const char *msg) { return fail(-1, "%s: %s", fn, msg); }
+
+// `bytes` (a multiple of 16) at the 16-byte aligned p = the pattern v, the first word `first`: one launch on `st`
+int fill16(void *p, int64_t bytes, uint32_t v, uint32_t first, hipStream_t st) {
+    const int64_t n16 = bytes / 16;
+    if (n16 <= 0) return 0;
+    hipLaunchKernelGGL(k_fill16, dim3((unsigned)ceil_div(n16, (int64_t)256)), dim3(256), 0, st, static_cast<uint4 *>(p), n16, v, first);
+    RC_HIP(-2, hipGetLastError());
+    return 0;
+}
 
 struct Geo {
     int64_t nb, nbp;
@@ -587,7 +610,7 @@ int rc_search_select(uint8_t *flags, const uint64_t *keys, const float *scores, 
         const Cands c{flags, keys, scores, live, active, length, solution, static_cast<unsigned long long *>(workspace), (uint64_t)(slots - 1),
                       g.nbp, width};
         const SelectArgs a{c, depth, sel_parent, sel_action, sel_count};
-        RC_HIP(-2, hipMemsetAsync(workspace, 0xFF, (size_t)slots * 8, S(stream)));       // every slot kEmpty
+        if (int rc = fill16(workspace, slots * 8, ~0u, ~0u, S(stream))) return rc;       // every slot kEmpty
         hipLaunchKernelGGL((k_insert<T>), dim3((unsigned)((T::A * g.nbp + 255) / 256)), dim3(256), 0, S(stream), c);
         RC_HIP(-2, hipGetLastError());
         hipLaunchKernelGGL((k_select<T>), dim3((unsigned)n), dim3(kSelThreads), 0, S(stream), a);
@@ -956,7 +979,7 @@ int rca_init(const uint8_t *roots, int64_t n, int64_t root_pitch, int cube_size,
         if (int rc = root_shift<T>("rca_init", n, root_pitch, rshift)) return rc;
         const Pool o = make_pool(pool_stickers, pool_keys, pool_parent, pool_action, pool_g, pool_score, pool_prio, pool_state, count, overflow,
                                  table, pg, n, capacity, pool_pitch);
-        RC_HIP(-2, hipMemsetAsync(table, 0xFF, (size_t)pg.slots * 8, S(stream)));           // every slot kEmpty, once per search
+        if (int rc = fill16(table, pg.slots * 8, ~0u, ~0u, S(stream))) return rc;           // every slot kEmpty, once per search
         hipLaunchKernelGGL((k_astar_init<T>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, S(stream), roots, n, root_pitch, rshift, o, live,
                            active, length, solution, ended);
         RC_HIP(-2, hipGetLastError());
@@ -1011,7 +1034,7 @@ int rca_merge(int64_t n, int cube_size, int batch, int64_t pitch, int64_t capaci
         const MergeArgs a{s, make_pool(pool_stickers, pool_keys, pool_parent, pool_action, pool_g, pool_score, pool_prio, pool_state, count, overflow,
                                        table, pg, n, capacity, pool_pitch),
                           iteration, pop_node, ended, weight};
-        RC_HIP(-2, hipMemsetAsync(scratch, 0xFF, (size_t)sslots * 8, S(stream)));
+        if (int rc = fill16(scratch, sslots * 8, ~0u, ~0u, S(stream))) return rc;
         hipLaunchKernelGGL((k_insert<T>), dim3((unsigned)((T::A * g.nbp + 255) / 256)), dim3(256), 0, S(stream), s);
         RC_HIP(-2, hipGetLastError());
         hipLaunchKernelGGL((k_astar_merge<T>), dim3((unsigned)n), dim3(kSelThreads), 0, S(stream), a);
@@ -1319,9 +1342,8 @@ int rcp_build_begin(uint8_t *table, int64_t bytes, int cube_size, void *stream) 
     return by_size(cube_size, [&](auto t) {
         using T = decltype(t);
         if (int rc = table_arg<T>("rcp_build_begin", table, bytes)) return rc;
-        RC_HIP(-2, hipMemsetAsync(table, 0xFF, (size_t)CornerSpace<T>::N, S(stream)));
-        RC_HIP(-2, hipMemsetAsync(table, 0, 1, S(stream)));              // corner_index(solved) = 0
-        return 0;
+        static_assert(CornerSpace<T>::N % 16 == 0, "the table is filled 16 bytes at a time");
+        return fill16(table, (int64_t)CornerSpace<T>::N, ~0u, 0xFFFFFF00u, S(stream));   // every entry 0xFF; corner_index(solved) = 0: byte 0 is 0
     });
 }
 
@@ -1331,7 +1353,8 @@ int rcp_build_level(uint8_t *table, int64_t bytes, int cube_size, int depth, uin
         if (int rc = table_arg<T>("rcp_build_level", table, bytes)) return rc;
         if (depth < 0 || depth >= 254) return fail("rcp_build_level: depth must be in 0..253");
         if (!count || !aligned16(count)) return fail("rcp_build_level: count is NULL or not 16-byte aligned");
-        RC_HIP(-2, hipMemsetAsync(count, 0, 4, S(stream)));
+        hipLaunchKernelGGL(k_store32, dim3(1), dim3(1), 0, S(stream), count, 0u);
+        RC_HIP(-2, hipGetLastError());
         hipLaunchKernelGGL((k_pdb_level<T>), dim3((CornerSpace<T>::N + 255u) / 256u), dim3(256), 0, S(stream), table, (uint32_t)depth, count);
         RC_HIP(-2, hipGetLastError());
         return 0;
