@@ -432,6 +432,59 @@ int rcc_from_cubies(const uint8_t *cubies, int64_t n_cubes, int64_t cubie_pitch,
  * of piece p in the order of corner_cw[p] / edge_facelets[p]. */
 int rcc_tables(int cube_size, uint8_t *corner_cw, uint8_t *edge_facelets, uint8_t *corner_colours, uint8_t *edge_colours);
 
+/* ---------------------------------------------------------------------------------------------------------------------------------
+ * Edge pattern databases (prefix rce_): exact distance tables over the places and flips of up to 7 of the 12 edge pieces, Korf's
+ * companion of the corner table (include/rubiksearch.h rcp_*).  3x3x3 ONLY: the 2x2x2 has no edges, and no entry point takes a
+ * cube_size.  No reference counterpart.
+ *
+ * THE RULE.
+ *   tracked set   `mask`: bit t set = edge PIECE t (numbered as edge_defs) is tracked; k set bits, 1 <= k <= 7, t_0 < ... < t_{k-1}.
+ *   pattern       for each t_i the slot p_i in 0..11 it sits in and its ori bit o_i = the low bit of that slot's edge byte
+ *                 (piece * 2 + ori, the rcc_* / RC_FMT_CODE edge byte).
+ *   index         d_i = p_i - #{j < i : p_j < p_i} (in [0, 12 - i));  perm = sum_i d_i * prod_{j = i+1}^{k-1} (12 - j);
+ *                 index = perm * 2^k + sum_i o_i * 2^i, below N(k) = 12!/(12-k)! * 2^k = 24, 528, 10 560, 190 080, 3 041 280,
+ *                 42 577 920, 510 935 040 (all below 2^32).
+ *   home          p_i = t_i, o_i = 0: rce_home_index(mask), NOT 0 in general.
+ *   move a        2 * esrc[a][q] + eflip[a][q] is the edge byte of slot q after move a on the solved cube (rce_tables): a piece in slot s
+ *                 goes to the q with esrc[a][q] == s and its ori bit is XORed with eflip[a][q].
+ *   table         table[i] = the least number of quarter turns that bring pattern i home; nothing stays 0xFF.  An admissible and
+ *                 consistent bound on the cube's distance.  Unlike the corner table's, its parity is NOT the distance's.
+ *   illegal       a row set with an edge byte >= 24, a tracked piece absent or a tracked piece twice: h = 0xFF (score -255) and NO table
+ *                 read.  Untracked slots are not looked at beyond the range check.  Every table address passes one guard
+ *                 (idx < N ? table[idx] : 0xFF); the host checks bytes >= N(k).
+ *
+ * Conventions as in the rcc_* section: caller-owned device memory, stream-ordered, nothing allocated; RC_EINVAL before any launch
+ * (rc_last_error names the operand) for a mask that is 0, has a bit above 11 or more than 7 bits, a table smaller than N(k), a NULL
+ * or misaligned pointer, a negative size; pad columns and every byte outside the rows keep their bytes; n == 0 succeeds without a
+ * launch; every pointer needs 16-byte alignment and no more.
+ *
+ * Host only, no device: N(k) and the home index of `mask` (-1 for a bad mask); the library's move tables esrc, eflip [12][12]. */
+int64_t rce_table_bytes(int mask);
+int64_t rce_home_index(int mask);
+int rce_tables(uint8_t *esrc, uint8_t *eflip);
+/* Breadth-first build, one launch per level.  rce_build_begin: every entry 0xFF, home 0 (one fill kernel).  rce_build_level: an entry
+ * still 0xFF becomes depth + 1 iff one of its 12 neighbours holds `depth`; *count (one device uint32, 16-byte aligned, zeroed by the
+ * call) receives how many were set.  Each lane writes its own entry only: the table after a level does not depend on scheduling.  The
+ * table is complete when a level sets nothing.  depth in 0..253. */
+int rce_build_begin(uint8_t *table, int64_t bytes, int mask, void *stream);
+int rce_build_level(uint8_t *table, int64_t bytes, int mask, int depth, uint32_t *count, void *stream);
+/* indices [n] (uint32) -> the 20 cubie rows (rcc_* layout, [tiles][20][cubie_pitch]) of a REACHABLE cube with that pattern: corners
+ * home; the tracked pieces as the index says; the untracked pieces fill the free slots, both in ascending order, with ori 0; if the
+ * flip sum is odd the edge in the highest free slot is flipped; then, if the edge permutation is odd, the edges of the two highest
+ * free slots trade places.  An index >= N(k) is written as the solved cube and sets *bad (one device byte the caller zeroes and
+ * reads, required). */
+int rce_unrank(const uint32_t *indices, int64_t n, int mask, uint8_t *cubies, int64_t cubie_pitch, uint8_t *bad, void *stream);
+/* out[c] = table[index of cube c], 0xFF for an illegal row set.  rows: a tiled [tiles][20][pitch] buffer in RC_FMT_CODE or rcc_cubies
+ * layout (their edge rows are the same bytes); only rows 8..19 are read. */
+int rce_lookup(const uint8_t *rows, int64_t n, int64_t pitch, int mask, const uint8_t *table, int64_t bytes, uint8_t *out, void *stream);
+/* The same over rc_search_expand's candidate code buffer (include/rubiksearch.h: child-major [A * tiles][20][pitch], tiles =
+ * ceil(n_problems * width / pitch), pitch a power of two >= 512), EVERY slot j < A * tiles * pitch, also those past `live` whose bytes
+ * are arbitrary: combine 0: scores[j] = -(float)h;  combine 1: scores[j] = -(float)h where that is LESS than what scores[j] holds
+ * (a tie, -0 against +0 included, and a NaN keep what is there).  One launch per table forms the maximum of several tables; -255,
+ * the illegal score, wins over everything. */
+int rce_score_codes(const uint8_t *code, int64_t n_problems, int width, int64_t pitch, int mask, const uint8_t *table, int64_t bytes,
+                    float *scores, int combine, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,6 +9,8 @@ Drop-in surface for the env path of SUNGBEOMCHOI/Rubiks-Cube-Solver:
   ops                 batched operator layer (assets/py333.py:211-246)
   CornerTable         exact distances of the corner states on the device (pattern.py): God's algorithm on the 2x2x2, the admissible corner
                       bound on the 3x3x3; search.* take it with front="table"
+  EdgeTable, MaxTable exact distances of up to 7 tracked edge pieces of the 3x3x3 (pattern.py), and the maximum of a corner table and edge
+                      tables: the stronger admissible bound front="table" takes in a CornerTable's place
   get_cubies, RCC_*   the cube as pieces: (piece, orientation) bytes, the legality status bits, perfect indices (ops.cubies / from_cubies)
   py333               the same operators under the reference's names, one cube per call
   py222               the six names cube_env.py:8 imports from the file the reference does not ship (2x2x2, one cube per call)
@@ -18,7 +20,8 @@ from .tables import (ACTION_NAMES, RCC_BAD_COLOUR, RCC_BAD_FIXED, RCC_BAD_PIECE,
                      RCC_TWIST, get_cubies, get_env_config, get_tables)
 
 __all__ = ["get_env_config", "get_tables", "get_cubies", "ACTION_NAMES", "RCC_BAD_COLOUR", "RCC_BAD_FIXED", "RCC_BAD_PIECE", "RCC_DUP_PIECE",
-           "RCC_TWIST", "RCC_FLIP", "RCC_PARITY", "RCC_NAMES", "ops", "make_env", "CubeEnv", "VecCubeEnv", "TensorReplayBuffer", "CodeNet", "CornerTable"]
+           "RCC_TWIST", "RCC_FLIP", "RCC_PARITY", "RCC_NAMES", "ops", "make_env", "CubeEnv", "VecCubeEnv", "TensorReplayBuffer", "CodeNet", "CornerTable", "EdgeTable",
+           "MaxTable"]
 
 
 def __getattr__(name):  # torch-dependent parts load lazily
@@ -32,8 +35,8 @@ def __getattr__(name):  # torch-dependent parts load lazily
         return importlib.import_module(f"{__name__}.replay").TensorReplayBuffer
     if name == "CodeNet":
         return importlib.import_module(f"{__name__}.codenet").CodeNet
-    if name == "CornerTable":
-        return importlib.import_module(f"{__name__}.pattern").CornerTable
+    if name in ("CornerTable", "EdgeTable", "MaxTable"):
+        return getattr(importlib.import_module(f"{__name__}.pattern"), name)
     if name in ("CubeEnv", "make_env"):
         return getattr(importlib.import_module(f"{__name__}.cube_env"), name)
     raise AttributeError(name)

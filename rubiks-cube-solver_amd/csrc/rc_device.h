@@ -1259,4 +1259,126 @@ __device__ __forceinline__ CornerCoord corner_move(CornerCoord c) {
     return r;
 }
 
+// ------------------------------------------------------------------------ edge coordinates
+// include/rubikhip.h "Edge pattern databases" (rce_*), 3x3x3 only.  The tracked set is a RUN-TIME 12-bit mask of k <= 7 pieces, so
+// one kernel serves every mask: the loops below are unrolled to kEdgeMaxK steps and step i is guarded by the wave-uniform i < k; the
+// state lives in nibbles of two registers, never in an indexed array (no scratch).
+//   EdgeCoord   nibble i of `pos` = the slot p_i of tracked piece t_i, bit i of `ori` = its ori bit o_i.  WHICH pieces are tracked
+//               does not enter: a move acts on slots, so the index space is walked with k alone;
+//   kEdgeMove   rc_tables.h emove_src / emove_flip turned round: nibble s of dst[a] = the slot q a piece in slot s goes to
+//               (emove_src[a][q] == s), bit s of flip[a] = emove_flip[a][q], the flip it takes on the way.
+constexpr int kEdgeMaxK = 7, kEdgeSlots = 12;
+
+// N(k) = 12!/(12 - k)! * 2^k: 24 ... 510 935 040, all below 2^32
+constexpr uint32_t edge_space(int k) {
+    uint32_t n = 1;
+    for (int i = 0; i < k; ++i) n *= 2u * (uint32_t)(kEdgeSlots - i);
+    return n;
+}
+
+struct EdgeMoveTable {
+    uint64_t dst[Cube3::A];
+    uint32_t flip[Cube3::A];
+    constexpr EdgeMoveTable() : dst{}, flip{} {
+        for (int a = 0; a < Cube3::A; ++a)
+            for (int q = 0; q < kEdgeSlots; ++q) {
+                const int s = Cube3::emove_src[a][q];
+                dst[a] |= (uint64_t)q << (4 * s);
+                flip[a] |= (uint32_t)Cube3::emove_flip[a][q] << s;
+            }
+    }
+};
+inline constexpr EdgeMoveTable kEdgeMove{};
+
+struct EdgeCoord {
+    uint32_t pos, ori;
+};
+
+// THE GUARD of the edge tables: the only place a table address is formed.  n = N(k); the host has checked bytes >= n.
+__device__ __forceinline__ uint32_t edge_table_at(const uint8_t *table, uint32_t idx, uint32_t n) {
+    return idx < n ? (uint32_t)table[idx] : 0xFFu;
+}
+
+// idx < N(k) (the caller checks): index = perm * 2^k + sum o_i 2^i, perm = sum d_i * prod_{j > i} (12 - j), d_i = the rank of p_i
+// among the slots p_0 .. p_{i-1} have left free
+__device__ __forceinline__ EdgeCoord edge_unrank(uint32_t idx, uint32_t k) {
+    EdgeCoord c{0u, idx & ((1u << k) - 1u)};
+    uint32_t perm = idx >> k, dig = 0;
+    sfor<kEdgeMaxK>([&](auto xc) {
+        constexpr uint32_t i = kEdgeMaxK - 1 - decltype(xc)::value, radix = kEdgeSlots - i;
+        if (i < k) {
+            const uint32_t q = perm / radix;
+            dig |= (perm - q * radix) << (4 * i);
+            perm = q;
+        }
+    });
+    uint64_t list = 0xBA9876543210ull;                                    // the free slots, ascending from nibble 0
+    sfor<kEdgeMaxK>([&](auto ic) {
+        constexpr uint32_t i = decltype(ic)::value;
+        if (i < k) {
+            const uint32_t sh = 4u * ((dig >> (4 * i)) & 15u);            // d_i <= 11: sh <= 44
+            const uint64_t low = (1ull << sh) - 1ull;
+            c.pos |= (uint32_t)((list >> sh) & 15ull) << (4 * i);
+            list = (list & low) | ((list >> 4) & ~low);
+        }
+    });
+    return c;
+}
+
+__device__ __forceinline__ uint32_t edge_rank(EdgeCoord c, uint32_t k) {
+    uint32_t used = 0, perm = 0;
+    sfor<kEdgeMaxK>([&](auto ic) {
+        constexpr uint32_t i = decltype(ic)::value;
+        if (i < k) {
+            const uint32_t p = (c.pos >> (4 * i)) & 15u;
+            perm = perm * (kEdgeSlots - i) + p - (uint32_t)__popc(used & ((1u << p) - 1u));
+            used |= 1u << p;
+        }
+    });
+    return (perm << k) | c.ori;
+}
+
+template <int A_>
+__device__ __forceinline__ EdgeCoord edge_move(EdgeCoord c, uint32_t k) {
+    EdgeCoord r{0u, c.ori};
+    sfor<kEdgeMaxK>([&](auto ic) {
+        constexpr uint32_t i = decltype(ic)::value;
+        if (i < k) {
+            const uint32_t s = (c.pos >> (4 * i)) & 15u;
+            r.pos |= (uint32_t)((kEdgeMove.dst[A_] >> (4u * s)) & 15ull) << (4 * i);
+            r.ori ^= ((kEdgeMove.flip[A_] >> s) & 1u) << i;
+        }
+    });
+    return r;
+}
+
+// The index of the 12 edge bytes e[q] (slot q; piece * 2 + ori, any byte value) under the tracked set `mask`; all-ones for an ILLEGAL
+// row set: a byte >= 24, a tracked piece absent, a tracked piece twice.  Untracked slots are not looked at beyond the range check.
+__device__ __forceinline__ uint32_t edge_index_of(const uint32_t (&e)[kEdgeSlots], uint32_t mask, uint32_t k) {
+    uint64_t where = 0;                                                   // nibble p: a slot that holds piece p
+    uint32_t seen = 0, twice = 0, oris = 0, big = 0;
+    sfor<kEdgeSlots>([&](auto qc) {
+        constexpr uint32_t q = decltype(qc)::value;
+        const uint32_t b = e[q], piece = (b >> 1) & 15u, bit = 1u << piece;
+        big |= (uint32_t)(b >= 24u);
+        twice |= seen & bit;
+        seen |= bit;
+        where |= (uint64_t)q << (4u * piece);
+        oris |= (b & 1u) << piece;
+    });
+    if (big | (mask & ~seen) | (mask & twice)) return 0xffffffffu;
+    EdgeCoord c{0u, 0u};
+    uint32_t m = mask;
+    sfor<kEdgeMaxK>([&](auto ic) {
+        constexpr uint32_t i = decltype(ic)::value;
+        if (i < k) {
+            const uint32_t t = (uint32_t)__ffs((int)m) - 1u;              // t_i: m != 0 while i < k
+            m &= m - 1u;
+            c.pos |= (uint32_t)((where >> (4u * t)) & 15ull) << (4 * i);
+            c.ori |= ((oris >> t) & 1u) << i;
+        }
+    });
+    return edge_rank(c, k);
+}
+
 }  // namespace rc

@@ -9,6 +9,10 @@ classical admissible lower bound: h <= true distance, with the distance's parity
     table.levels                                  # states per distance, level 0 first
     table.distance(env)                           # uint8 [N]
     torch.save(table.table.cpu(), path); CornerTable(torch.load(path).cuda(), 2)
+
+The 3x3x3's corner table sees 8 of 20 cubies.  EdgeTable (include/rubikhip.h "Edge pattern databases", DESIGN.md "Edge pattern
+databases") is its companion over up to 7 tracked edge pieces, and MaxTable(corner, *edge_tables) the maximum of several tables --
+admissible and consistent like its members, and accepted by front="table" wherever a CornerTable is.
 """
 from __future__ import annotations
 
@@ -125,3 +129,173 @@ class CornerTable:
         legal corner state."""
         check(_pattern_lib.pattern_lib().rcp_score_keys(ptr(keys), n_problems, width, pitch, self.cube_size, ptr(self.table), self.table.numel(),
                                                         ptr(scores), stream_ptr(self.device)))
+
+
+class EdgeTable:
+    """An edge pattern database of the 3x3x3 (include/rubikhip.h "Edge pattern databases", DESIGN.md "Edge pattern databases"): the
+    exact number of quarter turns that bring up to 7 tracked edge pieces home, whatever the other cubies do -- an admissible,
+    consistent lower bound that sees what the corner table is blind to.
+
+        e = EdgeTable.build(range(6), "cuda")         # pieces 0..5: 42.6 MB, breadth-first, one launch per level
+        e.distance(env)                               # uint8 [N]
+        MaxTable(corner, e, EdgeTable.build(range(6, 12)))   # Korf's maximum, for front="table"
+
+    table: uint8 device tensor [N(k)]; mask / edges: the tracked pieces; levels: patterns per distance (None for a wrapped tensor)."""
+    cube_size = 3
+
+    def __init__(self, table, edges, levels=None, cube_size=3):
+        """Wrap a table built earlier.  ValueError for a tensor that cannot be one: wrong size, dtype or device are found before the
+        device is touched, table[home] != 0 by reading one byte."""
+        from . import _edge_lib
+        if cube_size != 3:
+            raise ValueError(f"edge tables exist for the 3x3x3 only (the 2x2x2 has no edges), got cube_size {cube_size!r}")
+        self.mask = _edge_lib.edge_mask(edges)
+        self.edges = tuple(e for e in range(_edge_lib.N_EDGES) if self.mask >> e & 1)
+        n = _edge_lib.table_bytes(self.mask)
+        if not isinstance(table, torch.Tensor) or table.dtype != torch.uint8 or table.dim() != 1 or table.numel() != n or not table.is_contiguous():
+            raise ValueError(f"an edge table of the pieces {self.edges} is a contiguous uint8 tensor of {n} entries, got "
+                             f"{tuple(table.shape) if isinstance(table, torch.Tensor) else type(table).__name__}"
+                             f"{' of ' + str(table.dtype) if isinstance(table, torch.Tensor) else ''}")
+        if not table.is_cuda:
+            raise ValueError(f"the table must live on a HIP device (there is no CPU fallback), got {table.device}")
+        if table.data_ptr() % 16:
+            raise ValueError("the table must start 16-byte aligned (a slice at an odd offset?)")
+        self.home = _edge_lib.home_index(self.mask)
+        if levels is None and int(table[self.home]) != 0:
+            raise ValueError(f"not an edge table of the pieces {self.edges}: table[{self.home}], the home pattern's distance, is not 0")
+        self.table, self.device = table, table.device
+        self.levels = None if levels is None else tuple(int(c) for c in levels)
+
+    @classmethod
+    def build(cls, edges, device="cuda", cube_size=3):
+        """Breadth-first over the index space: rce_build_begin, then one rce_build_level per distance until a level sets nothing (the
+        count is read back once per level)."""
+        from . import _edge_lib
+        if cube_size != 3:
+            raise ValueError(f"edge tables exist for the 3x3x3 only (the 2x2x2 has no edges), got cube_size {cube_size!r}")
+        mask = _edge_lib.edge_mask(edges)
+        n = _edge_lib.table_bytes(mask)
+        dev = torch.device(device)
+        if dev.type == "cuda" and dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        _lib.init(dev)
+        L = _edge_lib.edge_lib()
+        table = torch.empty(n, dtype=torch.uint8, device=dev)
+        count = torch.zeros(4, dtype=torch.int32, device=dev)  # one uint32, 16-byte aligned
+        _lib.check(L.rce_build_begin(ptr(table), n, mask, stream_ptr(dev)))
+        levels = [1]
+        for depth in range(MAX_LEVELS + 1):
+            _lib.check(L.rce_build_level(ptr(table), n, mask, depth, ptr(count), stream_ptr(dev)))
+            c = int(count[0])
+            if c == 0:
+                return cls(table, mask, levels)
+            levels.append(c)
+        raise RuntimeError(f"the edge table of mask {mask:#x} has more than {MAX_LEVELS} levels")
+
+    @property
+    def depth(self):
+        """The largest distance in the table (needs levels: a built table)."""
+        return None if self.levels is None else len(self.levels) - 1
+
+    def distance(self, cubes, n=None, pitch=None):
+        """uint8 [N]: table[index] of every cube (one rce_lookup launch); ILLEGAL = 0xFF where the edge bytes are no pattern.  cubes: a
+        VecCubeEnv (encoded to compact codes first), or a tiled RC_FMT_CODE / cubie buffer [tiles, 20, pitch] with n cubes (pitch
+        None: its last dimension)."""
+        from . import _edge_lib
+        if hasattr(cubes, "stickers"):
+            if cubes.cube_size != 3:
+                raise ValueError(f"the table is a 3x3x3's, the cubes are {cubes.cube_size}x{cubes.cube_size}x{cubes.cube_size}")
+            if cubes.stickers.device != self.device:
+                raise ValueError(f"the table is on {self.device}, the cubes on {cubes.stickers.device}")
+            n, pitch = cubes.num_envs, None
+            code = ops.alloc_code(n, 3, self.device, cubes.stickers.shape[-1])
+            ops.encode(cubes.stickers, n, 3, code, _lib.FMT_CODE)
+            cubes = code
+        if n is None:
+            raise ValueError("distance(rows, n): the number of cubes is required for a code or cubie buffer")
+        if cubes.device != self.device:
+            raise ValueError(f"the table is on {self.device}, the cubes on {cubes.device}")
+        p = ops._state_arg(cubes, 20, n, pitch, "distance rows")
+        out = torch.empty(_lib.pitch_for(max(n, 1), 16), dtype=torch.uint8, device=self.device)[:n]
+        _lib.init(self.device)
+        _lib.check(_edge_lib.edge_lib().rce_lookup(ptr(cubes), n, p, self.mask, ptr(self.table), self.table.numel(), ptr(out),
+                                                   stream_ptr(self.device)))
+        return out
+
+    def cubies(self, indices, out=None, cubie_pitch=None, bad=None):
+        """rce_unrank: pattern indices (any integer tensor or sequence; values >= N are flagged) -> the cubie rows of a reachable cube
+        with that pattern.  bad: the flag, a uint8 device tensor [1] the caller zeroes and reads; None: read back at once and raised
+        as IndexError."""
+        from . import _edge_lib
+        idx = torch.as_tensor(indices).to(self.device)
+        if idx.dim() != 1 or idx.dtype.is_floating_point:
+            raise ValueError("indices must be a 1-D integer tensor or sequence")
+        n = idx.numel()
+        if idx.dtype != torch.int32:                           # uint32 values in an int32 tensor (torch has no arithmetic on uint32)
+            if n and (int(idx.min()) < 0 or int(idx.max()) > 0xFFFFFFFF):
+                raise ValueError("indices must be in 0..2^32 - 1")
+            idx = torch.where(idx >= 1 << 31, idx - (1 << 32), idx).to(torch.int32)
+        buf = torch.empty(_lib.pitch_for(max(n, 1) * 4, 16) // 4, dtype=torch.int32, device=self.device)
+        buf[:n] = idx
+        if out is None:
+            out = ops.alloc_code(n, 3, self.device, cubie_pitch)
+        p = ops._state_arg(out, 20, n, cubie_pitch, "cubies out")
+        flag = torch.zeros(1, dtype=torch.uint8, device=self.device) if bad is None else ops._vec(bad, 1, torch.uint8, "cubies bad")
+        _lib.init(self.device)
+        _lib.check(_edge_lib.edge_lib().rce_unrank(ptr(buf), n, self.mask, ptr(out), p, ptr(flag), stream_ptr(self.device)))
+        if bad is None and int(flag):
+            raise IndexError(f"edge pattern index out of range 0..{self.table.numel() - 1}")
+        return out
+
+    def states(self, indices):
+        """Tiled sticker states [tiles, S, pitch] of the patterns `indices` (rce_unrank, then ops.from_cubies): corners home, the
+        untracked edges in ascending order, adjusted so that the cube is reachable."""
+        cub = self.cubies(indices)
+        return ops.from_cubies(cub, len(indices), 3, bad=torch.zeros(1, dtype=torch.uint8, device=self.device))
+
+    def score_codes(self, code, n_problems, width, pitch, scores, combine=0):
+        """rce_score_codes: over every slot of rc_search_expand's candidate code buffer, scores[j] = -table[index] (combine 0) or the
+        lesser of that and what scores[j] holds (combine 1); -255 for an illegal row set."""
+        from . import _edge_lib
+        _lib.check(_edge_lib.edge_lib().rce_score_codes(ptr(code), n_problems, width, pitch, self.mask, ptr(self.table), self.table.numel(),
+                                                        ptr(scores), int(combine), stream_ptr(self.device)))
+
+
+class MaxTable:
+    """The maximum of pattern databases, Korf's heuristic: MaxTable(corner, *edge_tables), corner a CornerTable of the 3x3x3 or None.
+    Every member is admissible and consistent, so their maximum is; front="table" takes it wherever it takes a CornerTable.
+    ValueError for no table at all, a member that is no table, or members on different devices -- before any launch."""
+    cube_size = 3
+
+    def __init__(self, corner=None, *edge_tables):
+        if corner is not None and not isinstance(corner, CornerTable):
+            raise ValueError(f"MaxTable(corner, *edge_tables): corner is a pattern.CornerTable or None, got {type(corner).__name__}")
+        for e in edge_tables:
+            if not isinstance(e, EdgeTable):
+                raise ValueError(f"MaxTable(corner, *edge_tables): every further member is a pattern.EdgeTable, got {type(e).__name__}")
+        if corner is not None and corner.cube_size != 3:
+            raise ValueError(f"MaxTable is the 3x3x3's (the 2x2x2 has no edges); the corner table is a {corner.cube_size}x{corner.cube_size}x{corner.cube_size}'s")
+        members = ([corner] if corner is not None else []) + list(edge_tables)
+        if not members:
+            raise ValueError("MaxTable needs at least one table")
+        if any(m.device != members[0].device for m in members):
+            raise ValueError(f"the tables of a MaxTable must live on one device, got {[str(m.device) for m in members]}")
+        self.corner, self.edge_tables, self.device = corner, tuple(edge_tables), members[0].device
+
+    def distance(self, env):
+        """uint8 [N]: the element-wise maximum of the members' distances (0xFF, illegal, wins)."""
+        parts = ([self.corner.distance(env)] if self.corner is not None else []) + [e.distance(env) for e in self.edge_tables]
+        out = parts[0]
+        for p in parts[1:]:
+            out = torch.maximum(out, p)
+        return out
+
+    def score(self, keys, code, n_problems, width, pitch, scores):
+        """scores = -max over the members, over every candidate slot: rcp_score_keys for the corner table (it writes), then one
+        rce_score_codes(combine=1) per edge table; without a corner table the first edge table writes (combine=0)."""
+        wrote = self.corner is not None
+        if wrote:
+            self.corner.score_keys(keys, n_problems, width, pitch, scores)
+        for e in self.edge_tables:
+            e.score_codes(code, n_problems, width, pitch, scores, combine=int(wrote))
+            wrote = True

@@ -13,6 +13,8 @@ the candidate codes into a [chunk, H1] buffer, and the rest of the encoder and t
 front="table" (DESIGN.md "Corner pattern database") replaces it by ONE launch and no net: the `model` is a pattern.CornerTable and
 rcp_score_keys writes scores = -table[corner index] from the candidate keys.  In astar_search it also adds rcp_relax after rca_merge (an
 open node reached again by fewer moves takes the lower g): with batch = 1 and weight = 1 the table-guided search is A* proper.
+On the 3x3x3 the `model` may also be a pattern.MaxTable (DESIGN.md "Edge pattern databases"): the maximum of a corner table and edge
+tables, one rce_score_codes(combine=1) launch per edge table over the candidate codes after rcp_score_keys.
 
 astar_search / AStarPlan (DESIGN.md "A* search"): batch-weighted A* around the same expand and score.  Per cube a persistent node pool
 with an exact hash set; an iteration is rca_pop (the B best open nodes -> the beam), rc_search_expand, the score above, rca_merge (the
@@ -151,6 +153,8 @@ class BeamPlan:
     def score_table(self, table):
         """scores = -table[corner index] of every candidate KEY: one rcp_score_keys launch over all A * NBp slots, no net."""
         _check_table(table, self.cs, self.keys.device)
+        if hasattr(table, "edge_tables"):                      # a pattern.MaxTable: the maximum, one further launch per edge table
+            return table.score(self.keys, self.code, self.P, self.W, self.pitch, self.scores)
         table.score_keys(self.keys, self.P, self.W, self.pitch, self.scores)
 
     def select(self):
@@ -180,10 +184,10 @@ class BeamPlan:
 
 
 def _check_table(table, cube_size, device=None):
-    """front="table": the ValueErrors of a `model` that is no CornerTable of this cube size on this device (before any launch; the
-    device is looked at last, and only where one is given)."""
-    from .pattern import CornerTable
-    if not isinstance(table, CornerTable):
+    """front="table": the ValueErrors of a `model` that is no CornerTable (or MaxTable, the 3x3x3's maximum of a corner table and edge
+    tables) of this cube size on this device (before any launch; the device is looked at last, and only where one is given)."""
+    from .pattern import CornerTable, MaxTable
+    if not isinstance(table, (CornerTable, MaxTable)):
         raise ValueError(f"front='table' scores with a pattern.CornerTable in the model position, got {type(table).__name__}")
     if table.cube_size != cube_size:
         raise ValueError(f"front='table': the table is a {table.cube_size}x{table.cube_size}x{table.cube_size}'s, the cubes are "

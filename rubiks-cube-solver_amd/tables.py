@@ -527,3 +527,13 @@ def get_corner_moves(cube_size: int):
     t, cb = get_tables(cube_size), get_cubies(cube_size)
     cub = cb.cubies(t.solved[t.perm.astype(np.int64)])[0][:, :cb.nc]
     return (cub // 3).astype(np.uint8), (cub % 3).astype(np.uint8)
+
+
+def get_edge_moves():
+    """(src, flip) uint8 [A][NE] of the 3x3x3: how a move acts on the edge state (piece[q], ori[q]) of the cubie rule above
+    (include/rubikhip.h "Edge pattern databases"): piece'[q] = piece[src[a][q]], ori'[q] = ori[src[a][q]] ^ flip[a][q], where
+    2 * src[a][q] + flip[a][q] is the edge byte of slot q after move a on the solved cube (moves gather: state[perm[a]]).  The
+    2x2x2 has no edges."""
+    t, cb = get_tables(3), get_cubies(3)
+    cub = cb.cubies(t.solved[t.perm.astype(np.int64)])[0][:, cb.nc:]
+    return (cub // 2).astype(np.uint8), (cub % 2).astype(np.uint8)

@@ -238,6 +238,11 @@ class VecCubeEnv:
         solution length on the 2x2x2, an admissible lower bound with the right parity on the 3x3x3; 0xFF for illegal corners."""
         return table.distance(self)
 
+    def edge_distance(self, table):
+        """uint8 [N]: the exact distance of every cube's tracked EDGE pieces from a pattern.EdgeTable (3x3x3; one encode and one
+        rce_lookup launch), an admissible lower bound on the cube's; a pattern.MaxTable gives the maximum over its members."""
+        return table.distance(self)
+
     def from_cubies(self, cubies):
         """Set every cube from its cubie bytes: [N, SLOTS] rows (host or device) or a tiled cubie tensor as cubies() returns it.  The
         assembly need not be legal (legality() tells); a byte that names no (piece, orientation) raises ValueError and the env keeps
