@@ -485,6 +485,71 @@ int rce_lookup(const uint8_t *rows, int64_t n, int64_t pitch, int mask, const ui
 int rce_score_codes(const uint8_t *code, int64_t n_problems, int width, int64_t pitch, int mask, const uint8_t *table, int64_t bytes,
                     float *scores, int combine, void *stream);
 
+/* ---------------------------------------------------------------------------------------------------------------------------------
+ * Subgroup chain (prefix rct_): Thistlethwaite's chain <all> > <U,D,R,L,F2,B2> > <U,D,F2,R2,B2,L2> > <half turns> > {solved} as four
+ * exact coset-distance tables and a descent that goes downhill in each: a solution of ANY legal cube without a search and without a
+ * net, at most 47 generators = 87 quarter turns long.  3x3x3 ONLY: no entry point takes a cube_size.  No reference counterpart.
+ *
+ * THE RULE.  Cubie bytes as in the rcc_* section: corner slots 0..7 hold piece cp[q] with ori co[q], edge slots 0..11 hold ep[q] with
+ * eo[q]; lehmer as defined there; a subset's rank is the lexicographic rank of its sorted slot tuple.
+ *   stage 0   domain: every cube.  index = sum_{q<11} eo[q] * 2^q, N = 2048, goal 0.  Generators, in this order: the 12 actions 0..11.
+ *   stage 1   domain: all 12 eo = 0.  index = sum_{q<7} co[q] * 3^q + 2187 * C, C = the rank among the 495 4-subsets of {0..11} of the
+ *             slots that hold pieces 8..11; N = 1 082 565; goal: twist 0, C = 494.  Generators: U, U', F2, R, R', D, D', B2, L, L'.
+ *   stage 2   domain: stage 1's goal set (all eo and co 0, pieces 8..11 in slots 8..11).  index = lehmer(cp) + 40320 * E, E = the rank
+ *             among the 70 4-subsets of {0..7} of the slots that hold pieces {0, 2, 4, 6}; N = 2 822 400; goals: the 96 entries
+ *             (h, E_home), h in H = the corner permutations half turns reach (rct_corner_cosets), E_home = 20 = the rank of (0, 2, 4, 6).
+ *             Generators: U, U', F2, R2, D, D', B2, L2.
+ *   stage 3   domain: stage 2's goal set.  index = ((r * 24 + m) * 24 + s) * 24 + e: r = the rank of lehmer(cp) in sorted H, m = the
+ *             lehmer of (ep[0], ep[2], ep[4], ep[6]) / 2, s = that of ((ep[1], ep[3], ep[5], ep[7]) - 1) / 2, e = that of ep[8..11] - 8;
+ *             N = 1 327 104; goal: the solved cube, index 0.  Generators: U2, F2, R2, D2, B2, L2.  The 663 552 entries whose corner
+ *             and edge permutations differ in parity belong to no cube and stay 0xFF.
+ *   table     table[i] = the least number of the stage's generators (a half turn counts one) that bring coset i to a goal.
+ *   descent   at distance d > 0 take the FIRST generator of the stage's order whose child reads d - 1, emit its one or two quarter-turn
+ *             actions (a half turn is the clockwise action twice), repeat until 0.  At most 16 generators are taken per call.
+ *   guard     every table address passes one guard (idx < N ? table[idx] : 0xFF); the host checks bytes >= N.
+ * status, one byte per cube of rct_descend (0: fine; a cube with a nonzero status is not moved, but for RCT_STUCK): */
+#define RCT_ILLEGAL 1u   /* a byte names no cubie (>= 24), or a piece occurs twice */
+#define RCT_OUTSIDE 2u   /* the cube is not in the stage's domain, or its entry is 0xFF */
+#define RCT_NO_ROOM 4u   /* length < 0 or length + 2 * d > max_length: the cube is not walked */
+#define RCT_STUCK 8u     /* no child is one closer, or the walk is not home after 16 generators: the table is not this stage's.  The
+                            walk stops where it is; what it took so far is written */
+/* Conventions as in the rce_* section: caller-owned device memory, stream-ordered, nothing allocated, nothing synchronises; RC_EINVAL
+ * before any launch (rc_last_error names the operand) for a stage outside 0..3, a table smaller than N, a NULL or misaligned pointer,
+ * a negative size; pad columns and every byte outside the rows keep their bytes; n == 0 succeeds without a launch; every pointer
+ * needs 16-byte alignment and no more.
+ *
+ * Host only, no device: N of a stage (-1 for a bad stage); its generators, gens [12][2] = the one or two actions of each (0xFF: none,
+ * also in the rows from *count on); sorted H, h [96].  Any pointer may be NULL. */
+int64_t rct_table_bytes(int stage);
+int rct_generators(int stage, uint8_t *gens, int *count);
+int rct_corner_cosets(uint16_t *h);
+/* Breadth-first build, one launch per level, as rce_build_*.  rct_build_begin: every entry 0xFF, the goals 0 (one fill kernel).
+ * rct_build_level: an entry still 0xFF becomes depth + 1 iff one of its neighbours under the stage's generators holds `depth` (the
+ * generator sets are closed under inversion); *count (one device uint32, 16-byte aligned, zeroed by the call) receives how many were
+ * set.  Each lane writes its own entry only.  The table is complete when a level sets nothing.  depth in 0..253. */
+int rct_build_begin(uint8_t *table, int64_t bytes, int stage, void *stream);
+int rct_build_level(uint8_t *table, int64_t bytes, int stage, int depth, uint32_t *count, void *stream);
+/* index[c] (uint32) = the stage's index of the cubie rows ([tiles][20][cubie_pitch], rcc_* layout) of cube c; 0xFFFFFFFF for an
+ * illegal row set (RCT_ILLEGAL's rule) and for a cube outside the stage's domain.  The twist, flip and parity sums are NOT looked at:
+ * that is rcc_cubies' status. */
+int rct_index(const uint8_t *cubies, int64_t n, int64_t cubie_pitch, int stage, uint32_t *index, void *stream);
+/* indices [n] (uint32) -> the 20 cubie rows of a REACHABLE cube of the stage's domain with that index.  What the index leaves free:
+ *   stage 0   every piece home, co 0, eo[11] closes the flip sum;
+ *   stage 1   corners home, co[7] closes the twist, eo 0; pieces 8..11 fill the subset's slots and pieces 0..7 the other slots, both
+ *             ascending; then, if the edge permutation is odd, the edges of the two highest slots outside the subset trade places;
+ *   stage 2   co, eo 0; pieces 0, 2, 4, 6 fill the subset's slots and 1, 3, 5, 7 the other slots of 0..7, both ascending, 8..11 home;
+ *             then, if the corner and edge permutations differ in parity, the edges of slots 10 and 11 trade places;
+ *   stage 3   nothing.
+ * An index >= N, and a stage-3 index whose permutations differ in parity, is written as the solved cube and sets *bad (one device
+ * byte the caller zeroes and reads, required). */
+int rct_unrank(const uint32_t *indices, int64_t n, int stage, uint8_t *cubies, int64_t cubie_pitch, uint8_t *bad, void *stream);
+/* The walk of one stage, in place, one launch: cube c's rows are moved to the stage's goal set, its quarter turns are appended to
+ * column c of actions [max_length][act_pitch] (uint8; act_pitch % 16 == 0, act_pitch >= n) from row length[c] on, and length[c]
+ * (int32) advances; rows past the new length keep their bytes (the caller prefills the no-op 12).  moves[c] = the table value at
+ * entry, 0xFF for an illegal cube or one outside the domain; status[c] as above.  max_length >= 1. */
+int rct_descend(uint8_t *cubies, int64_t n, int64_t cubie_pitch, int stage, const uint8_t *table, int64_t bytes, uint8_t *actions,
+                int max_length, int64_t act_pitch, int32_t *length, uint8_t *moves, uint8_t *status, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -299,3 +299,137 @@ class MaxTable:
         for e in self.edge_tables:
             e.score_codes(code, n_problems, width, pitch, scores, combine=int(wrote))
             wrote = True
+
+
+class ChainTables:
+    """The four coset-distance tables of Thistlethwaite's subgroup chain (include/rubikhip.h "Subgroup chain", DESIGN.md "Subgroup
+    chain"): <all> > <U,D,R,L,F2,B2> > <U,D,F2,R2,B2,L2> > <half turns> > {solved}.  3x3x3 only, 5.2 MB in all; search.chain_solve
+    walks any legal cube home through them, without a net and without a search, in at most 87 quarter turns.
+
+        chain = ChainTables.build("cuda")             # breadth-first, one launch per level
+        chain.levels[2], chain.depth[2]               # cosets per distance of stage 2, its largest distance
+        chain.distance(env, 0)                        # uint8 [N]: generators to stage 0's goal; 0xFF outside the stage's domain
+        chain_solve(chain, env)["length"]
+
+    tables: four uint8 device tensors [N(stage)]; levels / depth: per stage (None for wrapped tensors)."""
+    cube_size = 3
+
+    def __init__(self, tables, levels=None, cube_size=3):
+        """Wrap tables built earlier.  ValueError for tensors that cannot be them: a wrong count, size, dtype or device -- found
+        before the device is touched."""
+        from . import _chain_lib
+        if cube_size != 3:
+            raise ValueError(f"the subgroup chain exists for the 3x3x3 only, got cube_size {cube_size!r}")
+        tables = tuple(tables)
+        if len(tables) != _chain_lib.STAGES:
+            raise ValueError(f"a chain has {_chain_lib.STAGES} tables, got {len(tables)}")
+        for s, t in enumerate(tables):
+            n = _chain_lib.table_bytes(s)
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.dim() != 1 or t.numel() != n or not t.is_contiguous():
+                raise ValueError(f"the table of stage {s} is a contiguous uint8 tensor of {n} entries, got "
+                                 f"{tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__}"
+                                 f"{' of ' + str(t.dtype) if isinstance(t, torch.Tensor) else ''}")
+            if not t.is_cuda:
+                raise ValueError(f"the tables must live on a HIP device (there is no CPU fallback), got {t.device}")
+            if t.device != tables[0].device:
+                raise ValueError(f"the tables of a chain must live on one device, got {[str(x.device) for x in tables]}")
+            if t.data_ptr() % 16:
+                raise ValueError("every table must start 16-byte aligned (a slice at an odd offset?)")
+        self.tables, self.device = tables, tables[0].device
+        self.levels = None if levels is None else tuple(tuple(int(c) for c in lv) for lv in levels)
+
+    @classmethod
+    def build(cls, device="cuda", cube_size=3):
+        """Breadth-first over each stage's index space: rct_build_begin, then one rct_build_level per distance until a level sets
+        nothing (the count is read back once per level)."""
+        from . import _chain_lib
+        if cube_size != 3:
+            raise ValueError(f"the subgroup chain exists for the 3x3x3 only, got cube_size {cube_size!r}")
+        dev = torch.device(device)
+        if dev.type == "cuda" and dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        _lib.init(dev)
+        L = _chain_lib.chain_lib()
+        count = torch.zeros(4, dtype=torch.int32, device=dev)  # one uint32, 16-byte aligned
+        tables, levels = [], []
+        for stage in range(_chain_lib.STAGES):
+            n = _chain_lib.table_bytes(stage)
+            table = torch.empty(n, dtype=torch.uint8, device=dev)
+            _lib.check(L.rct_build_begin(ptr(table), n, stage, stream_ptr(dev)))
+            lv = [int((table == 0).sum())]
+            for depth in range(MAX_LEVELS + 1):
+                _lib.check(L.rct_build_level(ptr(table), n, stage, depth, ptr(count), stream_ptr(dev)))
+                c = int(count[0])
+                if c == 0:
+                    break
+                lv.append(c)
+            else:
+                raise RuntimeError(f"the table of stage {stage} has more than {MAX_LEVELS} levels")
+            tables.append(table)
+            levels.append(lv)
+        return cls(tables, levels)
+
+    @property
+    def depth(self):
+        """The largest distance of each table (needs levels: built tables)."""
+        return None if self.levels is None else tuple(len(lv) - 1 for lv in self.levels)
+
+    def _cubie_arg(self, cubes, n, pitch, what):
+        """(cubie buffer, n, pitch) of a VecCubeEnv (one rcc_cubies launch) or of a tiled cubie buffer [tiles, 20, pitch] with n cubes."""
+        if hasattr(cubes, "stickers"):
+            if cubes.cube_size != 3:
+                raise ValueError(f"the chain is a 3x3x3's, the cubes are {cubes.cube_size}x{cubes.cube_size}x{cubes.cube_size}")
+            if cubes.stickers.device != self.device:
+                raise ValueError(f"the tables are on {self.device}, the cubes on {cubes.stickers.device}")
+            n, pitch = cubes.num_envs, None
+            cubes = ops.cubies(cubes.stickers, n, 3, status=False)["cubies"]
+        if n is None:
+            raise ValueError(f"{what}(cubies, stage, n): the number of cubes is required for a cubie buffer")
+        if cubes.device != self.device:
+            raise ValueError(f"the tables are on {self.device}, the cubes on {cubes.device}")
+        return cubes, n, ops._state_arg(cubes, 20, n, pitch, f"{what} cubies")
+
+    def index(self, cubes, stage, n=None, pitch=None):
+        """int64 [N]: the stage's index of every cube (one rct_index launch), -1 for an illegal row set and for a cube outside the
+        stage's domain.  cubes: a VecCubeEnv, or a tiled cubie buffer [tiles, 20, pitch] with n cubes."""
+        from . import _chain_lib
+        stage = _chain_lib.check_stage(stage)
+        cubes, n, p = self._cubie_arg(cubes, n, pitch, "index")
+        out = torch.empty(_lib.pitch_for(max(n, 1) * 4, 16) // 4, dtype=torch.int32, device=self.device)[:n]
+        _lib.init(self.device)
+        _lib.check(_chain_lib.chain_lib().rct_index(ptr(cubes), n, p, stage, ptr(out), stream_ptr(self.device)))
+        return out.to(torch.int64)                             # all-ones, the uint32 of an int32 tensor, is -1
+
+    def distance(self, cubes, stage, n=None, pitch=None):
+        """uint8 [N]: the stage's generators between every cube and the stage's goal set, ILLEGAL = 0xFF where index() is -1 and for
+        a stage-3 entry no cube has."""
+        idx = self.index(cubes, stage, n, pitch)
+        t = self.tables[stage]
+        d = t[idx.clamp(0, t.numel() - 1)]
+        return torch.where(idx < 0, torch.full_like(d, ILLEGAL), d)
+
+    def cubies(self, indices, stage, out=None, cubie_pitch=None, bad=None):
+        """rct_unrank: a stage's indices (any integer tensor or sequence) -> the cubie rows of a reachable cube of its domain with
+        that index.  An index >= N and a stage-3 index of the wrong parity are flagged.  bad: the flag, a uint8 device tensor [1] the
+        caller zeroes and reads; None: read back at once and raised as IndexError."""
+        from . import _chain_lib
+        stage = _chain_lib.check_stage(stage)
+        idx = torch.as_tensor(indices).to(self.device)
+        if idx.dim() != 1 or idx.dtype.is_floating_point:
+            raise ValueError("indices must be a 1-D integer tensor or sequence")
+        n = idx.numel()
+        if idx.dtype != torch.int32:                           # uint32 values in an int32 tensor (torch has no arithmetic on uint32)
+            if n and (int(idx.min()) < 0 or int(idx.max()) > 0xFFFFFFFF):
+                raise ValueError("indices must be in 0..2^32 - 1")
+            idx = torch.where(idx >= 1 << 31, idx - (1 << 32), idx).to(torch.int32)
+        buf = torch.empty(_lib.pitch_for(max(n, 1) * 4, 16) // 4, dtype=torch.int32, device=self.device)
+        buf[:n] = idx
+        if out is None:
+            out = ops.alloc_code(n, 3, self.device, cubie_pitch)
+        p = ops._state_arg(out, 20, n, cubie_pitch, "cubies out")
+        flag = torch.zeros(1, dtype=torch.uint8, device=self.device) if bad is None else ops._vec(bad, 1, torch.uint8, "cubies bad")
+        _lib.init(self.device)
+        _lib.check(_chain_lib.chain_lib().rct_unrank(ptr(buf), n, stage, ptr(out), p, ptr(flag), stream_ptr(self.device)))
+        if bad is None and int(flag):
+            raise IndexError(f"stage {stage}: an index is out of range 0..{self.tables[stage].numel() - 1} or names no cube")
+        return out

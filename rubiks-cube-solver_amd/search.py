@@ -523,3 +523,60 @@ def astar_solve_percentage(model, cube_size, sample_scramble_count, sample_cube_
         _check_table(model, cube_size)                         # before the cubes are scrambled on the device
     return _solve_percentage(lambda env: astar_search(model, env, batch, max_iterations, weight=weight, capacity=capacity, graph=graph,
                                                       front=front), cube_size, sample_scramble_count, sample_cube_count, device, seeds)
+
+
+def chain_solve(tables, env, graph=False):
+    """Solve every cube of a 3x3x3 env by Thistlethwaite's subgroup chain (include/rubikhip.h "Subgroup chain", DESIGN.md "Subgroup
+    chain"): rcc_cubies once, then one rct_descend per stage of `tables`, a pattern.ChainTables -- no net, no search, at most 87
+    quarter turns.  The env is left as it is.  A cube whose legality() is nonzero is not walked: between the two, one mask sets its
+    entry length to -1, which rct_descend refuses.
+
+    Returns dict(solved bool [P], length int32 [P] (-1: not solved), actions uint8 [L, P] (padded with the no-op 12; L = max(1,
+    length.max())), stage_moves uint8 [4, P] (each table's value at entry, 0xFF where the stage did not see the cube in its domain),
+    status uint8 [P] (the OR of the stages' RCT_* bytes; RCT_ILLEGAL alone for an illegal cube)).
+    graph=True captures the launches in one hipGraph and replays it."""
+    from . import _chain_lib
+    from .pattern import ChainTables
+    if not isinstance(tables, ChainTables):
+        raise ValueError(f"chain_solve(tables, env): tables is a pattern.ChainTables, got {type(tables).__name__}")
+    if not hasattr(env, "stickers") or env.cube_size != 3:
+        raise ValueError(f"chain_solve needs a 3x3x3 VecCubeEnv, got {'a ' + str(env.cube_size) + 'x' + str(env.cube_size) + 'x' + str(env.cube_size) + ' one' if hasattr(env, 'cube_size') else type(env).__name__}")
+    if env.stickers.device != tables.device:
+        raise ValueError(f"the tables are on {tables.device}, the cubes on {env.stickers.device}")
+    n, dev, ML = env.num_envs, tables.device, _chain_lib.MAX_LENGTH
+    vec = lambda dtype, rows=1: torch.empty((rows, _lib.pitch_for(n, 16)), dtype=dtype, device=dev)
+    cub = ops.alloc_code(n, 3, dev, env.stickers.shape[-1])
+    legal, length = vec(torch.uint8)[0], vec(torch.int32)[0]
+    actions, moves, status = vec(torch.uint8, ML), vec(torch.uint8, 4), vec(torch.uint8, 4)
+    p_c, ap = ops._state_arg(cub, 20, n, None, "chain_solve cubies"), actions.shape[1]
+    _lib.init(dev)
+    L = _chain_lib.chain_lib()
+
+    def launches():
+        ops.cubies(env.stickers, n, 3, cubies=cub, status=legal)
+        actions.fill_(12)                                      # fill kernels, no memset: a captured memset is not replayed in order
+        length.copy_(legal.ne(0).to(torch.int32).neg())
+        for s in range(_chain_lib.STAGES):
+            _lib.check(L.rct_descend(ptr(cub), n, p_c, s, ptr(tables.tables[s]), tables.tables[s].numel(), ptr(actions), ML, ap, ptr(length),
+                                     ptr(moves[s]), ptr(status[s]), stream_ptr(dev)))
+
+    if graph:
+        side = torch.cuda.Stream(dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(side):
+            launches()                                         # warm-up outside the capture
+        torch.cuda.current_stream(dev).wait_stream(side)
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            launches()
+        g.replay()
+    else:
+        launches()
+    bad = legal[:n] != 0
+    st = status[0, :n] | status[1, :n] | status[2, :n] | status[3, :n]
+    st = torch.where(bad, torch.full_like(st, _chain_lib.ILLEGAL), st)
+    solved = st == 0
+    out_len = torch.where(solved, length[:n], torch.full_like(length[:n], -1))
+    rows = max(1, int(out_len.max()))
+    acts = torch.where(solved[None, :], actions[:rows, :n], torch.full_like(actions[:rows, :n], 12))
+    return dict(solved=solved, length=out_len, actions=acts.contiguous(), stage_moves=moves[:, :n].contiguous(), status=st)

@@ -27,6 +27,7 @@ from __future__ import annotations
 
 import functools
 import itertools
+import math
 from dataclasses import dataclass
 
 import numpy as np
@@ -537,3 +538,51 @@ def get_edge_moves():
     t, cb = get_tables(3), get_cubies(3)
     cub = cb.cubies(t.solved[t.perm.astype(np.int64)])[0][:, cb.nc:]
     return (cub // 2).astype(np.uint8), (cub % 2).astype(np.uint8)
+
+
+# ---- the subgroup chain (include/rubikhip.h "Subgroup chain", prefix rct_): <all> > <U,D,R,L,F2,B2> > <U,D,F2,R2,B2,L2> > <half turns> > {solved}
+CHAIN_SIZES = (2048, 2187 * 495, 40320 * 70, 96 * 24 ** 3)
+CHAIN_NO_ACTION = 0xFF
+_CHAIN_QUARTER = ((0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11), (0, 1, 4, 5, 6, 7, 10, 11), (0, 1, 6, 7), ())   # quarter turns of each stage; the other faces turn by halves
+
+
+@dataclass(frozen=True)
+class ChainData:
+    sizes: tuple  # N of the four coset tables
+    generators: tuple  # per stage uint8 [count][2]: the one or two quarter-turn actions of each generator, in the rule's order (0xFF: none)
+    gen_codes: np.ndarray  # uint8 [4][12]  action + 16 * (half turn), 0xFF beyond the stage's count (rc_tables.h chain_gen)
+    corner_cosets: np.ndarray  # uint16 [96]  H: lehmer(cp) of the corner permutations half turns reach, ascending
+
+
+def _lehmer(p):
+    n = len(p)
+    return sum(sum(p[r] < p[q] for r in range(q + 1, n)) * math.factorial(n - 1 - q) for q in range(n))
+
+
+@functools.lru_cache(maxsize=None)
+def get_chain() -> ChainData:
+    """The generated data of the subgroup chain (3x3x3 only): the generator lists and H, the corner permutations reachable from
+    solved by half turns, found by closure under get_corner_moves' half turns."""
+    gens, codes = [], np.full((4, 12), CHAIN_NO_ACTION, np.uint8)
+    for stage, quarter in enumerate(_CHAIN_QUARTER):
+        rows = []
+        for a in range(12):
+            if a in quarter:
+                rows.append((a, CHAIN_NO_ACTION))
+            elif a % 2 == 0:                                                   # a half turn: the clockwise action twice
+                rows.append((a, a))
+        gens.append(np.array(rows, np.uint8))
+        codes[stage, :len(rows)] = [a + 16 * (b != CHAIN_NO_ACTION) for a, b in rows]
+    src = get_corner_moves(3)[0].astype(np.int64)
+    half = [src[a][src[a]] for a in range(0, 12, 2)]
+    seen, todo = {tuple(range(8))}, [tuple(range(8))]
+    while todo:
+        p = np.array(todo.pop())
+        for h in half:
+            q = tuple(int(x) for x in p[h])
+            if q not in seen:
+                seen.add(q)
+                todo.append(q)
+    h = np.array(sorted(_lehmer(p) for p in seen), np.uint16)
+    assert len(h) == 96
+    return ChainData(sizes=CHAIN_SIZES, generators=tuple(gens), gen_codes=codes, corner_cosets=h)

@@ -243,6 +243,11 @@ class VecCubeEnv:
         rce_lookup launch), an admissible lower bound on the cube's; a pattern.MaxTable gives the maximum over its members."""
         return table.distance(self)
 
+    def chain_solve(self, tables, graph=False):
+        """search.chain_solve(tables, self): every cube solved through a pattern.ChainTables (3x3x3 only); the env is left as it is."""
+        from .search import chain_solve
+        return chain_solve(tables, self, graph=graph)
+
     def from_cubies(self, cubies):
         """Set every cube from its cubie bytes: [N, SLOTS] rows (host or device) or a tiled cubie tensor as cubies() returns it.  The
         assembly need not be legal (legality() tells); a byte that names no (piece, orientation) raises ValueError and the env keeps
