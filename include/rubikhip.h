@@ -550,6 +550,74 @@ int rct_unrank(const uint32_t *indices, int64_t n, int stage, uint8_t *cubies, i
 int rct_descend(uint8_t *cubies, int64_t n, int64_t cubie_pitch, int stage, const uint8_t *table, int64_t bytes, uint8_t *actions,
                 int max_length, int64_t act_pitch, int32_t *length, uint8_t *moves, uint8_t *status, void *stream);
 
+/* ---------------------------------------------------------------------------------------------------------------------------------
+ * Iterative-deepening A* (prefix ida_): Korf's cost-bounded depth-first search under the pattern databases above -- the OPTIMAL
+ * solution of a cube with no node memory: a cube's whole search is a trail of moves, a depth and a bound.  3x3x3 ONLY.  No reference
+ * counterpart.  The prefix does not start with "rc": every export of this library that does belongs to one of the sections above,
+ * whose lists are closed; a section of further names is the only kind they admit.
+ *
+ * THE RULE.
+ *   state       the 20 cubie bytes of the rcc_* section.  Move a acts by the corner and edge move tables (rcp_tables, rce_tables); a ^ 1
+ *               undoes a.  A cube is the goal iff all 20 bytes are the solved cube's.
+ *   heuristic   h(x) = the maximum over the tables given: at most one corner table (index = corner_index, as rcp_*) and 0..4 edge
+ *               tables, each with its mask (index as rce_*); h = 0 with no table.  Every table address passes the one guard of its
+ *               section (idx < N ? table[idx] : 0xFF); the host checks bytes >= N.
+ *   canonical   after a path ending ..., p2, p1 move m is skipped iff m == p1 ^ 1, or m == p1 and m is odd (a half turn is the even
+ *               action twice), or m == p1 == p2, or (m >> 1) + 3 == (p1 >> 1) (faces f and f + 3 commute: U/D, F/B, R/L; the lower
+ *               face goes first).  ida_canonical gives the mask.  12, 114, 1068, 10 011, 93 840, ... sequences of length 1, 2, ...
+ *   iteration   at `bound`, depth-first from the start node, moves in the order 0..11.  Every generated child y at depth g + 1 counts
+ *               one in nodes; f = g + 1 + h(y).  f > bound: next = min(next, f), the child is dropped.  Otherwise, y the goal: SOLVED,
+ *               length = g + 1, the trail is the solution.  Otherwise descend into y.  The iteration exhausted: next > limit gives
+ *               EXHAUSTED (next stays readable, a proven lower bound), otherwise bound = next, next = +inf = 2^31 - 1, and the search
+ *               starts again from the start node.  First bound = floor + h(start); a first bound above the limit is EXHAUSTED with
+ *               next = that bound.  A start node that is the goal: SOLVED, length = floor, nodes = 0.  The answer of a SOLVED cube is
+ *               therefore unique: the first optimal solution in this order, with this count of nodes.
+ *   limit       limit[c] counts as min(limit[c], max_depth): a trail never outgrows the rows of path.
+ *   frame       caller-owned, per cube c; nothing lives in the library.
+ *                 path    uint8 [max_depth][path_pitch], max_depth <= 32, path_pitch % 16 == 0, path_pitch >= n.  path[0..floor) is a
+ *                         prefix the caller wrote; the start node is the root moved by it, the search never goes above it, and the
+ *                         canonical rule looks at its last two moves.  A SOLVED cube's rows floor..length-1 receive the solution; no
+ *                         other row is ever written (the caller prefills 12, the no-op).
+ *                 floor   int32, may be NULL (= 0);  limit  int32.
+ *                 trail   uint64 [n][2]: nibble i (of 32) = move i of the path from the root to the current node, prefix included.
+ *                         The trail, not path, carries a running search from call to call: rows of path written at one budget's
+ *                         cuts and not at another's would break the invariance below.
+ *                 cursor  uint8: the least move not yet tried at the current node (0..12).
+ *                 depth, bound, next  int32;  nodes  uint64;  status  uint8, 0 = running, else the bits below.
+ *               The root cubies are an input and are never written: a call rebuilds the current node by replaying trail[0..depth).  A
+ *               cube with a nonzero status is not touched again.  After SOLVED length = depth.
+ *   budget      ida_search advances every running cube by at most max_steps passes.  A pass generates one child (dropped, entered or
+ *               the goal), or goes back one level (the inverse of the last move is applied; at the start node: the iteration ends as
+ *               above).  The kernel's only loop is bounded by max_steps; no loop's trip count depends on what a table holds.
+ *   invariance  the frame after k passes in all depends on the inputs alone, not on how the calls cut the k. */
+#define IDA_SOLVED 1u
+#define IDA_EXHAUSTED 2u
+#define IDA_ILLEGAL 4u     /* a cubie byte >= 24, a piece twice, or a table read 0xFF */
+#define IDA_BAD_FRAME 8u   /* floor, depth or cursor out of range, bound above the limit, a prefix or trail move >= 12 */
+/* Conventions as in the rct_* section: caller-owned device memory, stream-ordered, nothing allocated, nothing synchronises; RC_EINVAL
+ * before any launch with nothing written (rc_last_error names the operand) for a NULL or misaligned pointer, a negative size, a table
+ * smaller than its N, a bad mask, n_edge outside 0..4, max_depth outside 1..32, max_steps outside 1..ida_max_steps(); pad columns keep
+ * their bytes; n == 0 succeeds without a launch; every pointer needs 16-byte alignment and no more.  corner_table may be NULL (no
+ * corner table); masks, edge_tables (device pointers) and edge_bytes are HOST arrays of n_edge entries and travel to the kernel by value.
+ *
+ * Host only, no device: the largest max_steps ida_search takes (one launch at it stays near a second); allowed [13][13][12], the
+ * canonical rule as the kernel was compiled with it: allowed[p2][p1][m] = 1 iff m may follow ..., p2, p1 (12 = no move); a NULL
+ * pointer is RC_EINVAL. */
+int64_t ida_max_steps(void);
+int ida_canonical(uint8_t *allowed);
+/* The frame's first contents: legality of the cubie rows (IDA_ILLEGAL), the prefix replayed (IDA_BAD_FRAME for floor outside
+ * 0..max_depth or a prefix byte >= 12), the first bound, zeroed counters.  A cube with one of these two bits gets depth = bound = 0. */
+int ida_init(const uint8_t *cubies, int64_t n, int64_t cubie_pitch, const uint8_t *corner_table, int64_t corner_bytes, int n_edge,
+             const int *masks, const uint8_t *const *edge_tables, const int64_t *edge_bytes, uint8_t *path, int max_depth, int64_t path_pitch,
+             const int32_t *floor, const int32_t *limit, uint64_t *trail, uint8_t *cursor, int32_t *depth, int32_t *bound, int32_t *next,
+             uint64_t *nodes, uint8_t *status, void *stream);
+/* At most max_steps passes per running cube; the frames are stored, and the cubes still running are added to *running (one device
+ * uint32, 16-byte aligned, zeroed by the call). */
+int ida_search(const uint8_t *cubies, int64_t n, int64_t cubie_pitch, const uint8_t *corner_table, int64_t corner_bytes, int n_edge,
+               const int *masks, const uint8_t *const *edge_tables, const int64_t *edge_bytes, uint8_t *path, int max_depth, int64_t path_pitch,
+               const int32_t *floor, const int32_t *limit, uint64_t *trail, uint8_t *cursor, int32_t *depth, int32_t *bound, int32_t *next,
+               uint64_t *nodes, uint8_t *status, int64_t max_steps, uint32_t *running, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

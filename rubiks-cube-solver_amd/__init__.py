@@ -13,6 +13,7 @@ Drop-in surface for the env path of SUNGBEOMCHOI/Rubiks-Cube-Solver:
                       tables: the stronger admissible bound front="table" takes in a CornerTable's place
   ChainTables         the four coset-distance tables of Thistlethwaite's subgroup chain (pattern.py), and chain_solve, the descent through
   chain_solve         them (search.py): a solution of ANY legal 3x3x3 in at most 87 quarter turns, no net, no search
+  ida_search          Korf's IDA* under those pattern databases (search.py): the OPTIMAL solution of a 3x3x3, no node pool
   get_cubies, RCC_*   the cube as pieces: (piece, orientation) bytes, the legality status bits, perfect indices (ops.cubies / from_cubies)
   py333               the same operators under the reference's names, one cube per call
   py222               the six names cube_env.py:8 imports from the file the reference does not ship (2x2x2, one cube per call)
@@ -23,7 +24,7 @@ from .tables import (ACTION_NAMES, RCC_BAD_COLOUR, RCC_BAD_FIXED, RCC_BAD_PIECE,
 
 __all__ = ["get_env_config", "get_tables", "get_cubies", "ACTION_NAMES", "RCC_BAD_COLOUR", "RCC_BAD_FIXED", "RCC_BAD_PIECE", "RCC_DUP_PIECE",
            "RCC_TWIST", "RCC_FLIP", "RCC_PARITY", "RCC_NAMES", "ops", "make_env", "CubeEnv", "VecCubeEnv", "TensorReplayBuffer", "CodeNet", "CornerTable", "EdgeTable",
-           "MaxTable", "ChainTables", "chain_solve"]
+           "MaxTable", "ChainTables", "chain_solve", "ida_search"]
 
 
 def __getattr__(name):  # torch-dependent parts load lazily
@@ -39,8 +40,8 @@ def __getattr__(name):  # torch-dependent parts load lazily
         return importlib.import_module(f"{__name__}.codenet").CodeNet
     if name in ("CornerTable", "EdgeTable", "MaxTable", "ChainTables"):
         return getattr(importlib.import_module(f"{__name__}.pattern"), name)
-    if name == "chain_solve":
-        return importlib.import_module(f"{__name__}.search").chain_solve
+    if name in ("chain_solve", "ida_search"):
+        return getattr(importlib.import_module(f"{__name__}.search"), name)
     if name in ("CubeEnv", "make_env"):
         return getattr(importlib.import_module(f"{__name__}.cube_env"), name)
     raise AttributeError(name)

@@ -580,3 +580,168 @@ def chain_solve(tables, env, graph=False):
     rows = max(1, int(out_len.max()))
     acts = torch.where(solved[None, :], actions[:rows, :n], torch.full_like(actions[:rows, :n], 12))
     return dict(solved=solved, length=out_len, actions=acts.contiguous(), stage_moves=moves[:, :n].contiguous(), status=st)
+
+
+def _ida_members(table):
+    """(corner table or None, edge tables, device or None) of ida_search's `table`: a CornerTable, an EdgeTable, a MaxTable or None."""
+    from . import _ida_lib
+    from .pattern import CornerTable, EdgeTable, MaxTable
+    if table is None:
+        return None, (), None
+    if isinstance(table, CornerTable):
+        corner, edges = table, ()
+    elif isinstance(table, EdgeTable):
+        corner, edges = None, (table,)
+    elif isinstance(table, MaxTable):
+        corner, edges = table.corner, table.edge_tables
+    else:
+        raise ValueError(f"ida_search(table, env): table is a pattern.CornerTable, EdgeTable, MaxTable or None, got {type(table).__name__}")
+    if corner is not None and corner.cube_size != 3:
+        raise ValueError(f"ida_search is the 3x3x3's; the corner table is a {corner.cube_size}x{corner.cube_size}x{corner.cube_size}'s")
+    if len(edges) > _ida_lib.MAX_EDGE_TABLES:
+        raise ValueError(f"ida_search takes at most {_ida_lib.MAX_EDGE_TABLES} edge tables, got {len(edges)}")
+    return corner, tuple(edges), table.device
+
+
+class IdaFrame:
+    """The caller-owned frame of n cubes (include/rubikhip.h "Iterative-deepening A*") and the two launching calls on it.  cubies: a
+    tiled cubie buffer of n cubes with pitch p_c; prefix: None or uint8 [k, n], written into path's first k rows with floor = k."""
+
+    def __init__(self, table, cubies, n, p_c, max_depth, limit, prefix=None):
+        from ctypes import c_int, c_int64, c_void_p
+        from . import _ida_lib
+        corner, edges, _ = _ida_members(table)
+        dev = cubies.device
+        self.n, self.dev, self.max_depth, self.L = n, dev, int(max_depth), _ida_lib.ida_lib()
+        pitch = _lib.pitch_for(max(n, 1), 16)
+        vec = lambda dtype, rows=1: torch.zeros((rows, pitch), dtype=dtype, device=dev)
+        self.path = torch.full((self.max_depth, pitch), _ida_lib.NOOP, dtype=torch.uint8, device=dev)
+        self.floor = None
+        if prefix is not None and prefix.shape[0]:
+            self.path[:prefix.shape[0], :n] = prefix
+            self.floor = torch.full((pitch,), prefix.shape[0], dtype=torch.int32, device=dev)
+        self.limit = vec(torch.int32)[0]
+        self.limit[:n] = limit
+        self.trail = torch.zeros((pitch, 2), dtype=torch.int64, device=dev)
+        self.cursor, self.status = vec(torch.uint8)[0], vec(torch.uint8)[0]
+        self.depth, self.bound, self.next = vec(torch.int32)[0], vec(torch.int32)[0], vec(torch.int32)[0]
+        self.nodes = vec(torch.int64)[0]
+        self.running = torch.zeros(4, dtype=torch.int32, device=dev)       # one uint32, 16-byte aligned
+        k = len(edges)
+        self._keep = (corner, edges, cubies)
+        self._args = (ptr(cubies), n, p_c, ptr(corner.table) if corner is not None else None, corner.table.numel() if corner is not None else 0, k,
+                      (c_int * max(k, 1))(*[e.mask for e in edges]), (c_void_p * max(k, 1))(*[ptr(e.table) for e in edges]),
+                      (c_int64 * max(k, 1))(*[e.table.numel() for e in edges]), ptr(self.path), self.max_depth, pitch,
+                      ptr(self.floor) if self.floor is not None else None, ptr(self.limit), ptr(self.trail), ptr(self.cursor), ptr(self.depth),
+                      ptr(self.bound), ptr(self.next), ptr(self.nodes), ptr(self.status))
+
+    def init(self):
+        _lib.check(self.L.ida_init(*self._args, stream_ptr(self.dev)))
+
+    def search(self, steps):
+        _lib.check(self.L.ida_search(*self._args, int(steps), ptr(self.running), stream_ptr(self.dev)))
+
+    def run(self, max_steps, steps_per_call):
+        """ida_search until no cube runs or max_steps passes per cube are spent; one read-back per call."""
+        spent = 0
+        while spent < max_steps:
+            k = min(steps_per_call, max_steps - spent)
+            self.search(k)
+            spent += k
+            if int(self.running[0]) == 0:
+                break
+        return spent
+
+
+def ida_search(table, env, *, limit=20, max_steps=1 << 22, steps_per_call=None, split=0):
+    """The OPTIMAL solution of every cube of a 3x3x3 env by iterative-deepening A* (include/rubikhip.h "Iterative-deepening A*" has THE
+    RULE, DESIGN.md "IDA*" the numbers): depth-first under a cost bound that grows from h(start), with h the maximum of the tables
+    given -- a pattern.CornerTable, EdgeTable, MaxTable, or None for h = 0.  No node is ever stored: a search is a trail of moves, so it
+    keeps answering where astar_search stops for want of iterations or of pool.  The env is left as it is.  rcc_cubies runs once; a cube whose legality() is nonzero is
+    not searched (status ILLEGAL).
+
+    limit: the largest length looked for (<= 32).  max_steps: the passes (children generated + levels gone back) every cube may spend;
+    steps_per_call: how many of them one launch makes (default and cap: ida_max_steps()); after each launch one uint32 is read back.
+    split = k in 1..3, for batches far smaller than the device: cubes farther than k moves from solved are searched once per canonical
+    move sequence of length k (12 | 114 | 1068 lanes per cube) with the limit held at the cube's bound, round by round; the answer is
+    that of the lowest sequence that solved, the unsplit path byte for byte.  A round runs ONE iteration, at the cube's bound, per
+    sequence; max_steps then bounds every round's searches, and nodes counts every round's.
+
+    Returns dict(solved bool [N], length int32 [N] (-1: not solved), actions uint8 [L, N] (padded with the no-op 12; L = max(1,
+    length.max())), nodes int64 [N], bound int32 [N] (solved: the length; else a PROVEN lower bound on the distance: every f below it
+    was excluded), status uint8 [N] (IDA_SOLVED 1, IDA_EXHAUSTED 2: no solution within limit, IDA_ILLEGAL 4, 0: the budget ran out))."""
+    from . import _ida_lib
+    corner, edges, dev = _ida_members(table)
+    if not hasattr(env, "stickers") or env.cube_size != 3:
+        raise ValueError(f"ida_search needs a 3x3x3 VecCubeEnv, got {'a ' + str(env.cube_size) + 'x' + str(env.cube_size) + 'x' + str(env.cube_size) + ' one' if hasattr(env, 'cube_size') else type(env).__name__}")
+    ints = lambda v: isinstance(v, int) and not isinstance(v, bool)
+    if not ints(limit) or not 0 <= limit <= _ida_lib.MAX_DEPTH:
+        raise ValueError(f"limit must be an integer in 0..{_ida_lib.MAX_DEPTH}, got {limit!r}")
+    if not ints(split) or not 0 <= split <= 3:
+        raise ValueError(f"split must be an integer in 0..3, got {split!r}")
+    if not ints(max_steps) or max_steps < 1:
+        raise ValueError(f"max_steps must be a positive integer, got {max_steps!r}")
+    cap = _ida_lib.max_steps()
+    if steps_per_call is None:
+        steps_per_call = cap
+    if not ints(steps_per_call) or not 1 <= steps_per_call <= cap:
+        raise ValueError(f"steps_per_call must be an integer in 1..ida_max_steps() = {cap}, got {steps_per_call!r}")
+    if dev is not None and env.stickers.device != dev:
+        raise ValueError(f"the tables are on {dev}, the cubes on {env.stickers.device}")
+    n, dev = env.num_envs, env.stickers.device
+    _lib.init(dev)
+    cub = ops.alloc_code(n, 3, dev, env.stickers.shape[-1])
+    legal = torch.empty(_lib.pitch_for(n, 16), dtype=torch.uint8, device=dev)
+    ops.cubies(env.stickers, n, 3, cubies=cub, status=legal)
+    p_c = ops._state_arg(cub, 20, n, None, "ida_search cubies")
+    max_depth = max(1, limit)
+
+    fr = IdaFrame(table, cub, n, p_c, max_depth, min(limit, split) if split else limit)
+    fr.init()
+    fr.status[:n] = torch.where(legal[:n] != 0, torch.full_like(legal[:n], _ida_lib.ILLEGAL), fr.status[:n])   # not a cube: not searched
+    fr.run(max_steps, steps_per_call)
+    status, nodes = fr.status[:n].clone(), fr.nodes[:n].clone()
+    depth, path = fr.depth[:n].clone(), fr.path[:, :n].clone()
+    bound = torch.where(status == _ida_lib.EXHAUSTED, fr.next[:n], fr.bound[:n])
+
+    if split and limit > split:
+        P = torch.as_tensor(_ida_lib.prefixes(split), device=dev)          # [np, k]
+        n_p = P.shape[0]
+        todo = torch.nonzero(status == _ida_lib.EXHAUSTED)[:, 0]            # farther than `split` moves: bound = next > split
+        todo = todo[bound[todo] <= limit]
+        status[todo] = 0
+        aos = ops.to_aos(cub, n)
+        while todo.numel():
+            m = todo.numel() * n_p
+            cub2 = torch.empty((20, _lib.pitch_for(m, 16)), dtype=torch.uint8, device=dev)
+            cub2[:, :m] = aos[todo].repeat_interleave(n_p, 0).T
+            sub = IdaFrame(table, cub2, m, cub2.shape[1], max_depth, bound[todo].repeat_interleave(n_p), prefix=P.T.repeat(1, todo.numel()))
+            sub.init()
+            # every f below the cube's bound is excluded already: a sub-search starts its first iteration at that bound, not at its own
+            sub.bound[:m] = torch.where(sub.status[:m] == 0, sub.limit[:m], sub.bound[:m])
+            sub.run(max_steps, steps_per_call)
+            st = sub.status[:m].view(-1, n_p)
+            nodes[todo] += sub.nodes[:m].view(-1, n_p).sum(1)
+            won = st == _ida_lib.SOLVED
+            first = won.to(torch.uint8).argmax(1)                          # the lowest prefix that solved
+            col = torch.arange(todo.numel(), device=dev) * n_p + first
+            stuck = (st == 0).any(1) | ((st & (_ida_lib.ILLEGAL | _ida_lib.BAD_FRAME)) != 0).any(1)
+            below = torch.arange(n_p, device=dev)[None, :] < first[:, None]
+            hit = won.any(1) & ~((st != _ida_lib.EXHAUSTED) & below).any(1)    # no lower prefix is undecided: the unsplit search's answer
+            status[todo[hit]] = _ida_lib.SOLVED
+            depth[todo[hit]] = sub.depth[col[hit]]
+            path[:, todo[hit]] = sub.path[:, col[hit]]
+            bound[todo[hit]] = sub.depth[col[hit]]
+            nxt = torch.where(st == _ida_lib.EXHAUSTED, sub.next[:m].view(-1, n_p), torch.full_like(st, 0, dtype=torch.int32) + _ida_lib.INF).min(1).values
+            go = ~hit & ~stuck
+            bound[todo[go]] = nxt[go]
+            over = go & (nxt > limit)
+            status[todo[over]] = _ida_lib.EXHAUSTED
+            todo = todo[go & ~over]
+
+    solved = status == _ida_lib.SOLVED
+    length = torch.where(solved, depth, torch.full_like(depth, -1))
+    bound = torch.where(solved, depth, bound)
+    rows = max(1, int(length.max())) if n else 1
+    acts = torch.where(solved[None, :], path[:rows], torch.full_like(path[:rows], _ida_lib.NOOP))
+    return dict(solved=solved, length=length, actions=acts.contiguous(), nodes=nodes, bound=bound, status=status)

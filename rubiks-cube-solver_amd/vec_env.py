@@ -248,6 +248,12 @@ class VecCubeEnv:
         from .search import chain_solve
         return chain_solve(tables, self, graph=graph)
 
+    def ida_search(self, table, **kwargs):
+        """search.ida_search(table, self, ...): the optimal solution of every cube by IDA* under a CornerTable, an EdgeTable, a MaxTable
+        or None (3x3x3 only); the env is left as it is."""
+        from .search import ida_search
+        return ida_search(table, self, **kwargs)
+
     def from_cubies(self, cubies):
         """Set every cube from its cubie bytes: [N, SLOTS] rows (host or device) or a tiled cubie tensor as cubies() returns it.  The
         assembly need not be legal (legality() tells); a byte that names no (piece, orientation) raises ValueError and the env keeps

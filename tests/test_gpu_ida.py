@@ -1,0 +1,581 @@
+"""IDA* on the GPU (search.ida_search, the ida_* entry points of librubikhip.so) against the plain-Python restatement
+(tests/ida_ref.py), which moves cubes by the oracle and reads host copies of the device's own tables: lengths against breadth-first
+distances and against astar_search, paths / node counts / bounds against the restatement wherever it can follow (its node cap),
+budget invariance, split, limits, the status bits, every operand carved out of a guarded arena at the minimum alignment, every argument
+error, each launching export under capture and replay, and bounds against chain_solve on random cubes.  All comparisons are exact.
+GPU only."""
+import ctypes
+import os
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+from tests import ida_ref as R
+from tests.test_gpu_cubies import FILL, Arena, rows_arena
+from tests.test_gpu_search import env_of, scrambles
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import stream_cases as C  # noqa: E402
+import stream_driver as D  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda"
+EINVAL = -1
+OFFSET = 16                                  # every operand 16 bytes past a 32-byte boundary: the alignment the header asks for, no more
+CONFIGS = ("corner", "edge3", "edge4", "best")
+
+
+def mods():
+    from rubiks_cube_solver_amd import _ida_lib, _lib, ops, pattern, search
+    return _lib, _ida_lib, ops, pattern, search
+
+
+def stream():
+    from rubiks_cube_solver_amd import _lib
+    return _lib.stream_ptr(torch.device(DEV, torch.cuda.current_device()))
+
+
+@pytest.fixture(scope="module")
+def tabs():
+    """The tables, built once: {config: (table object, restated heuristic on host copies of the same bytes)}."""
+    _, _, _, pattern, _ = mods()
+    corner = pattern.CornerTable.build(3, DEV)
+    lo, hi = pattern.EdgeTable.build(range(6), DEV), pattern.EdgeTable.build(range(6, 12), DEV)
+    e3, e4 = pattern.EdgeTable.build((3, 7, 8), DEV), pattern.EdgeTable.build((1, 4, 6, 10), DEV)
+    hc = corner.table.cpu().numpy()
+    he = {e: (e.mask, e.table.cpu().numpy()) for e in (lo, hi, e3, e4)}
+    return {"none": (None, R.Heuristic()), "corner": (corner, R.Heuristic(hc)), "edge3": (e3, R.Heuristic(None, [he[e3]])),
+            "edge4": (e4, R.Heuristic(None, [he[e4]])),
+            "best": (pattern.MaxTable(corner, lo, hi), R.Heuristic(hc, [he[lo], he[hi]]))}
+
+
+def bytes_of(env):
+    _, _, ops, _, _ = mods()
+    return ops.to_aos(ops.cubies(env.stickers, env.num_envs, 3, status=False)["cubies"], env.num_envs).cpu().numpy()
+
+
+def env_of_bytes(rows):
+    from rubiks_cube_solver_amd import VecCubeEnv
+    env = VecCubeEnv(len(rows), DEV, 3, obs=None)
+    env.from_cubies(np.asarray(rows, np.uint8))
+    return env
+
+
+def host(res):
+    return {k: v.cpu().numpy() if isinstance(v, torch.Tensor) else v for k, v in res.items()}
+
+
+def same_as_frame(res, c, f, what):
+    """One cube of ida_search's result against a restated frame."""
+    got = (int(res["status"][c]), int(res["length"][c]), int(res["nodes"][c]), int(res["bound"][c]))
+    assert got == (f.status, f.length, f.nodes, f.lower_bound), (what, c, got, (f.status, f.length, f.nodes, f.lower_bound))
+    acts = res["actions"][:, c]
+    if f.status == R.SOLVED:
+        assert acts[:f.depth].tolist() == f.path and (acts[f.depth:] == R.NOOP).all(), (what, c)
+    else:
+        assert (acts == R.NOOP).all(), (what, c)
+
+
+# ------------------------------------------------------------------------------------------------------------------ 1. no table
+def test_without_a_table_the_length_is_the_distance(tabs):
+    """All 1 + 12 + 114 + 1068 states within 3 moves and 200 each at 4 and 5: length = the breadth-first distance and the path,
+    replayed by the oracle's movers, solves the cube; path, nodes and bound equal the restatement's on every state within 2 moves,
+    every 24th at 3, four at 4 and whatever of the first two at 5 its node cap reaches."""
+    _, _, _, _, search = mods()
+    dist, levels = R.spheres(5)
+    xs = [x for lv in levels[:4] for x in lv] + levels[4][::len(levels[4]) // 200][:200] + levels[5][::len(levels[5]) // 200][:200]
+    rows = np.array([R.to_bytes(x) for x in xs], np.uint8)
+    env = env_of_bytes(rows)
+    before = env.stickers.clone()
+    res = host(search.ida_search(None, env, limit=6))
+    assert torch.equal(env.stickers, before)
+    want = np.array([dist[x] for x in xs])
+    assert res["solved"].all() and (res["status"] == R.SOLVED).all() and (res["length"] == want).all() and (res["bound"] == want).all()
+    assert res["actions"].shape == (5, len(xs))
+    home = R.to_bytes(R.HOME)
+    for c in range(len(xs)):
+        ln = want[c]
+        assert (res["actions"][ln:, c] == R.NOOP).all() and R.replay_bytes(rows[c], res["actions"][:ln, c]) == home, c
+    follow = list(range(127)) + list(range(127, 1195, 24)) + list(range(1195, 1395, 50)) + list(range(1395, 1397))
+    reached = 0
+    for c in follow:
+        try:
+            f = R.solve(rows[c], tabs["none"][1], limit=6)
+        except R.OutOfReach:
+            assert want[c] == 5
+            continue
+        same_as_frame(res, c, f, "no table")
+        reached += 1
+    assert reached >= len(follow) - 2
+
+
+# --------------------------------------------------------------------------------------------------------------------- 2. tables
+@pytest.fixture(scope="module")
+def walks():
+    """500 walks each of 3, 5 and 7 moves, 200 each of 9 and 10."""
+    scr = scrambles(3, [3] * 500 + [5] * 500 + [7] * 500 + [9] * 200 + [10] * 200, seed=11)
+    env = env_of(3, scr)
+    return dict(env=env, rows=bytes_of(env), scr=scr)
+
+
+BUDGET = {"corner": 1 << 15, "edge3": 1 << 15, "edge4": 1 << 15, "best": 1 << 16}
+
+
+@pytest.mark.parametrize("config", CONFIGS)
+def test_under_tables_everything_equals_the_restatement(tabs, walks, config):
+    """Every cube gets BUDGET passes.  Under the MaxTable the restatement follows ALL 1900 cubes, pass for pass up to the same budget
+    (its node cap, 2 * 10^5, is reached by none).  Under the weaker tables, whose deep searches no Python loop follows, it follows
+    four cubes of every walk length whatever became of them (solved, or still running: then bound and nodes are those of the cut
+    search) up to 20 000 restated nodes each, and up to 300 further solved cubes of at most 400 nodes.  Every solution, replayed on the
+    oracle's movers, solves its cube and is no longer than the walk."""
+    _, _, _, _, search = mods()
+    table, h = tabs[config]
+    env, rows = walks["env"], walks["rows"]
+    res = host(search.ida_search(table, env, limit=12, max_steps=BUDGET[config], steps_per_call=min(BUDGET[config], 1 << 14)))
+    n = len(rows)
+    walked = (walks["scr"] != 12).sum(1)
+    assert set(np.unique(res["status"])) <= {0, R.SOLVED} and res["solved"][:1000 if config == "best" else 500].all()
+    home = R.to_bytes(R.HOME)
+    for c in np.flatnonzero(res["solved"]):
+        ln = res["length"][c]
+        assert ln <= walked[c] and (walked[c] - ln) % 2 == 0 and R.replay_bytes(rows[c], res["actions"][:ln, c]) == home, c
+    assert (res["bound"][~res["solved"]] <= walked[~res["solved"]]).all()    # a proven lower bound
+    if config == "best":
+        follow, cap = list(range(n)), 200000
+        assert res["solved"].all() and res["nodes"].max() < cap
+    else:
+        sample = [c for start in (0, 500, 1000, 1500, 1700) for c in range(start, start + 4)]
+        follow = sample + [c for c in np.flatnonzero(res["solved"] & (res["nodes"] <= 400)) if c not in sample][:300]
+        cap = 20000
+    print(config, "followed:", len(follow), "restated nodes at most:", int(np.minimum(res["nodes"][follow], cap).sum()))
+    for c in follow:
+        f = R.Frame(rows[c], h, 12, 12)
+        try:
+            f.run(max_passes=BUDGET[config], max_nodes=cap)
+        except R.OutOfReach:
+            assert res["nodes"][c] >= cap, c
+            continue
+        same_as_frame(res, c, f, config)
+
+
+def test_lengths_equal_astar_under_the_best_table(tabs, walks):
+    """astar_search(front="table") with batch 1 and weight 1 is optimal under the same admissible bound: equal lengths cube for cube
+    on ALL 1900 walks wherever A* answered without overflow.  IDA* answers every cube.  A* (300 iterations) has to answer every 3-, 5-
+    and 7-move walk -- it did so within 200 before this search existed (tests/test_gpu_edge.py) -- and most, i.e. more than half, of
+    the 9- and 10-move walks, so that the comparison is made where the searches are deep."""
+    _, _, _, _, search = mods()
+    table = tabs["best"][0]
+    env = walks["env"]
+    ida = host(search.ida_search(table, env, limit=12))
+    star = host(search.astar_search(table, env, 1, 300, front="table"))
+    both = ida["solved"] & star["solved"] & ~star["overflow"]
+    per_length = {k: (int(both[s].sum()), s.stop - s.start) for k, s in ((3, slice(0, 500)), (5, slice(500, 1000)), (7, slice(1000, 1500)),
+                                                                         (9, slice(1500, 1700)), (10, slice(1700, 1900)))}
+    print("both answered, per walk length:", per_length, "A* overflow:", int(star["overflow"].sum()))
+    assert ida["solved"].all()
+    assert all(per_length[k][0] == per_length[k][1] for k in (3, 5, 7)) and all(2 * per_length[k][0] > per_length[k][1] for k in (9, 10))
+    assert (ida["length"][both] == star["length"][both]).all()
+    assert not (star["solved"] & ~star["overflow"] & ~ida["solved"]).any()
+
+
+# ---------------------------------------------------------------------------------------------------------- 3. budget invariance
+def frame_bytes(fr, n):
+    return {k: getattr(fr, k)[..., :n].cpu().numpy() if k != "trail" else fr.trail[:n].cpu().numpy()
+            for k in ("path", "trail", "cursor", "depth", "bound", "next", "nodes", "status")}
+
+
+@pytest.mark.parametrize("config", ("best", "edge3"))
+def test_the_frame_does_not_depend_on_how_the_budget_is_cut(tabs, walks, config):
+    """4096 passes per cube in launches of 1, 7, 64 and 4096: byte-equal frames and paths -- cubes solved on the way and cubes still
+    running (the edge3 table leaves most 7-move walks running); eight of them against the restatement cut at 4096 passes."""
+    _, _, ops, _, search = mods()
+    table, h = tabs[config]
+    pick = np.concatenate([np.arange(s, s + 16) for s in (0, 500, 1000, 1500)])
+    env = env_of(3, walks["scr"][pick])
+    n = len(pick)
+    cub = ops.cubies(env.stickers, n, 3, status=False)["cubies"]
+    p_c = ops._state_arg(cub, 20, n, None, "cubies")
+    frames = {}
+    for per_call in (1, 7, 64, 4096):
+        fr = search.IdaFrame(table, cub, n, p_c, 12, 12)
+        fr.init()
+        assert fr.run(4096, per_call) <= 4096 + per_call
+        frames[per_call] = frame_bytes(fr, n)
+    for per_call in (1, 7, 64):
+        for k, v in frames[4096].items():
+            assert (frames[per_call][k] == v).all(), (per_call, k)
+    got = frames[4096]
+    assert (got["status"] == R.SOLVED).any() and (config == "best" or (got["status"] == 0).any())
+    for c in range(0, n, 8):
+        f = R.Frame(walks["rows"][pick[c]], h, 12, 12).run(max_passes=4096)
+        assert (got["status"][c], got["depth"][c], got["bound"][c], got["next"][c], got["nodes"][c], got["cursor"][c]) == \
+               (f.status, f.depth, f.bound, f.next, f.nodes, f.cursor), c
+        assert got["trail"][c].view(np.uint64).tolist() == f.words, c
+
+
+# --------------------------------------------------------------------------------------------------------------- 4. split, limit
+@pytest.mark.parametrize("split", (1, 2))
+def test_split_returns_the_unsplit_answer(tabs, walks, split):
+    """Cubes 0..8 moves from solved, some nearer than the prefix is long: the same status, length and path, byte for byte."""
+    _, _, _, _, search = mods()
+    near = np.pad(scrambles(3, [0, 1, 1, 2, 2, 3, 3, 4], seed=3), ((0, 0), (0, 6)), constant_values=12)
+    scr = np.concatenate([near, walks["scr"][0:8], walks["scr"][500:516], walks["scr"][1000:1016], walks["scr"][1500:1508]], 0)
+    env = env_of(3, scr)
+    table = tabs["best"][0]
+    whole = host(search.ida_search(table, env, limit=12))
+    parts = host(search.ida_search(table, env, limit=12, split=split))
+    assert whole["solved"].all() and (whole["length"] > split).sum() >= 30 and (whole["length"] <= split).any()
+    for k in ("solved", "status", "length", "bound", "actions"):
+        assert (whole[k] == parts[k]).all(), k
+    near = whole["length"] <= split
+    assert (parts["nodes"][near] == whole["nodes"][near]).all() and (parts["nodes"][~near] > 0).all()
+    # the limit holds for the split search too
+    short = host(search.ida_search(table, env, limit=4, split=split))
+    far = whole["length"] > 4
+    assert (short["status"][far] == R.EXHAUSTED).all() and (short["bound"][far] > 4).all() and (short["bound"][far] <= whole["length"][far]).all()
+    assert (short["length"][~far] == whole["length"][~far]).all()
+
+
+def test_a_limit_below_the_distance_is_exhausted_with_the_restated_next(tabs, walks):
+    _, _, _, _, search = mods()
+    table, h = tabs["best"]
+    pick = np.arange(1000, 1032)
+    env = env_of(3, walks["scr"][pick])
+    whole = host(search.ida_search(table, env, limit=12))
+    assert whole["solved"].all()
+    for limit in (0, 3, 5):
+        res = host(search.ida_search(table, env, limit=limit))
+        far = whole["length"] > limit
+        assert far.any() and (res["status"][far] == R.EXHAUSTED).all() and (res["length"][far] == -1).all()
+        assert (res["length"][~far] == whole["length"][~far]).all()
+        for c in np.flatnonzero(far)[:12]:
+            f = R.solve(walks["rows"][pick[c]], h, limit=limit)
+            assert f.status == R.EXHAUSTED and limit < f.next <= whole["length"][c]
+            same_as_frame(res, c, f, limit)
+
+
+def test_cubes_that_are_not_legal_are_not_searched(tabs):
+    """A twisted corner, a flipped edge and two edges swapped are well-formed cubie rows that no move sequence solves: legality() is
+    nonzero, the status is IDA_ILLEGAL with nothing generated, and the legal cubes beside them are solved as ever."""
+    _, _, _, _, search = mods()
+    rows = bytes_of(env_of(3, scrambles(3, [4] * 6, seed=4)))
+    rows[1, 0] = 3 * (rows[1, 0] // 3) + (rows[1, 0] % 3 + 1) % 3
+    rows[3, 8] ^= 1
+    rows[4, [8, 9]] = rows[4, [9, 8]]
+    env = env_of_bytes(rows)
+    assert (env.legality().cpu().numpy() != 0).tolist() == [False, True, False, True, True, False]
+    for table in (None, tabs["best"][0]):
+        for split in (0, 1):
+            res = host(search.ida_search(table, env, limit=8, max_steps=1 << 18, split=split))   # h = 0: up to 117 582 children
+            assert res["status"].tolist() == [R.SOLVED, R.ILLEGAL, R.SOLVED, R.ILLEGAL, R.ILLEGAL, R.SOLVED], (split, res["status"])
+            assert (res["length"][[1, 3, 4]] == -1).all() and (res["nodes"][[1, 3, 4]] == 0).all() and (res["length"][[0, 2, 5]] <= 4).all()
+
+
+# ----------------------------------------------------------------------------------------------- 5. the C ABI in guarded arenas
+class Raw:
+    """One set of ida_* operands, each in an arena of its own, OFFSET bytes past a 32-byte boundary, with guards of FILL.  `host`
+    of every arena is what the device must hold: expect(frames) rewrites it from restated frames."""
+
+    def __init__(self, table, rows, layout, max_depth, limit, prefix=None, floor=None):
+        _, _, _, _, search = mods()
+        n = self.n = len(rows)
+        self.corner, self.edges, _ = search._ida_members(table)
+        self.max_depth = max_depth
+        self.cub = rows_arena(np.asarray(rows, np.uint8), n, 20, layout, OFFSET)
+        self.pp = -(-n // 16) * 16 + 16                                      # a pitch with pad columns
+        self.path = Arena(max_depth * self.pp, OFFSET)
+        self.path0 = np.full((max_depth, self.pp), FILL, np.uint8)
+        self.path0[:, :n] = R.NOOP
+        if prefix is not None:
+            self.path0[:len(prefix), :n] = prefix
+        self.path.expect(self.path0)
+        self.floor = None if floor is None else Arena(4 * n, OFFSET)
+        if floor is not None:
+            self.floor.expect(np.asarray(floor, np.int32))
+        self.limit = Arena(4 * n, OFFSET)
+        self.limit.expect(np.asarray(limit, np.int32))
+        size = dict(trail=16, cursor=1, depth=4, bound=4, next=4, nodes=8, status=1)
+        self.frame = {k: Arena(s * n, OFFSET) for k, s in size.items()}
+        self.running = Arena(4, OFFSET)
+        self.arenas = [self.cub, self.path, self.limit, self.running, *self.frame.values()] + ([self.floor] if self.floor else [])
+        for a in self.arenas:
+            a.upload()
+        k = len(self.edges)
+        self.masks = (ctypes.c_int * max(k, 1))(*[e.mask for e in self.edges])
+        self.etabs = (ctypes.c_void_p * max(k, 1))(*[e.table.data_ptr() for e in self.edges])
+        self.ebytes = (ctypes.c_int64 * max(k, 1))(*[e.table.numel() for e in self.edges])
+
+    def args(self, **kw):
+        a = dict(cubies=self.cub.ptr(), n=self.n, cubie_pitch=self.cub.pitch,
+                 corner=ctypes.c_void_p(self.corner.table.data_ptr()) if self.corner is not None else None,
+                 corner_bytes=self.corner.table.numel() if self.corner is not None else 0, n_edge=len(self.edges), masks=self.masks,
+                 etabs=self.etabs, ebytes=self.ebytes, path=self.path.ptr(), max_depth=self.max_depth, path_pitch=self.pp,
+                 floor=self.floor.ptr() if self.floor else None, limit=self.limit.ptr(), **{k: v.ptr() for k, v in self.frame.items()})
+        a.update(kw)
+        return list(a.values())
+
+    def init(self, **kw):
+        _, _ida, _, _, _ = mods()
+        return _ida.ida_lib().ida_init(*self.args(**kw), stream())
+
+    def search(self, steps, running="own", **kw):
+        _, _ida, _, _, _ = mods()
+        return _ida.ida_lib().ida_search(*self.args(**kw), steps, self.running.ptr() if running == "own" else running, stream())
+
+    def expect(self, frames, running=None):
+        n = self.n
+        path = self.path0.copy()
+        for c, f in enumerate(frames):
+            if f.status == R.SOLVED:
+                path[f.floor:f.depth, c] = f.nib[f.floor:f.depth]
+        self.path.expect(path)
+        self.frame["trail"].expect(np.array([f.words for f in frames], np.uint64))
+        for k, dt in (("cursor", np.uint8), ("depth", np.int32), ("bound", np.int32), ("next", np.int32), ("nodes", np.uint64), ("status", np.uint8)):
+            self.frame[k].expect(np.array([getattr(f, k) for f in frames], dt))
+        if running is not None:
+            self.running.expect(np.array([running], np.uint32))
+
+    def check(self, what):
+        torch.cuda.synchronize()
+        for a in self.arenas:
+            a.check(what)
+
+
+def restated(raw_rows, h, max_depth, limit, path=None, floor=None):
+    """path: what the rows of `path` hold at ida_init, [max_depth, >= n] (needed with floor alone)."""
+    n = len(raw_rows)
+    return [R.Frame(raw_rows[c], h, int(limit[c]), max_depth, prefix=() if floor is None else tuple(int(m) for m in path[:, c]),
+                    floor_given=None if floor is None else int(floor[c])) for c in range(n)]
+
+
+@pytest.mark.parametrize("n,layout", [(n, lay) for n in (1, 3, 513, 1029) for lay in ("tight", "padded", "t512") if lay != "t512" or n > 512])
+def test_every_byte_of_every_operand(tabs, n, layout):
+    """Walks of 0..6 moves, every other cube below a one-move prefix (floor 1), limits 0..7: after ida_init, after 5 passes and after
+    the search has ended every byte of every operand, its pad columns and its guards are the restatement's."""
+    table, h = tabs["best"]
+    _lib, _, _, _, _ = mods()
+    _lib.init(torch.device(DEV, torch.cuda.current_device()))
+    rng = np.random.default_rng(n)
+    rows = bytes_of(env_of(3, scrambles(3, [c % 7 for c in range(n)], seed=n)))
+    floor = (np.arange(n) % 2).astype(np.int32)
+    prefix = rng.integers(0, 12, (1, n)).astype(np.uint8)
+    limit = (7 - np.arange(n) % 8).astype(np.int32)
+    raw = Raw(table, rows, layout, 9, limit, prefix, floor)
+    frames = restated(rows, h, 9, limit, raw.path0, floor)
+    assert raw.init() == 0
+    raw.expect(frames)
+    raw.check("ida_init")
+    for f in frames:
+        f.run(max_passes=5)
+    assert raw.search(5) == 0
+    raw.expect(frames, running=sum(f.status == 0 for f in frames))
+    raw.check("five passes")
+    for f in frames:
+        f.run()
+    assert raw.search(1 << 14) == 0
+    raw.expect(frames, running=0)
+    raw.check("to the end")
+    assert {f.status for f in frames} >= ({R.SOLVED, R.EXHAUSTED} if n > 3 else {R.SOLVED})
+    assert raw.search(1 << 14) == 0                                          # nothing runs: nothing is touched
+    raw.check("a further call")
+
+
+def test_illegal_rows_bad_prefixes_and_floors_get_their_bits_and_nothing_moves(tabs):
+    table, h = tabs["corner"]
+    _lib, _, _, _, _ = mods()
+    _lib.init(torch.device(DEV, torch.cuda.current_device()))
+    n = 12
+    rows = bytes_of(env_of(3, scrambles(3, [4] * n, seed=2)))
+    rows[1, 3] = 24                                                          # no cubie
+    rows[2, 9] = rows[2, 8]                                                  # an edge piece twice
+    rows[3, 0] = rows[3, 1]                                                  # a corner piece twice
+    rows[4, 19] = 0xFF
+    floor = np.array([0, 0, 0, 0, 0, -1, 7, 2, 2, 2, 6, 0], np.int32)
+    prefix = np.tile(np.array([[0], [4]], np.uint8), (1, n))
+    prefix[1, 8] = 12                                                        # a no-op inside the prefix
+    prefix[0, 9] = 200
+    raw = Raw(table, rows, "tight", 6, np.full(n, 6, np.int32), prefix, floor)
+    frames = restated(rows, h, 6, np.full(n, 6), raw.path0, floor)
+    assert [f.status for f in frames][1:7] == [R.ILLEGAL] * 4 + [R.BAD_FRAME] * 2 and [f.status for f in frames][8:11] == [R.BAD_FRAME] * 3
+    assert all(frames[c].status in (0, R.EXHAUSTED) for c in (0, 7, 11))     # row 10: floor 6 reaches into the no-op rows of path
+    assert raw.init() == 0
+    raw.expect(frames)
+    raw.check("ida_init")
+    for f in frames:
+        f.run()
+    assert raw.search(1 << 14) == 0
+    raw.expect(frames, running=0)
+    raw.check("ida_search")
+    assert frames[0].status == R.SOLVED and frames[7].status in (R.SOLVED, R.EXHAUSTED) and frames[7].depth >= 2
+    # a foreign table: every entry 0xFF is IDA_ILLEGAL, at the start node or at the first child
+    foreign = torch.full_like(table.table, 0xFF)
+    raw = Raw(table, rows[:1], "tight", 6, np.full(1, 6, np.int32))
+    assert raw.init(corner=ctypes.c_void_p(foreign.data_ptr())) == 0
+    torch.cuda.synchronize()
+    assert raw.frame["status"].view.cpu().numpy().tolist() == [R.ILLEGAL]
+
+
+def test_every_argument_error_writes_nothing(tabs):
+    table, _ = tabs["best"]
+    _lib, _ida, _, _, _ = mods()
+    _lib.init(torch.device(DEV, torch.cuda.current_device()))
+    n = 20
+    rows = bytes_of(env_of(3, scrambles(3, [3] * n, seed=1)))
+    raw = Raw(table, rows, "tight", 8, np.full(n, 8, np.int32), floor=np.zeros(n, np.int32))
+    odd = lambda a: ctypes.c_void_p(a.view.data_ptr() + 8)
+    small = (ctypes.c_int64 * 2)(raw.ebytes[0] - 1, raw.ebytes[1])
+    badmask = (ctypes.c_int * 2)(0x1000, raw.masks[1])
+    bad = [dict(n=-1), dict(cubies=None), dict(cubies=odd(raw.cub)), dict(cubie_pitch=24), dict(cubie_pitch=16), dict(corner=odd(raw.cub)),
+           dict(corner_bytes=88179839), dict(n_edge=5), dict(n_edge=-1), dict(masks=None), dict(etabs=None), dict(ebytes=None),
+           dict(ebytes=small), dict(masks=badmask), dict(path=None), dict(path=odd(raw.path)), dict(max_depth=0), dict(max_depth=33),
+           dict(path_pitch=16), dict(path_pitch=raw.pp + 8), dict(floor=odd(raw.floor)), dict(limit=None), dict(limit=odd(raw.limit))]
+    bad += [dict([(k, None)]) for k in raw.frame] + [dict([(k, odd(raw.frame[k]))]) for k in ("trail", "cursor", "status", "nodes")]
+    for kw in bad:
+        assert raw.init(**kw) == EINVAL and _lib.lib().rc_last_error().startswith(b"ida_init"), kw
+        assert raw.search(4, **kw) == EINVAL and _lib.lib().rc_last_error().startswith(b"ida_search"), kw
+    for steps in (0, -1, _ida.max_steps() + 1):
+        assert raw.search(steps) == EINVAL
+    assert raw.search(4, running=None) == EINVAL and raw.search(4, running=odd(raw.running)) == EINVAL
+    raw.check("argument errors")
+    assert raw.init(n=0) == 0 and raw.search(4, n=0) == 0                    # succeeds without a launch
+    raw.check("n == 0")
+    assert raw.search(_ida.max_steps()) == 0                                 # the cap itself is taken (a frame of FILL: BAD_FRAME or skipped)
+    torch.cuda.synchronize()
+
+
+# ------------------------------------------------------------------------------------------------------- 6. capture and replay
+def _s_rows(w):
+    depth = [c % 6 for c in range(C.N)]
+    scr = scrambles(3, depth, seed=C._SEED[w])
+    return scr
+
+
+def _s_common(ctx, arena, table):
+    t = ctx.torch
+    n = C.N
+    _, _, _, _, search = mods()
+    corner, edges, _ = search._ida_members(table)
+    k = len(edges)
+    fixed = dict(masks=(ctypes.c_int * k)(*[e.mask for e in edges]), etabs=(ctypes.c_void_p * k)(*[e.table.data_ptr() for e in edges]),
+                 ebytes=(ctypes.c_int64 * k)(*[e.table.numel() for e in edges]))
+    pp = C.pitch_of(n) * C.tiles_of(n)
+    src = arena.input((C.tiles_of(n), 20, C.pitch_of(n)))
+    limit = arena.input((n,), t.int32)
+    limit.copy_(t.as_tensor((7 - np.arange(n) % 4).astype(np.int32)))
+    path = arena.state((8, pp))
+    fr = dict(trail=arena.state((n, 2), t.int64), cursor=arena.state((n,)), depth=arena.state((n,), t.int32), bound=arena.state((n,), t.int32),
+              next=arena.state((n,), t.int32), nodes=arena.state((n,), t.int64), status=arena.state((n,)))
+    args = [C.P(src), n, C.pitch_of(n), C.P(corner.table), corner.table.numel(), k, fixed["masks"], fixed["etabs"], fixed["ebytes"], C.P(path), 8, pp,
+            None, C.P(limit)] + [C.P(v) for v in fr.values()]
+    return n, src, limit, path, fr, args, fixed
+
+
+def _s_data(ctx, tabs_, w):
+    key = ("ida", w)
+    if key not in ctx.cache:
+        rows = bytes_of(env_of(3, _s_rows(w)))
+        frames = restated(rows, tabs_["best"][1], 8, 7 - np.arange(C.N) % 4)
+        ctx.cache[key] = (rows, frames)
+    return ctx.cache[key]
+
+
+def _s_check(path, fr, frames):
+    n = len(frames)
+    want = np.full((8, n), R.NOOP, np.uint8)
+    for c, f in enumerate(frames):
+        if f.status == R.SOLVED:
+            want[f.floor:f.depth, c] = f.nib[f.floor:f.depth]
+    assert (path[:, :n].cpu().numpy() == want).all(), "path"
+    assert fr["trail"].cpu().numpy().view(np.uint64).tolist() == [f.words for f in frames], "trail"
+    for k in ("cursor", "depth", "bound", "next", "nodes", "status"):
+        assert fr[k].cpu().numpy().tolist() == [getattr(f, k) for f in frames], k
+
+
+def _s_init(ctx, tabs_, arena):
+    _, _ida, _, _, _ = mods()
+    n, src, limit, path, fr, args, keep = _s_common(ctx, arena, tabs_["best"][0])
+    host_rows = {w: C.tiled(ctx, _s_data(ctx, tabs_, w)[0], n) for w in C.SETS}
+
+    def fill(w):
+        src.copy_(host_rows[w])
+        path.fill_(R.NOOP)
+        for v in fr.values():
+            v.fill_(0x55 if v.dtype == ctx.torch.uint8 else 0x55555555)
+    call = lambda: ctx.L.check(_ida.ida_lib().ida_init(*args, ctx.sp()))
+    built = C.built(call, [fill], lambda w: _s_check(path, fr, [f.clone() for f in _s_data(ctx, tabs_, w)[1]]))
+    built.keep = (keep, limit)                                               # the call holds their addresses only
+    return built
+
+
+def _s_search(ctx, tabs_, arena):
+    _, _ida, _, _, _ = mods()
+    n, src, limit, path, fr, args, keep = _s_common(ctx, arena, tabs_["best"][0])
+    running = arena.output((4,), ctx.torch.int32)
+    host_rows = {w: C.tiled(ctx, _s_data(ctx, tabs_, w)[0], n) for w in C.SETS}
+    start, done = {}, {}
+    for w in C.SETS:
+        frames = [f.clone() for f in _s_data(ctx, tabs_, w)[1]]
+        start[w] = dict(trail=np.array([f.words for f in frames], np.uint64).view(np.int64),
+                        **{k: np.array([getattr(f, k) for f in frames]) for k in ("cursor", "depth", "bound", "next", "nodes", "status")})
+        for f in frames:
+            f.run(max_passes=12)
+        done[w] = frames
+        assert sum(f.status == 0 for f in frames) > 0 and sum(f.status == R.SOLVED for f in frames) > n // 6
+
+    def fill(w):
+        src.copy_(host_rows[w])
+        path.fill_(R.NOOP)
+        for k, v in fr.items():
+            v.copy_(ctx.torch.as_tensor(start[w][k].astype(v.cpu().numpy().dtype)))
+
+    def check(w):
+        _s_check(path, fr, done[w])
+        assert running.cpu().numpy()[0] == sum(f.status == 0 for f in done[w]), "running"
+    call = lambda: ctx.L.check(_ida.ida_lib().ida_search(*args, 12, C.P(running), ctx.sp()))
+    built = C.built(call, [fill], check)
+    built.keep = (keep, limit)                                               # the call holds their addresses only
+    return built
+
+
+IDA_ROWS = {"ida_init": _s_init, "ida_search": _s_search}
+
+
+def test_every_launching_export_has_a_stream_row():
+    _, _ida, _, _, _ = mods()
+    assert set(IDA_ROWS) == set(_ida.IDA_SIGNATURES) - {"ida_max_steps", "ida_canonical"}   # those two launch nothing
+
+
+@pytest.fixture(scope="module")
+def ctx(oracle):
+    return C.Ctx(oracle, "cuda")
+
+
+@pytest.mark.parametrize("export", sorted(IDA_ROWS))
+def test_one_call_under_capture_and_replay(ctx, tabs, export):
+    from tests.test_gpu_stream_order import GraphBackend
+    try:
+        with torch.no_grad():
+            D.run(GraphBackend(ctx.ops, ctx.L), lambda arena: IDA_ROWS[export](ctx, tabs, arena))
+    except Exception as e:  # noqa: BLE001
+        if any(s in str(e) for s in ("illegal memory access", "HIP error", "hipError")) and "capture" not in str(e).lower():
+            pytest.exit(f"a GPU fault in this case: nothing more is started on the device -- {e}", returncode=3)
+        raise
+
+
+# ---------------------------------------------------------------------------------------------------------------- 7. random cubes
+def test_bounds_on_random_cubes_stay_below_the_chain_solution(tabs):
+    """1029 cubes scrambled by 100 moves, 2048 passes each: nothing is solved by luck that the chain's solution contradicts -- bound <=
+    chain_solve's length for every cube, length <= it where IDA* solved; the bound is at least the table's value."""
+    _, _, _, pattern, search = mods()
+    table = tabs["best"][0]
+    env = env_of(3, scrambles(3, [100] * 1029, seed=9))
+    chain = search.chain_solve(pattern.ChainTables.build(DEV), env)
+    assert bool(chain["solved"].all())
+    res = search.ida_search(table, env, limit=20, max_steps=2048)
+    h = table.distance(env).to(torch.int32)
+    assert bool((res["bound"] <= chain["length"]).all()) and bool((res["bound"] >= h).all())
+    s = res["solved"]
+    assert bool((res["length"][s] <= chain["length"][s]).all()) and bool((res["status"][~s] == 0).all())
+    assert int(res["nodes"].min()) > 0 and int(res["nodes"].max()) <= 2048
