@@ -37,10 +37,10 @@ class Library:
 
 
 LIBRARIES = {l.name: l for l in (
-    Library("hip", "_lib", "librubikhip.so", ("rubikhip.hip", "rc_host.h", "rc_device.h", "rc_tables.h", "rc_cubies.h", "rc_episode.h", "rubikhip.h"), _HIPCC, "RUBIKHIP_LIB", "rc_build_id",
-            "rc_last_error", headers=("rubikepisode.h",)),
+    Library("hip", "_lib", "librubikhip.so", ("rubikhip.hip", "rc_host.h", "rc_device.h", "rc_tables.h", "rc_table.h", "rc_cubies.h", "rc_edge.h", "rc_chain.h", "rc_ida.h",
+                                              "rc_episode.h", "rubikhip.h"), _HIPCC, "RUBIKHIP_LIB", "rc_build_id", "rc_last_error", headers=("rubikepisode.h",)),
     Library("tree", "_tree", "librubiktree.so", ("rc_tree.cpp", "rc_host.h", "rubiktree.h"), _GXX, "RUBIKTREE_LIB", "rc_tree_build_id", None),
-    Library("search", "_search_lib", "librubiksearch.so", ("rc_search.hip", "rc_host.h", "rc_device.h", "rc_tables.h", "rc_sym.h", "rc_sym_tables.h", "rubiksearch.h"),
+    Library("search", "_search_lib", "librubiksearch.so", ("rc_search.hip", "rc_host.h", "rc_device.h", "rc_tables.h", "rc_table.h", "rc_sym.h", "rc_sym_tables.h", "rubiksearch.h"),
             _HIPCC, "RUBIKSEARCH_LIB", "rc_search_build_id", "rc_search_last_error", headers=("rubiksym.h",)),
     Library("net", "_net_lib", "librubiknet.so", ("rc_net.hip", "rc_host.h", "rubiknet.h"), _HIPCC, "RUBIKNET_LIB", "rc_net_build_id", "rc_net_last_error"))}
 HIP_SOURCES, TREE_SOURCES, SEARCH_SOURCES, NET_SOURCES = (LIBRARIES[n].sources for n in ("hip", "tree", "search", "net"))

@@ -1294,11 +1294,6 @@ struct EdgeCoord {
     uint32_t pos, ori;
 };
 
-// THE GUARD of the edge tables: the only place a table address is formed.  n = N(k); the host has checked bytes >= n.
-__device__ __forceinline__ uint32_t edge_table_at(const uint8_t *table, uint32_t idx, uint32_t n) {
-    return idx < n ? (uint32_t)table[idx] : 0xFFu;
-}
-
 // idx < N(k) (the caller checks): index = perm * 2^k + sum o_i 2^i, perm = sum d_i * prod_{j > i} (12 - j), d_i = the rank of p_i
 // among the slots p_0 .. p_{i-1} have left free
 __device__ __forceinline__ EdgeCoord edge_unrank(uint32_t idx, uint32_t k) {

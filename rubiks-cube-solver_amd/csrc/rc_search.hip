@@ -25,6 +25,7 @@
 #include "../../include/rubiksearch.h"
 #include "rc_device.h"
 #include "rc_host.h"
+#include "rc_table.h"
 
 using namespace rc;
 
@@ -504,7 +505,6 @@ __global__ void __launch_bounds__(256) k_fill16(uint4 *p, int64_t n16, uint32_t 
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i < n16) p[i] = make_uint4(i == 0 ? first : v, v, v, v);
 }
-__global__ void k_store32(uint32_t *p, uint32_t v) { *p = v; }
 
 // ------------------------------------------------------------------------------------------------- host side
 // -1: bad argument, -2: a HIP call failed (include/rubiksearch.h)
@@ -1062,37 +1062,23 @@ int rca_backtrack(int64_t n, int cube_size, int64_t capacity, const int32_t *poo
 // The rcp_* entry points (include/rubiksearch.h "Corner pattern database", DESIGN.md "Corner pattern database"), on rc_device.h's
 // corner coordinates (corners_of / corner_index_of: stickers -> index; corner_unrank / corner_move / corner_rank: the index space).
 //
-//   k_pdb_level    one lane per table entry, PULL: an entry that is still 0xFF unranks itself, ranks its A neighbours and becomes
-//                  depth + 1 iff one of them holds `depth`.  A lane writes its own entry only; a neighbour another lane is writing
-//                  meanwhile reads 0xFF or depth + 1, neither of which is `depth`: the table after a level does not depend on timing
+//   CornerLevels   the corner index space of a cube size under rc_table.h k_table_level: A neighbours per entry
 //   k_pdb_unrank   index -> cubie rows, 4 cubes per lane (one dword per row; the ragged last pack byte by byte)
 //   k_pdb_lookup   the 24 corner sticker rows (+ the 3 fixed ones of the 2x2x2) -> dist, 4 cubes per lane
 //   k_pdb_score    4 consecutive key slots per lane -> their corner stickers as packed bytes -> scores
-// THE GUARD.  Every table address of these kernels is formed in table_at() below and nowhere else: it compares the index with the
-// compile-time table size N (the host has checked bytes >= N) before the load.  corner_index_of gives all-ones for an illegal corner
-// state, which fails that test like any other index >= N; the build's neighbour indices pass through it too.
+// Every table read goes through rc_table.h table_at with the compile-time table size N; corner_index_of gives all-ones for an illegal
+// corner state, which the guard turns into 0xFF.
 namespace {
 
 template <class T>
-__device__ __forceinline__ uint32_t table_at(const uint8_t *table, uint32_t idx) {
-    return idx < CornerSpace<T>::N ? (uint32_t)table[idx] : 0xFFu;       // THE GUARD: no load for an index outside the table
-}
-
-template <class T>
-__global__ void __launch_bounds__(256) k_pdb_level(uint8_t *table, uint32_t depth, uint32_t *count) {
-    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    bool set = false;
-    if (table_at<T>(table, i) == 0xFFu && i < CornerSpace<T>::N) {       // past N table_at reads nothing and says 0xFF
-        const CornerCoord c = corner_unrank<T>(i);
-        sfor<T::A>([&](auto ac) {
-            constexpr int A_ = decltype(ac)::value;
-            if (!set) set = table_at<T>(table, corner_rank<T>(corner_move<T, A_>(c))) == depth;
-        });
-        if (set) table[i] = (uint8_t)(depth + 1u);                       // the lane's own entry
-    }
-    const unsigned long long bal = __ballot(set);
-    if ((threadIdx.x & 63) == 0 && bal) atomicAdd(count, (uint32_t)__popcll(bal));
-}
+struct CornerLevels {
+    static constexpr int kNeighbours = T::A;
+    __host__ __device__ static constexpr uint32_t n() { return CornerSpace<T>::N; }
+    __device__ void block_begin() const {}
+    __device__ CornerCoord unrank(uint32_t i) const { return corner_unrank<T>(i); }
+    template <int A_>
+    __device__ uint32_t neighbour(CornerCoord c) const { return corner_rank<T>(corner_move<T, A_>(c)); }
+};
 
 struct UnrankArgs {
     const uint32_t *index;
@@ -1108,15 +1094,8 @@ __global__ void __launch_bounds__(256) k_pdb_unrank(UnrankArgs a) {
     const int64_t n0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
     if (n0 >= a.n) return;
     const bool full = n0 + 4 <= a.n;
-    uint32_t idx[4] = {0u, 0u, 0u, 0u};
-    if (full) {
-        const u32x4 u = *reinterpret_cast<const u32x4 *>(a.index + n0);
-        idx[0] = u[0]; idx[1] = u[1]; idx[2] = u[2]; idx[3] = u[3];
-    } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-            if (n0 + j < a.n) idx[j] = a.index[n0 + j];
-    }
+    uint32_t idx[4];
+    load_index4(a.index, n0, a.n, full, 0u, idx);
     uint32_t row[T::SLOTS] = {};
     bool bad = false;
 #pragma unroll
@@ -1147,17 +1126,7 @@ __global__ void __launch_bounds__(256) k_pdb_unrank(UnrankArgs a) {
         }
     }
     if (bad) *a.bad = 1;                                                  // every writer stores the same byte
-    uint8_t *dst = a.cubies + (a.sh >= 63 ? n0 : tiled(n0, a.pitch, a.sh, T::SLOTS));   // n0 % 4 == 0, pitch % 16 == 0: one tile, dword aligned
-    if (full) {
-#pragma unroll
-        for (int q = 0; q < T::SLOTS; ++q) *reinterpret_cast<uint32_t *>(dst + (int64_t)q * a.pitch) = row[q];
-    } else {
-#pragma unroll
-        for (int q = 0; q < T::SLOTS; ++q)
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                if (n0 + j < a.n) dst[(int64_t)q * a.pitch + j] = (uint8_t)(row[q] >> (8 * j));   // pad columns keep their bytes
-    }
+    store_cubie_rows4(a.cubies, n0, a.n, full, a.pitch, a.sh, row);
 }
 
 // the 4 distances of a pack as bytes
@@ -1165,7 +1134,7 @@ template <class T>
 __device__ __forceinline__ void pack_distances(const Corners<T, 1> &c, const uint8_t *table, uint32_t (&d)[4]) {
     sfor<4>([&](auto jc) {
         constexpr int j = decltype(jc)::value;
-        d[j] = table_at<T>(table, corner_index_of<T, 1, j>(c));
+        d[j] = table_at(table, corner_index_of<T, 1, j>(c), CornerSpace<T>::N);
     });
 }
 
@@ -1315,12 +1284,9 @@ __global__ void __launch_bounds__(kSelThreads) k_pdb_relax(RelaxArgs a) {
     }
 }
 
-// a table operand: present, 16-byte aligned, and large enough for every index below N
 template <class T>
-int table_arg(const char *fn, const void *table, int64_t bytes) {
-    if (!table || !aligned16(table)) return fail(fn, "table is NULL or not 16-byte aligned");
-    if (bytes < (int64_t)CornerSpace<T>::N) return fail(fn, "bytes is smaller than rcp_table_bytes()");
-    return 0;
+int corner_table_arg(const char *fn, const void *table, int64_t bytes) {
+    return table_arg(fn, table, bytes, CornerSpace<T>::N, "rcp_table_bytes()");
 }
 
 }  // namespace
@@ -1341,7 +1307,7 @@ int rcp_tables(int cube_size, uint8_t *src, uint8_t *twist) {
 int rcp_build_begin(uint8_t *table, int64_t bytes, int cube_size, void *stream) {
     return by_size(cube_size, [&](auto t) {
         using T = decltype(t);
-        if (int rc = table_arg<T>("rcp_build_begin", table, bytes)) return rc;
+        if (int rc = corner_table_arg<T>("rcp_build_begin", table, bytes)) return rc;
         static_assert(CornerSpace<T>::N % 16 == 0, "the table is filled 16 bytes at a time");
         return fill16(table, (int64_t)CornerSpace<T>::N, ~0u, 0xFFFFFF00u, S(stream));   // every entry 0xFF; corner_index(solved) = 0: byte 0 is 0
     });
@@ -1350,14 +1316,8 @@ int rcp_build_begin(uint8_t *table, int64_t bytes, int cube_size, void *stream) 
 int rcp_build_level(uint8_t *table, int64_t bytes, int cube_size, int depth, uint32_t *count, void *stream) {
     return by_size(cube_size, [&](auto t) {
         using T = decltype(t);
-        if (int rc = table_arg<T>("rcp_build_level", table, bytes)) return rc;
-        if (depth < 0 || depth >= 254) return fail("rcp_build_level: depth must be in 0..253");
-        if (!count || !aligned16(count)) return fail("rcp_build_level: count is NULL or not 16-byte aligned");
-        hipLaunchKernelGGL(k_store32, dim3(1), dim3(1), 0, S(stream), count, 0u);
-        RC_HIP(-2, hipGetLastError());
-        hipLaunchKernelGGL((k_pdb_level<T>), dim3((CornerSpace<T>::N + 255u) / 256u), dim3(256), 0, S(stream), table, (uint32_t)depth, count);
-        RC_HIP(-2, hipGetLastError());
-        return 0;
+        if (int rc = corner_table_arg<T>("rcp_build_level", table, bytes)) return rc;
+        return table_build_level("rcp_build_level", table, CornerLevels<T>{}, depth, count, S(stream), -2);
     });
 }
 
@@ -1388,7 +1348,7 @@ int rcp_lookup(const uint8_t *stp, int64_t n, int64_t pitch, int cube_size, cons
         if (!stp || !aligned16(stp)) return fail("rcp_lookup: st is NULL or not 16-byte aligned");
         const int sh = tile_shift(pitch, n, T::S);
         if (sh < 0) return fail("rcp_lookup: pitch: need pitch % 16 == 0 and pitch >= n_cubes, or a power-of-two tile >= 512");
-        if (int rc = table_arg<T>("rcp_lookup", table, bytes)) return rc;
+        if (int rc = corner_table_arg<T>("rcp_lookup", table, bytes)) return rc;
         if (!dist || !aligned16(dist)) return fail("rcp_lookup: dist is NULL or not 16-byte aligned");
         if (n == 0) return 0;
         const int64_t blocks = ceil_div(n, kSpan);
@@ -1407,7 +1367,7 @@ int rcp_score_keys(const uint64_t *keys, int64_t n, int width, int64_t pitch, in
         Geo g;
         if (int rc = geometry<T>(n, width, pitch, g)) return rc;
         if (!keys || !aligned16(keys)) return fail("rcp_score_keys: keys is NULL or not 16-byte aligned");
-        if (int rc = table_arg<T>("rcp_score_keys", table, bytes)) return rc;
+        if (int rc = corner_table_arg<T>("rcp_score_keys", table, bytes)) return rc;
         if (!scores || !aligned16(scores)) return fail("rcp_score_keys: scores is NULL or not 16-byte aligned");
         const int64_t total = (int64_t)T::A * g.nbp;                       // a multiple of 512
         hipLaunchKernelGGL((k_pdb_score<T>), dim3((unsigned)ceil_div(total, 1024)), dim3(256), 0, S(stream), keys, total, table, scores);

@@ -38,6 +38,7 @@
 #include "../../include/rubikhip.h"
 #include "rc_device.h"
 #include "rc_host.h"
+#include "rc_table.h"
 
 using namespace rc;
 
@@ -2208,6 +2209,12 @@ int rc_read_status(uint32_t *status, void *stream) {
 
 // the rcc_* section of include/rubikhip.h: cubie coordinates and the legality test
 #include "rc_cubies.h"
+
+// the distance tables of include/rubikhip.h, on rc_table.h; each may use the ones before it: rce_* edge pattern databases,
+// rct_* subgroup chain, ida_* iterative-deepening A*
+#include "rc_edge.h"
+#include "rc_chain.h"
+#include "rc_ida.h"
 
 // the rcx_* extension (include/rubikepisode.h): episode bookkeeping and the masked re-scramble
 #include "rc_episode.h"

@@ -26,6 +26,57 @@ MAX_LEVELS = 32        # a build that has not finished by then is an error (the 
 ILLEGAL = 0xFF         # distance() of a cube whose corners are no legal corner state
 
 
+def _device(device):
+    """torch.device(device), "cuda" resolved to the current device's index."""
+    dev = torch.device(device)
+    if dev.type == "cuda" and dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    return dev
+
+
+def _check_table(t, n, what, tables="the table", every="the table"):
+    """ValueError unless t can be `what`: a contiguous uint8 tensor of n entries on a HIP device, 16-byte aligned.  Nothing here
+    touches the device."""
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.dim() != 1 or t.numel() != n or not t.is_contiguous():
+        raise ValueError(f"{what} is a contiguous uint8 tensor of {n} entries, got "
+                         f"{tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__}"
+                         f"{' of ' + str(t.dtype) if isinstance(t, torch.Tensor) else ''}")
+    if not t.is_cuda:
+        raise ValueError(f"{tables} must live on a HIP device (there is no CPU fallback), got {t.device}")
+    if t.data_ptr() % 16:
+        raise ValueError(f"{every} must start 16-byte aligned (a slice at an odd offset?)")
+
+
+def _index_buffer(indices, device):
+    """(int32 device buffer padded to 16 bytes, n) of any 1-D integer tensor or sequence of uint32 values."""
+    idx = torch.as_tensor(indices).to(device)
+    if idx.dim() != 1 or idx.dtype.is_floating_point:
+        raise ValueError("indices must be a 1-D integer tensor or sequence")
+    n = idx.numel()
+    if idx.dtype != torch.int32:                           # uint32 values in an int32 tensor (torch has no arithmetic on uint32)
+        if n and (int(idx.min()) < 0 or int(idx.max()) > 0xFFFFFFFF):
+            raise ValueError("indices must be in 0..2^32 - 1")
+        idx = torch.where(idx >= 1 << 31, idx - (1 << 32), idx).to(torch.int32)
+    buf = torch.empty(_lib.pitch_for(max(n, 1) * 4, 16) // 4, dtype=torch.int32, device=device)
+    buf[:n] = idx
+    return buf, n
+
+
+def _build_levels(begin, level, table, n, dev, first_level, what):
+    """Breadth-first over an index space: begin(ptr, n, stream), then level(ptr, n, depth, count ptr, stream) per distance until a
+    level sets nothing (the count is read back once per level).  -> entries per distance; first_level(table): those at distance 0."""
+    count = torch.zeros(4, dtype=torch.int32, device=dev)  # one uint32, 16-byte aligned
+    begin(ptr(table), n, stream_ptr(dev))
+    levels = [first_level(table)]
+    for depth in range(MAX_LEVELS + 1):
+        level(ptr(table), n, depth, ptr(count), stream_ptr(dev))
+        c = int(count[0])
+        if c == 0:
+            return levels
+        levels.append(c)
+    raise RuntimeError(f"{what} has more than {MAX_LEVELS} levels")
+
+
 class CornerTable:
     """table: uint8 device tensor [N], N = rcp_table_bytes(cube_size); levels: states per distance (None for a wrapped tensor)."""
 
@@ -34,15 +85,7 @@ class CornerTable:
         that cannot be one: wrong size, dtype or device are found before the device is touched, table[0] != 0 by reading one byte."""
         if cube_size not in (2, 3):
             raise ValueError(f"cube_size must be 2 or 3, got {cube_size!r}")
-        n = _pattern_lib.table_bytes(cube_size)
-        if not isinstance(table, torch.Tensor) or table.dtype != torch.uint8 or table.dim() != 1 or table.numel() != n or not table.is_contiguous():
-            raise ValueError(f"a {cube_size}x{cube_size}x{cube_size} corner table is a contiguous uint8 tensor of {n} entries, got "
-                             f"{tuple(table.shape) if isinstance(table, torch.Tensor) else type(table).__name__}"
-                             f"{' of ' + str(table.dtype) if isinstance(table, torch.Tensor) else ''}")
-        if not table.is_cuda:
-            raise ValueError(f"the table must live on a HIP device (there is no CPU fallback), got {table.device}")
-        if table.data_ptr() % 16:
-            raise ValueError("the table must start 16-byte aligned (a slice at an odd offset?)")
+        _check_table(table, _pattern_lib.table_bytes(cube_size), f"a {cube_size}x{cube_size}x{cube_size} corner table")
         if levels is None and int(table[0]) != 0:
             raise ValueError("not a corner table: table[0], the solved state's distance, is not 0")
         self.table, self.cube_size, self.device = table, int(cube_size), table.device
@@ -53,22 +96,14 @@ class CornerTable:
         """Breadth-first over the index space: rcp_build_begin, then one rcp_build_level per distance until a level sets nothing (the
         count is read back once per level)."""
         n = _pattern_lib.table_bytes(cube_size)                # NotImplementedError for another size
-        dev = torch.device(device)
-        if dev.type == "cuda" and dev.index is None:
-            dev = torch.device("cuda", torch.cuda.current_device())
+        dev = _device(device)
         _lib.init(dev)
         L = _pattern_lib.pattern_lib()
         table = torch.empty(n, dtype=torch.uint8, device=dev)
-        count = torch.zeros(4, dtype=torch.int32, device=dev)  # one uint32, 16-byte aligned
-        check(L.rcp_build_begin(ptr(table), n, cube_size, stream_ptr(dev)))
-        levels = [1]
-        for depth in range(MAX_LEVELS + 1):
-            check(L.rcp_build_level(ptr(table), n, cube_size, depth, ptr(count), stream_ptr(dev)))
-            c = int(count[0])
-            if c == 0:
-                return cls(table, cube_size, levels)
-            levels.append(c)
-        raise RuntimeError(f"the corner table of the {cube_size}x{cube_size}x{cube_size} has more than {MAX_LEVELS} levels")
+        levels = _build_levels(lambda t, n, st: check(L.rcp_build_begin(t, n, cube_size, st)),
+                               lambda t, n, depth, count, st: check(L.rcp_build_level(t, n, cube_size, depth, count, st)),
+                               table, n, dev, lambda table: 1, f"the corner table of the {cube_size}x{cube_size}x{cube_size}")
+        return cls(table, cube_size, levels)
 
     @property
     def depth(self):
@@ -97,16 +132,7 @@ class CornerTable:
     def cubies(self, indices, out=None, cubie_pitch=None, bad=None):
         """rcp_unrank: corner indices (any integer tensor or sequence; values >= N are flagged) -> cubie rows in the rcc_* layout.  bad:
         the flag, a uint8 device tensor [1] the caller zeroes and reads; None: read back at once and raised as IndexError."""
-        idx = torch.as_tensor(indices).to(self.device)
-        if idx.dim() != 1 or idx.dtype.is_floating_point:
-            raise ValueError("indices must be a 1-D integer tensor or sequence")
-        n = idx.numel()
-        if idx.dtype != torch.int32:                           # uint32 values in an int32 tensor (torch has no arithmetic on uint32)
-            if n and (int(idx.min()) < 0 or int(idx.max()) > 0xFFFFFFFF):
-                raise ValueError("indices must be in 0..2^32 - 1")
-            idx = torch.where(idx >= 1 << 31, idx - (1 << 32), idx).to(torch.int32)
-        buf = torch.empty(_lib.pitch_for(max(n, 1) * 4, 16) // 4, dtype=torch.int32, device=self.device)
-        buf[:n] = idx
+        buf, n = _index_buffer(indices, self.device)
         SL = ops._size(self.cube_size)[2]
         if out is None:
             out = ops.alloc_code(n, self.cube_size, self.device, cubie_pitch)
@@ -151,15 +177,7 @@ class EdgeTable:
             raise ValueError(f"edge tables exist for the 3x3x3 only (the 2x2x2 has no edges), got cube_size {cube_size!r}")
         self.mask = _edge_lib.edge_mask(edges)
         self.edges = tuple(e for e in range(_edge_lib.N_EDGES) if self.mask >> e & 1)
-        n = _edge_lib.table_bytes(self.mask)
-        if not isinstance(table, torch.Tensor) or table.dtype != torch.uint8 or table.dim() != 1 or table.numel() != n or not table.is_contiguous():
-            raise ValueError(f"an edge table of the pieces {self.edges} is a contiguous uint8 tensor of {n} entries, got "
-                             f"{tuple(table.shape) if isinstance(table, torch.Tensor) else type(table).__name__}"
-                             f"{' of ' + str(table.dtype) if isinstance(table, torch.Tensor) else ''}")
-        if not table.is_cuda:
-            raise ValueError(f"the table must live on a HIP device (there is no CPU fallback), got {table.device}")
-        if table.data_ptr() % 16:
-            raise ValueError("the table must start 16-byte aligned (a slice at an odd offset?)")
+        _check_table(table, _edge_lib.table_bytes(self.mask), f"an edge table of the pieces {self.edges}")
         self.home = _edge_lib.home_index(self.mask)
         if levels is None and int(table[self.home]) != 0:
             raise ValueError(f"not an edge table of the pieces {self.edges}: table[{self.home}], the home pattern's distance, is not 0")
@@ -175,22 +193,14 @@ class EdgeTable:
             raise ValueError(f"edge tables exist for the 3x3x3 only (the 2x2x2 has no edges), got cube_size {cube_size!r}")
         mask = _edge_lib.edge_mask(edges)
         n = _edge_lib.table_bytes(mask)
-        dev = torch.device(device)
-        if dev.type == "cuda" and dev.index is None:
-            dev = torch.device("cuda", torch.cuda.current_device())
+        dev = _device(device)
         _lib.init(dev)
         L = _edge_lib.edge_lib()
         table = torch.empty(n, dtype=torch.uint8, device=dev)
-        count = torch.zeros(4, dtype=torch.int32, device=dev)  # one uint32, 16-byte aligned
-        _lib.check(L.rce_build_begin(ptr(table), n, mask, stream_ptr(dev)))
-        levels = [1]
-        for depth in range(MAX_LEVELS + 1):
-            _lib.check(L.rce_build_level(ptr(table), n, mask, depth, ptr(count), stream_ptr(dev)))
-            c = int(count[0])
-            if c == 0:
-                return cls(table, mask, levels)
-            levels.append(c)
-        raise RuntimeError(f"the edge table of mask {mask:#x} has more than {MAX_LEVELS} levels")
+        levels = _build_levels(lambda t, n, st: _lib.check(L.rce_build_begin(t, n, mask, st)),
+                               lambda t, n, depth, count, st: _lib.check(L.rce_build_level(t, n, mask, depth, count, st)),
+                               table, n, dev, lambda table: 1, f"the edge table of mask {mask:#x}")
+        return cls(table, mask, levels)
 
     @property
     def depth(self):
@@ -227,16 +237,7 @@ class EdgeTable:
         with that pattern.  bad: the flag, a uint8 device tensor [1] the caller zeroes and reads; None: read back at once and raised
         as IndexError."""
         from . import _edge_lib
-        idx = torch.as_tensor(indices).to(self.device)
-        if idx.dim() != 1 or idx.dtype.is_floating_point:
-            raise ValueError("indices must be a 1-D integer tensor or sequence")
-        n = idx.numel()
-        if idx.dtype != torch.int32:                           # uint32 values in an int32 tensor (torch has no arithmetic on uint32)
-            if n and (int(idx.min()) < 0 or int(idx.max()) > 0xFFFFFFFF):
-                raise ValueError("indices must be in 0..2^32 - 1")
-            idx = torch.where(idx >= 1 << 31, idx - (1 << 32), idx).to(torch.int32)
-        buf = torch.empty(_lib.pitch_for(max(n, 1) * 4, 16) // 4, dtype=torch.int32, device=self.device)
-        buf[:n] = idx
+        buf, n = _index_buffer(indices, self.device)
         if out is None:
             out = ops.alloc_code(n, 3, self.device, cubie_pitch)
         p = ops._state_arg(out, 20, n, cubie_pitch, "cubies out")
@@ -324,17 +325,9 @@ class ChainTables:
         if len(tables) != _chain_lib.STAGES:
             raise ValueError(f"a chain has {_chain_lib.STAGES} tables, got {len(tables)}")
         for s, t in enumerate(tables):
-            n = _chain_lib.table_bytes(s)
-            if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.dim() != 1 or t.numel() != n or not t.is_contiguous():
-                raise ValueError(f"the table of stage {s} is a contiguous uint8 tensor of {n} entries, got "
-                                 f"{tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__}"
-                                 f"{' of ' + str(t.dtype) if isinstance(t, torch.Tensor) else ''}")
-            if not t.is_cuda:
-                raise ValueError(f"the tables must live on a HIP device (there is no CPU fallback), got {t.device}")
+            _check_table(t, _chain_lib.table_bytes(s), f"the table of stage {s}", "the tables", "every table")
             if t.device != tables[0].device:
                 raise ValueError(f"the tables of a chain must live on one device, got {[str(x.device) for x in tables]}")
-            if t.data_ptr() % 16:
-                raise ValueError("every table must start 16-byte aligned (a slice at an odd offset?)")
         self.tables, self.device = tables, tables[0].device
         self.levels = None if levels is None else tuple(tuple(int(c) for c in lv) for lv in levels)
 
@@ -345,28 +338,16 @@ class ChainTables:
         from . import _chain_lib
         if cube_size != 3:
             raise ValueError(f"the subgroup chain exists for the 3x3x3 only, got cube_size {cube_size!r}")
-        dev = torch.device(device)
-        if dev.type == "cuda" and dev.index is None:
-            dev = torch.device("cuda", torch.cuda.current_device())
+        dev = _device(device)
         _lib.init(dev)
         L = _chain_lib.chain_lib()
-        count = torch.zeros(4, dtype=torch.int32, device=dev)  # one uint32, 16-byte aligned
         tables, levels = [], []
         for stage in range(_chain_lib.STAGES):
             n = _chain_lib.table_bytes(stage)
-            table = torch.empty(n, dtype=torch.uint8, device=dev)
-            _lib.check(L.rct_build_begin(ptr(table), n, stage, stream_ptr(dev)))
-            lv = [int((table == 0).sum())]
-            for depth in range(MAX_LEVELS + 1):
-                _lib.check(L.rct_build_level(ptr(table), n, stage, depth, ptr(count), stream_ptr(dev)))
-                c = int(count[0])
-                if c == 0:
-                    break
-                lv.append(c)
-            else:
-                raise RuntimeError(f"the table of stage {stage} has more than {MAX_LEVELS} levels")
-            tables.append(table)
-            levels.append(lv)
+            tables.append(torch.empty(n, dtype=torch.uint8, device=dev))
+            levels.append(_build_levels(lambda t, n, st: _lib.check(L.rct_build_begin(t, n, stage, st)),
+                                        lambda t, n, depth, count, st: _lib.check(L.rct_build_level(t, n, stage, depth, count, st)),
+                                        tables[-1], n, dev, lambda table: int((table == 0).sum()), f"the table of stage {stage}"))
         return cls(tables, levels)
 
     @property
@@ -414,16 +395,7 @@ class ChainTables:
         caller zeroes and reads; None: read back at once and raised as IndexError."""
         from . import _chain_lib
         stage = _chain_lib.check_stage(stage)
-        idx = torch.as_tensor(indices).to(self.device)
-        if idx.dim() != 1 or idx.dtype.is_floating_point:
-            raise ValueError("indices must be a 1-D integer tensor or sequence")
-        n = idx.numel()
-        if idx.dtype != torch.int32:                           # uint32 values in an int32 tensor (torch has no arithmetic on uint32)
-            if n and (int(idx.min()) < 0 or int(idx.max()) > 0xFFFFFFFF):
-                raise ValueError("indices must be in 0..2^32 - 1")
-            idx = torch.where(idx >= 1 << 31, idx - (1 << 32), idx).to(torch.int32)
-        buf = torch.empty(_lib.pitch_for(max(n, 1) * 4, 16) // 4, dtype=torch.int32, device=self.device)
-        buf[:n] = idx
+        buf, n = _index_buffer(indices, self.device)
         if out is None:
             out = ops.alloc_code(n, 3, self.device, cubie_pitch)
         p = ops._state_arg(out, 20, n, cubie_pitch, "cubies out")

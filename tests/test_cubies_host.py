@@ -62,7 +62,8 @@ def test_header_exports_and_signature_table_agree():
     # no new library: the build id is the hash of the source list, the section's own file (csrc/rc_cubies.h) included
     assert list(_build.LIBRARIES) == ["hip", "tree", "search", "net"]
     src = [os.path.basename(p) for p in _build.LIBRARIES["hip"].sources]
-    assert src == ["rubikhip.hip", "rc_host.h", "rc_device.h", "rc_tables.h", "rc_cubies.h", "rc_episode.h", "rubikhip.h", "rubikepisode.h"]
+    assert src == ["rubikhip.hip", "rc_host.h", "rc_device.h", "rc_tables.h", "rc_table.h", "rc_cubies.h", "rc_edge.h", "rc_chain.h", "rc_ida.h", "rc_episode.h",
+                   "rubikhip.h", "rubikepisode.h"]
     assert _lib.build_id() == _build.source_hash(_build.LIBRARIES["hip"].sources) == _build.embedded_id(_lib.LIB_PATH)
 
 

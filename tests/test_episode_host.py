@@ -42,7 +42,8 @@ def test_header_exports_and_signature_table_agree():
     assert not set(_lib.SIGNATURES) & set(_episode_lib.EPISODE_SIGNATURES)
     # the extension's sources are part of the library's identity, after the files that were hashed before, in their old order
     src = [os.path.basename(p) for p in _build.LIBRARIES["hip"].sources]
-    assert [s for s in src if s not in ("rc_episode.h", "rubikepisode.h")] == ["rubikhip.hip", "rc_host.h", "rc_device.h", "rc_tables.h", "rc_cubies.h", "rubikhip.h"]
+    assert [s for s in src if s not in ("rc_episode.h", "rubikepisode.h")] == ["rubikhip.hip", "rc_host.h", "rc_device.h", "rc_tables.h", "rc_table.h", "rc_cubies.h", "rc_edge.h",
+                                                                             "rc_chain.h", "rc_ida.h", "rubikhip.h"]
     assert "rc_episode.h" in src and src[-1] == "rubikepisode.h"
     assert _episode_lib.build_tag() == _lib.build_id() == _build.source_hash(_build.LIBRARIES["hip"].sources)
 

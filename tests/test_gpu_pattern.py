@@ -93,6 +93,51 @@ def test_build_levels_and_the_restatement(tables, host_tables, ref222):
         pattern.CornerTable(broken, 2)
 
 
+def _level_builders():
+    """(name, N, begin(table), level(table, depth, count)) of the users of the one level kernel: the 2x2x2 corner space, the edge
+    spaces of mask 0x3 (528 entries; its home index is 0) and of mask 0x6 (528 entries, home index 48: the goal is not entry 0) and
+    chain stage 3 (the LDS prologue, entries no cube has)."""
+    from rubiks_cube_solver_amd import _chain_lib, _edge_lib, _search_lib
+    _lib, P, _, _, _ = mods()
+    ptr, st = _lib.ptr, stream()
+    Lp, Le, Lc = P.pattern_lib(), _edge_lib.edge_lib(), _chain_lib.chain_lib()
+    assert _edge_lib.home_index(0x6) != 0
+
+    def edge(mask):
+        return (f"edge mask {mask:#x}", _edge_lib.table_bytes(mask), lambda t: _lib.check(Le.rce_build_begin(ptr(t), t.numel(), mask, st)),
+                lambda t, d, c: _lib.check(Le.rce_build_level(ptr(t), t.numel(), mask, d, ptr(c), st)))
+    return (("corner 2x2x2", P.table_bytes(2), lambda t: _search_lib.check(Lp.rcp_build_begin(ptr(t), t.numel(), 2, st)),
+             lambda t, d, c: _search_lib.check(Lp.rcp_build_level(ptr(t), t.numel(), 2, d, ptr(c), st))),
+            edge(0x3), edge(0x6),
+            ("chain stage 3", _chain_lib.table_bytes(3), lambda t: _lib.check(Lc.rct_build_begin(ptr(t), t.numel(), 3, st)),
+             lambda t, d, c: _lib.check(Lc.rct_build_level(ptr(t), t.numel(), 3, d, ptr(c), st))))
+
+
+def test_every_level_of_the_shared_level_kernel():
+    """One level kernel, three index spaces: after EVERY level of each build the returned count is the number of entries that hold
+    depth + 1, nothing but 0xFF lies above depth + 1, and what earlier levels set is unchanged."""
+    _lib, _, _, pattern, _ = mods()
+    _lib.init(torch.device(DEV, torch.cuda.current_device()))
+    for name, n, begin, level in _level_builders():
+        assert n in (3674160, 528, 1327104)
+        table = torch.empty(n, dtype=torch.uint8, device=DEV)
+        count = torch.zeros(4, dtype=torch.int32, device=DEV)
+        begin(table)
+        assert int((table == 0).sum()) >= 1 and bool(((table == 0) | (table == 0xFF)).all()), name
+        for depth in range(pattern.MAX_LEVELS + 1):
+            before = table.clone()
+            level(table, depth, count)
+            c, was_set = int(count[0]), before != 0xFF
+            assert c == int((table == depth + 1).sum()), (name, depth)
+            assert not bool(((table > depth + 1) & (table != 0xFF)).any()), (name, depth)
+            assert torch.equal(table[was_set], before[was_set]), (name, depth)
+            if c == 0:
+                break
+        else:
+            raise AssertionError(f"{name}: no empty level within {pattern.MAX_LEVELS + 1}")
+        assert depth >= 1, name
+
+
 # --------------------------------------------------------------------------------------------------------- 2. rank / unrank
 @pytest.mark.parametrize("cs", (2, 3))
 def test_unrank_then_rank_is_the_identity(tables, cs):

@@ -178,13 +178,14 @@ def test_header_exports_and_signature_table_agree():
     assert not set(_search_lib.SIGNATURES) & set(_sym_lib.SYM_SIGNATURES)
     # the new sources are part of the library's identity: before rubiksearch.h, the public header last
     src = [os.path.basename(p) for p in _build.LIBRARIES["search"].sources]
-    assert src == ["rc_search.hip", "rc_host.h", "rc_device.h", "rc_tables.h", "rc_sym.h", "rc_sym_tables.h", "rubiksearch.h", "rubiksym.h"]
+    assert src == ["rc_search.hip", "rc_host.h", "rc_device.h", "rc_tables.h", "rc_table.h", "rc_sym.h", "rc_sym_tables.h", "rubiksearch.h", "rubiksym.h"]
     assert _search_lib.build_id() == _build.source_hash(_build.LIBRARIES["search"].sources)
     without = [p for p in _build.LIBRARIES["search"].sources if os.path.basename(p) not in ("rc_sym.h", "rc_sym_tables.h", "rubiksym.h")]
     assert _build.source_hash(without) != _search_lib.build_id()
     # librubikhip.so does not see the new files: rc_tables.h and its source list are what they were
-    assert [os.path.basename(p) for p in _build.LIBRARIES["hip"].sources] == ["rubikhip.hip", "rc_host.h", "rc_device.h", "rc_tables.h", "rc_cubies.h",
-                                                                              "rc_episode.h", "rubikhip.h", "rubikepisode.h"]
+    assert [os.path.basename(p) for p in _build.LIBRARIES["hip"].sources] == ["rubikhip.hip", "rc_host.h", "rc_device.h", "rc_tables.h", "rc_table.h",
+                                                                              "rc_cubies.h", "rc_edge.h", "rc_chain.h", "rc_ida.h", "rc_episode.h",
+                                                                              "rubikhip.h", "rubikepisode.h"]
 
 
 def test_python_argument_errors_come_before_any_device_use():
