@@ -618,6 +618,100 @@ int ida_search(const uint8_t *cubies, int64_t n, int64_t cubie_pitch, const uint
                const int32_t *floor, const int32_t *limit, uint64_t *trail, uint8_t *cursor, int32_t *depth, int32_t *bound, int32_t *next,
                uint64_t *nodes, uint8_t *status, int64_t max_steps, uint32_t *running, void *stream);
 
+/* ---------------------------------------------------------------------------------------------------------------------------------
+ * Two-phase (prefix tp_): Kociemba's two-phase algorithm -- a SHORT solution of any cube.  Phase 1 searches for ways into
+ * G1 = <U,D,F2,R2,B2,L2> (the goal set of the chain's stage 1), phase 2 solves each G1 cube found, optimally within G1, under four
+ * coset-distance tables of about 1 MB each.  3x3x3 ONLY.  No reference counterpart.  The prefix does not start with "rc" for the
+ * reason given in the ida_* section.
+ *
+ * THE RULE.  Cubie bytes, cp/co/ep/eo, lehmer and subset ranks as in the rcc_* / rct_* sections; the move tables are rcp_tables /
+ * rce_tables; the actions are 0..11 = U, U', F, F', R, R', D, D', B, B', L, L'.  All lengths are in quarter turns.
+ *   generators  phase 1: the 12 actions, cost 1 each.  Phase 2, in this order (the chain's stage 2): U, U', F2, R2, D, D', B2, L2 with
+ *               costs 1, 1, 2, 2, 1, 1, 2, 2; a half turn is the clockwise action twice.
+ *   tables      table[i] = the least cost to the goal under the phase's generators, 0xFF = not reached.
+ *                 0 twist-slice   index = sum_{q<7} co[q] * 3^q + 2187 * C, C = the rank among the 495 4-subsets of {0..11} of the slots
+ *                                 that hold pieces 8..11; N = 1 082 565; domain: every cube; goal: twist 0, C = 494.
+ *                 1 flip-slice    index = sum_{q<11} eo[q] * 2^q + 2048 * C; N = 1 013 760; every cube; goal: flip 0, C = 494.
+ *                 2 corner-slice  index = lehmer(cp) * 24 + s, s = lehmer(ep[8..11] - 8); N = 967 680; domain G1 (all co and eo 0, pieces
+ *                                 8..11 in slots 8..11); goal 0.
+ *                 3 edge-slice    index = lehmer(ep[0..7]) * 24 + s; N = 967 680; domain G1; goal 0.
+ *               Tables 0, 1 are phase 1's, tables 2, 3 phase 2's.  h = the maximum of the phase's two tables; a node is the phase's goal
+ *               iff both read 0.  Every table address passes the one guard (idx < N ? table[idx] : 0xFF); the host checks bytes >= N.
+ *   level       tp_build_level on tables 0, 1 is rct_build_level's rule.  On tables 2, 3 it is WEIGHTED: an entry still 0xFF becomes
+ *               depth + 1 iff a neighbour under a generator of cost w holds depth + 1 - w.  Each lane writes its own entry only; a
+ *               weighted table is complete when TWO levels in a row set nothing.
+ *   canonical   ida_canonical's rule on the trail of ACTIONS; a phase-2 generator is allowed iff its first action is.
+ *   search      the ida_* state machine: a pass generates one child or goes back one level; children in generator order;
+ *               f = g + cost + h(child); f > bound: next = min(next, f), the child is dropped; an exhausted iteration moves bound to
+ *               next (next = 2^31 - 1), or ends EXHAUSTED when next > the limit; a child whose h reads 0xFF ends ILLEGAL.  Frames are
+ *               caller-owned; the only loop is bounded by max_steps; the frame after k passes depends on the inputs alone, not on how
+ *               the calls cut the k.  A cube or column with a nonzero status is not touched again.
+ *   phase 1     one lane per cube c < n, floor 0, first bound h(root), limit[c] counts as min(limit[c], max_depth, 32).  It collects up
+ *               to K = candidates per cube: a goal child with f <= bound is never entered; it is EMITTED iff g + 1 == bound and its
+ *               last action is not a U or D turn (0, 1, 6, 7).  Emission writes, for slot j = found[c], column j * stride + c
+ *               (candidate-major; stride % 16 == 0, stride >= max(n, 16)): the trail with the last action into rows 0..g of path, g + 1
+ *               into cand_length, the 20 cubie rows of the G1 cube reached into cand_cubies ([tiles][20][cand_pitch] over
+ *               K * stride columns); then found[c] advances, and found[c] == K ends the cube FULL.  A root that is in G1 is emitted at
+ *               init with length 0 and searched all the same (bound 0).  Candidates come out by length and, within a length, in
+ *               depth-first order, each once.  depth = the number of actions on the trail; trail nibble i = action i.
+ *   phase 2     one lane per column c < n (n = K * stride after phase 1).  The root is the column's cubie rows: not in G1 gives
+ *               OUTSIDE.  floor[c] in 0..max_depth is the length of the prefix in rows 0..floor-1 of path column c; only its last
+ *               two actions are read (a byte >= 12 there: BAD_FRAME).  g starts at floor, and limit[c] counts the TOTAL length, as
+ *               min(limit[c], max_depth, floor + 32).  First bound floor + h(root); a bound above the limit is EXHAUSTED at init with
+ *               next = that bound -- tested BEFORE the goal, so a column with limit -1 is skipped whatever it holds; otherwise a root
+ *               that is the goal is SOLVED with length floor.  The first goal entered ends the column SOLVED: depth = the total length,
+ *               rows floor..depth-1 of path receive the actions (a half turn twice); no other row is written.  depth = g, the total
+ *               length at the current node; trail nibble i = generator i (0..7) of the phase-2 part (at most 32); cursor 0..8.
+ *   frame       path uint8 [max_depth][path_pitch], max_depth <= 48, path_pitch % 16 == 0 (phase 1: >= K * stride; phase 2: >= n), the
+ *               caller prefills 12; trail uint64 [n][2]; cursor uint8; depth, bound, next int32; nodes uint64 (children generated);
+ *               found int32 (phase 1); status uint8, 0 = running, else the bits below.  The root cubies are never written. */
+#define TP_SOLVED 1u      /* phase 2: the column is solved */
+#define TP_FULL 1u        /* phase 1: K candidates were emitted */
+#define TP_EXHAUSTED 2u
+#define TP_ILLEGAL 4u     /* a cubie byte >= 24, a piece twice, or a table read 0xFF */
+#define TP_BAD_FRAME 8u   /* floor, depth, cursor or found out of range, bound above the limit, a prefix or trail entry out of range */
+#define TP_OUTSIDE 16u    /* phase 2: the root is not in G1 */
+/* Conventions as in the ida_* section: caller-owned device memory, stream-ordered, nothing allocated, nothing synchronises; RC_EINVAL
+ * before any launch with nothing written (rc_last_error names the operand) for a NULL or misaligned pointer, a negative size, a table
+ * smaller than its N, which outside 0..3, candidates outside 1..4096, a bad stride or pitch, max_depth outside 1..48, max_steps
+ * outside 1..tp_max_steps(); pad columns keep their bytes; n == 0 succeeds without a launch; every pointer needs 16-byte alignment
+ * and no more.  table_a, table_b: tables 0, 1 for phase 1 and 2, 3 for phase 2.
+ *
+ * Host only, no device: N of table `which` (-1 for a bad one); the generators of phase 1 | 2, gens [12][2] = the one or two actions of
+ * each (0xFF: none, also in the rows from *count on) and cost [12] (0 from *count on), any pointer may be NULL; the largest max_steps
+ * a search call takes (one launch at it at 2^20 lanes stays near a second). */
+int64_t tp_table_bytes(int which);
+int tp_generators(int phase, uint8_t *gens, uint8_t *cost, int *count);
+int64_t tp_max_steps(void);
+/* Breadth-first build, one launch per level, as rct_build_*: tp_build_begin: every entry 0xFF, the goal 0 (one fill kernel);
+ * tp_build_level: the level rule above; *count (one device uint32, 16-byte aligned, zeroed by the call) receives how many entries
+ * were set to depth + 1.  depth in 0..253. */
+int tp_build_begin(uint8_t *table, int64_t bytes, int which, void *stream);
+int tp_build_level(uint8_t *table, int64_t bytes, int which, int depth, uint32_t *count, void *stream);
+/* index[c] (uint32) = table which's index of the cubie rows ([tiles][20][cubie_pitch]) of cube c; 0xFFFFFFFF for an illegal row set
+ * (a byte >= 24, a piece twice) and for a cube outside the table's domain. */
+int tp_index(const uint8_t *cubies, int64_t n, int64_t cubie_pitch, int which, uint32_t *index, void *stream);
+/* Phase 1: the frame's first contents (legality, first bound, a root in G1 emitted), and at most max_steps passes per running cube;
+ * the cubes still running are added to *running (one device uint32, 16-byte aligned, zeroed by the call). */
+int tp_phase1_init(const uint8_t *cubies, int64_t n, int64_t cubie_pitch, const uint8_t *table_a, int64_t bytes_a, const uint8_t *table_b,
+                   int64_t bytes_b, const int32_t *limit, int candidates, int64_t stride, uint8_t *path, int max_depth, int64_t path_pitch,
+                   int32_t *cand_length, uint8_t *cand_cubies, int64_t cand_pitch, uint64_t *trail, uint8_t *cursor, int32_t *depth,
+                   int32_t *bound, int32_t *next, uint64_t *nodes, int32_t *found, uint8_t *status, void *stream);
+int tp_phase1_search(const uint8_t *cubies, int64_t n, int64_t cubie_pitch, const uint8_t *table_a, int64_t bytes_a, const uint8_t *table_b,
+                     int64_t bytes_b, const int32_t *limit, int candidates, int64_t stride, uint8_t *path, int max_depth, int64_t path_pitch,
+                     int32_t *cand_length, uint8_t *cand_cubies, int64_t cand_pitch, uint64_t *trail, uint8_t *cursor, int32_t *depth,
+                     int32_t *bound, int32_t *next, uint64_t *nodes, int32_t *found, uint8_t *status, int64_t max_steps, uint32_t *running,
+                     void *stream);
+/* Phase 2, likewise, over n columns; floor may be NULL (= 0). */
+int tp_phase2_init(const uint8_t *cubies, int64_t n, int64_t cubie_pitch, const uint8_t *table_a, int64_t bytes_a, const uint8_t *table_b,
+                   int64_t bytes_b, uint8_t *path, int max_depth, int64_t path_pitch, const int32_t *floor, const int32_t *limit,
+                   uint64_t *trail, uint8_t *cursor, int32_t *depth, int32_t *bound, int32_t *next, uint64_t *nodes, uint8_t *status,
+                   void *stream);
+int tp_phase2_search(const uint8_t *cubies, int64_t n, int64_t cubie_pitch, const uint8_t *table_a, int64_t bytes_a, const uint8_t *table_b,
+                     int64_t bytes_b, uint8_t *path, int max_depth, int64_t path_pitch, const int32_t *floor, const int32_t *limit,
+                     uint64_t *trail, uint8_t *cursor, int32_t *depth, int32_t *bound, int32_t *next, uint64_t *nodes, uint8_t *status,
+                     int64_t max_steps, uint32_t *running, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

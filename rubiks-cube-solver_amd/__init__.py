@@ -14,6 +14,8 @@ Drop-in surface for the env path of SUNGBEOMCHOI/Rubiks-Cube-Solver:
   ChainTables         the four coset-distance tables of Thistlethwaite's subgroup chain (pattern.py), and chain_solve, the descent through
   chain_solve         them (search.py): a solution of ANY legal 3x3x3 in at most 87 quarter turns, no net, no search
   ida_search          Korf's IDA* under those pattern databases (search.py): the OPTIMAL solution of a 3x3x3, no node pool
+  TwoPhaseTables      the four coset tables of Kociemba's two-phase algorithm (pattern.py), and two_phase_solve (search.py): a SHORT
+  two_phase_solve     solution of ANY legal 3x3x3 -- never longer than chain_solve's -- by two table-guided depth-first searches
   get_cubies, RCC_*   the cube as pieces: (piece, orientation) bytes, the legality status bits, perfect indices (ops.cubies / from_cubies)
   py333               the same operators under the reference's names, one cube per call
   py222               the six names cube_env.py:8 imports from the file the reference does not ship (2x2x2, one cube per call)
@@ -24,7 +26,7 @@ from .tables import (ACTION_NAMES, RCC_BAD_COLOUR, RCC_BAD_FIXED, RCC_BAD_PIECE,
 
 __all__ = ["get_env_config", "get_tables", "get_cubies", "ACTION_NAMES", "RCC_BAD_COLOUR", "RCC_BAD_FIXED", "RCC_BAD_PIECE", "RCC_DUP_PIECE",
            "RCC_TWIST", "RCC_FLIP", "RCC_PARITY", "RCC_NAMES", "ops", "make_env", "CubeEnv", "VecCubeEnv", "TensorReplayBuffer", "CodeNet", "CornerTable", "EdgeTable",
-           "MaxTable", "ChainTables", "chain_solve", "ida_search"]
+           "MaxTable", "ChainTables", "chain_solve", "ida_search", "TwoPhaseTables", "two_phase_solve"]
 
 
 def __getattr__(name):  # torch-dependent parts load lazily
@@ -38,9 +40,9 @@ def __getattr__(name):  # torch-dependent parts load lazily
         return importlib.import_module(f"{__name__}.replay").TensorReplayBuffer
     if name == "CodeNet":
         return importlib.import_module(f"{__name__}.codenet").CodeNet
-    if name in ("CornerTable", "EdgeTable", "MaxTable", "ChainTables"):
+    if name in ("CornerTable", "EdgeTable", "MaxTable", "ChainTables", "TwoPhaseTables"):
         return getattr(importlib.import_module(f"{__name__}.pattern"), name)
-    if name in ("chain_solve", "ida_search"):
+    if name in ("chain_solve", "ida_search", "two_phase_solve"):
         return getattr(importlib.import_module(f"{__name__}.search"), name)
     if name in ("CubeEnv", "make_env"):
         return getattr(importlib.import_module(f"{__name__}.cube_env"), name)

@@ -463,6 +463,83 @@ __global__ void __launch_bounds__(256) k_chain_descend(ChainDescendArgs a) {
     a.status[b] = (uint8_t)status;
 }
 
+// ---- the two-phase coset spaces (include/rubikhip.h "Two-phase", the tp_* entry points of rc_ida.h): tables 0, 1 over every cube
+// under the 12 actions, tables 2, 3 over G1 = stage 2's domain under stage 2's generators, a half turn costing 2
+constexpr uint32_t kTpN[4] = {2187u * 495u, 2048u * 495u, 40320u * 24u, 40320u * 24u};
+
+// bit q = edge slot q holds one of the pieces 8..11
+__device__ __forceinline__ uint32_t chain_slice_mask(uint64_t ep) {
+    uint32_t slice = 0;
+    sfor<12>([&](auto qc) {
+        constexpr int q = decltype(qc)::value;
+        slice |= ((uint32_t)(ep >> (4 * q + 3)) & 1u) << q;
+    });
+    return slice;
+}
+
+template <int W>
+__device__ __forceinline__ bool tp_domain(const ChainCube &c) {
+    return W < 2 || chain_domain<2>(c);
+}
+
+template <int W>
+__device__ __forceinline__ uint32_t tp_index(const ChainCube &c) {
+    if constexpr (W == 0) {
+        return chain_index<1>(c, nullptr);                                    // twist + 2187 * C: stage 1's, whatever eo is
+    } else if constexpr (W == 1) {
+        return (c.eo & 0x7FFu) + 2048u * chain_subset_rank<12>(chain_slice_mask(c.ep));
+    } else if constexpr (W == 2) {
+        return chain_lehmer<8>(c.cp) * 24u + chain_lehmer<4>((uint32_t)(c.ep >> 32) & 0x3333u);
+    } else {
+        return chain_lehmer<8>((uint32_t)c.ep) * 24u + chain_lehmer<4>((uint32_t)(c.ep >> 32) & 0x3333u);
+    }
+}
+
+// a cube of table W's domain with index idx < N: what the index does not say is home (no neighbour's index reads it)
+template <int W>
+__device__ __forceinline__ ChainCube tp_unrank(uint32_t idx) {
+    ChainCube c{kChainCornersHome, 0u, kChainEdgesHome, 0u};
+    if constexpr (W == 0) {
+        chain_unrank<1>(idx, nullptr, c);
+    } else if constexpr (W == 1) {
+        const uint32_t flip = idx % 2048u, slice = chain_subset_unrank<12>(idx / 2048u);
+        c.eo = flip | (((uint32_t)__popc(flip) & 1u) << 11);
+        c.ep = chain_place(slice, 0xBA98ull) | chain_place(~slice & 0xFFFu, 0x76543210ull);
+    } else {
+        const uint64_t low = chain_unlehmer<8>(idx / 24u, kChainCornersHome);
+        if constexpr (W == 2) c.cp = (uint32_t)low;
+        c.ep = (chain_unlehmer<4>(idx % 24u, 0xBA98ull) << 32) | (W == 3 ? low : (uint64_t)kChainCornersHome);
+    }
+    return c;
+}
+
+template <int W>
+struct TpLevels {
+    static constexpr int kStage = W < 2 ? 0 : 2, kNeighbours = Cube3::chain_ngen[kStage];
+    __host__ __device__ static constexpr uint32_t n() { return kTpN[W]; }
+    template <int G>
+    __host__ __device__ static constexpr uint32_t cost() { return 1u + (uint32_t)(Cube3::chain_gen[kStage][G] >> 4); }
+    __device__ void block_begin() const {}
+    __device__ ChainCube unrank(uint32_t i) const { return tp_unrank<W>(i); }
+    template <int G>
+    __device__ uint32_t neighbour(const ChainCube &c) const { return tp_index<W>(chain_move<kStage, G>(c)); }
+};
+
+__global__ void __launch_bounds__(256) k_tp_fill(uint8_t *table, uint32_t n, uint32_t goal) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i < n) table[i] = i == goal ? 0u : 0xFFu;
+}
+
+template <int W>
+__global__ void __launch_bounds__(256) k_tp_index(const uint8_t *cubies, int64_t n, int64_t pitch, int sh, uint32_t *index) {
+    const int64_t b = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (b >= n) return;
+    ChainCube c;
+    const bool ok = chain_load(cubies + cubie_off(b, pitch, sh, Cube3::SLOTS), pitch, c) && tp_domain<W>(c);
+    const uint32_t idx = tp_index<W>(c);
+    index[b] = ok && idx < kTpN[W] ? idx : 0xffffffffu;
+}
+
 template <class F>
 int by_stage(int stage, F &&f) {
     switch (stage) {

@@ -43,6 +43,27 @@ __global__ void __launch_bounds__(256) k_table_level(uint8_t *table, Space s, ui
     if ((threadIdx.x & 63) == 0 && bal) atomicAdd(count, (uint32_t)__popcll(bal));
 }
 
+// The WEIGHTED level (rc_chain.h TpLevels, the two-phase tables whose half turns cost 2): Space::cost<M>() is what neighbour M costs,
+// and an entry that is still 0xFF becomes depth + 1 iff a neighbour of cost w holds depth + 1 - w.  depth + 1 - w wraps above 0xFF
+// when w > depth + 1, which no entry holds.  Pull and level-synchronous as above: a neighbour being written meanwhile reads 0xFF or
+// depth + 1, and depth + 1 - w is neither.
+template <class Space>
+__global__ void __launch_bounds__(256) k_table_level_weighted(uint8_t *table, Space s, uint32_t depth, uint32_t *count) {
+    s.block_begin();
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x, n = s.n();
+    bool set = false;
+    if (table_at(table, i, n) == 0xFFu && i < n) {
+        const auto c = s.unrank(i);
+        rc::sfor<Space::kNeighbours>([&](auto mc) {
+            constexpr int M = decltype(mc)::value;
+            if (!set) set = table_at(table, s.template neighbour<M>(c), n) == depth + 1u - Space::template cost<M>();
+        });
+        if (set) table[i] = (uint8_t)(depth + 1u);                        // the lane's own entry
+    }
+    const unsigned long long bal = __ballot(set);
+    if ((threadIdx.x & 63) == 0 && bal) atomicAdd(count, (uint32_t)__popcll(bal));
+}
+
 // a table operand: present, 16-byte aligned, and large enough for every index below n; `sizer`: the call that says how large
 int table_arg(const char *fn, const void *table, int64_t bytes, uint32_t n, const char *sizer) {
     if (!table || !aligned16(table)) return fail(kEinval, "%s: table is NULL or not 16-byte aligned", fn);
@@ -50,14 +71,18 @@ int table_arg(const char *fn, const void *table, int64_t bytes, uint32_t n, cons
     return 0;
 }
 
-// *_build_level after the caller's table_arg: *count = 0, then one level over s; `ehip`: the library's code for a failed HIP call
-template <class Space>
+// *_build_level after the caller's table_arg: *count = 0, then one level over s; `ehip`: the library's code for a failed HIP call;
+// WEIGHTED: the level kernel that asks the space for each neighbour's cost
+template <bool WEIGHTED = false, class Space>
 int table_build_level(const char *fn, uint8_t *table, Space s, int depth, uint32_t *count, hipStream_t st, int ehip) {
     if (depth < 0 || depth >= 254) return fail(kEinval, "%s: depth must be in 0..253", fn);
     if (!count || !aligned16(count)) return fail(kEinval, "%s: count is NULL or not 16-byte aligned", fn);
     hipLaunchKernelGGL(k_zero32, dim3(1), dim3(1), 0, st, count);
     RC_HIP(ehip, hipGetLastError());
-    hipLaunchKernelGGL(k_table_level<Space>, dim3((s.n() + 255u) / 256u), dim3(256), 0, st, table, s, (uint32_t)depth, count);
+    if constexpr (WEIGHTED)
+        hipLaunchKernelGGL(k_table_level_weighted<Space>, dim3((s.n() + 255u) / 256u), dim3(256), 0, st, table, s, (uint32_t)depth, count);
+    else
+        hipLaunchKernelGGL(k_table_level<Space>, dim3((s.n() + 255u) / 256u), dim3(256), 0, st, table, s, (uint32_t)depth, count);
     RC_HIP(ehip, hipGetLastError());
     return 0;
 }

@@ -12,7 +12,8 @@ classical admissible lower bound: h <= true distance, with the distance's parity
 
 The 3x3x3's corner table sees 8 of 20 cubies.  EdgeTable (include/rubikhip.h "Edge pattern databases", DESIGN.md "Edge pattern
 databases") is its companion over up to 7 tracked edge pieces, and MaxTable(corner, *edge_tables) the maximum of several tables --
-admissible and consistent like its members, and accepted by front="table" wherever a CornerTable is.
+admissible and consistent like its members, and accepted by front="table" wherever a CornerTable is.  ChainTables and TwoPhaseTables
+are coset-distance tables: distances to a subgroup, not to the solved cube (include/rubikhip.h "Subgroup chain", "Two-phase").
 """
 from __future__ import annotations
 
@@ -405,3 +406,101 @@ class ChainTables:
         if bad is None and int(flag):
             raise IndexError(f"stage {stage}: an index is out of range 0..{self.tables[stage].numel() - 1} or names no cube")
         return out
+
+
+class TwoPhaseTables:
+    """The four coset-distance tables of Kociemba's two-phase algorithm (include/rubikhip.h "Two-phase", DESIGN.md "Two-phase"):
+    0 twist-slice and 1 flip-slice over every cube under the 12 actions (phase 1), 2 corner-slice and 3 edge-slice over
+    G1 = <U,D,F2,R2,B2,L2> under U, U', F2, R2, D, D', B2, L2 with a half turn costing 2 (phase 2).  3x3x3 only, 4.0 MB in all;
+    search.two_phase_solve searches under them.
+
+        tp = TwoPhaseTables.build("cuda")             # breadth-first, one launch per level
+        tp.levels[2], tp.depth[2]                     # entries per distance of the corner-slice table, its largest distance
+        tp.distance(0, env)                           # uint8 [N]: quarter turns to twist 0 and the slice edges in the slice
+        two_phase_solve(tp, chain, env)["length"]
+
+    tables: four uint8 device tensors [N(which)]; levels / depth: per table (None for wrapped tensors)."""
+    cube_size = 3
+
+    def __init__(self, tables, levels=None, cube_size=3):
+        """Wrap tables built earlier.  ValueError for tensors that cannot be them: a wrong count, size, dtype or device -- found
+        before the device is touched."""
+        from . import _twophase_lib
+        if cube_size != 3:
+            raise ValueError(f"the two-phase tables exist for the 3x3x3 only, got cube_size {cube_size!r}")
+        tables = tuple(tables)
+        if len(tables) != _twophase_lib.TABLES:
+            raise ValueError(f"two phases have {_twophase_lib.TABLES} tables, got {len(tables)}")
+        for w, t in enumerate(tables):
+            _check_table(t, _twophase_lib.table_bytes(w), f"table {w}", "the tables", "every table")
+            if t.device != tables[0].device:
+                raise ValueError(f"the two-phase tables must live on one device, got {[str(x.device) for x in tables]}")
+        self.tables, self.device = tables, tables[0].device
+        self.levels = None if levels is None else tuple(tuple(int(c) for c in lv) for lv in levels)
+
+    @classmethod
+    def build(cls, device="cuda", cube_size=3):
+        """Breadth-first over each table's index space: tp_build_begin, then one tp_build_level per distance (the count is read back
+        once per level) until a level sets nothing -- two levels in a row for the weighted tables 2 and 3."""
+        from . import _twophase_lib
+        if cube_size != 3:
+            raise ValueError(f"the two-phase tables exist for the 3x3x3 only, got cube_size {cube_size!r}")
+        dev = _device(device)
+        _lib.init(dev)
+        L = _twophase_lib.twophase_lib()
+        count = torch.zeros(4, dtype=torch.int32, device=dev)  # one uint32, 16-byte aligned
+        tables, levels = [], []
+        for which in range(_twophase_lib.TABLES):
+            n = _twophase_lib.table_bytes(which)
+            t = torch.empty(n, dtype=torch.uint8, device=dev)
+            _lib.check(L.tp_build_begin(ptr(t), n, which, stream_ptr(dev)))
+            lv, empty = [1], 0
+            for depth in range(MAX_LEVELS + 2):
+                _lib.check(L.tp_build_level(ptr(t), n, which, depth, ptr(count), stream_ptr(dev)))
+                lv.append(int(count[0]))
+                empty = empty + 1 if lv[-1] == 0 else 0
+                if empty == (2 if which >= 2 else 1):
+                    break
+            else:
+                raise RuntimeError(f"two-phase table {which} has more than {MAX_LEVELS} levels")
+            tables.append(t)
+            levels.append(lv[:len(lv) - empty])
+        return cls(tables, levels)
+
+    @property
+    def depth(self):
+        """The largest distance of each table (needs levels: built tables)."""
+        return None if self.levels is None else tuple(len(lv) - 1 for lv in self.levels)
+
+    def _cubie_arg(self, cubes, n, pitch, what):
+        """(cubie buffer, n, pitch) of a VecCubeEnv (one rcc_cubies launch) or of a tiled cubie buffer [tiles, 20, pitch] with n cubes."""
+        if hasattr(cubes, "stickers"):
+            if cubes.cube_size != 3:
+                raise ValueError(f"the tables are a 3x3x3's, the cubes are {cubes.cube_size}x{cubes.cube_size}x{cubes.cube_size}")
+            if cubes.stickers.device != self.device:
+                raise ValueError(f"the tables are on {self.device}, the cubes on {cubes.stickers.device}")
+            n, pitch = cubes.num_envs, None
+            cubes = ops.cubies(cubes.stickers, n, 3, status=False)["cubies"]
+        if n is None:
+            raise ValueError(f"{what}(which, cubies, n): the number of cubes is required for a cubie buffer")
+        if cubes.device != self.device:
+            raise ValueError(f"the tables are on {self.device}, the cubes on {cubes.device}")
+        return cubes, n, ops._state_arg(cubes, 20, n, pitch, f"{what} cubies")
+
+    def index(self, which, cubes, n=None, pitch=None):
+        """int64 [N]: table which's index of every cube (one tp_index launch), -1 for an illegal row set and for a cube outside the
+        table's domain.  cubes: a VecCubeEnv, or a tiled cubie buffer [tiles, 20, pitch] with n cubes."""
+        from . import _twophase_lib
+        which = _twophase_lib.check_which(which)
+        cubes, n, p = self._cubie_arg(cubes, n, pitch, "index")
+        out = torch.empty(_lib.pitch_for(max(n, 1) * 4, 16) // 4, dtype=torch.int32, device=self.device)[:n]
+        _lib.init(self.device)
+        _lib.check(_twophase_lib.twophase_lib().tp_index(ptr(cubes), n, p, which, ptr(out), stream_ptr(self.device)))
+        return out.to(torch.int64)                             # all-ones, the uint32 of an int32 tensor, is -1
+
+    def distance(self, which, cubes, n=None, pitch=None):
+        """uint8 [N]: table[index], ILLEGAL = 0xFF where index() is -1."""
+        idx = self.index(which, cubes, n, pitch)
+        t = self.tables[which]
+        d = t[idx.clamp(0, t.numel() - 1)]
+        return torch.where(idx < 0, torch.full_like(d, ILLEGAL), d)

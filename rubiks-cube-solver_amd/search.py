@@ -745,3 +745,210 @@ def ida_search(table, env, *, limit=20, max_steps=1 << 22, steps_per_call=None, 
     rows = max(1, int(length.max())) if n else 1
     acts = torch.where(solved[None, :], path[:rows], torch.full_like(path[:rows], _ida_lib.NOOP))
     return dict(solved=solved, length=length, actions=acts.contiguous(), nodes=nodes, bound=bound, status=status)
+
+
+class TwoPhase1Frame:
+    """The caller-owned frame of phase 1 over n cubes (include/rubikhip.h "Two-phase") and its two launching calls.  cubies: a tiled
+    cubie buffer of n cubes with pitch p_c; candidate (j, c) lives in column j * stride + c of path, cand_length and cand_cubies."""
+
+    def __init__(self, tables, cubies, n, p_c, candidates, limit, max_depth=None):
+        from . import _twophase_lib as T
+        dev = cubies.device
+        self.n, self.dev, self.K, self.L = n, dev, int(candidates), T.twophase_lib()
+        self.max_depth = T.MAX_DEPTH if max_depth is None else int(max_depth)
+        self.stride = stride = _lib.pitch_for(max(n, 1), 16)
+        self.cols = cols = self.K * stride
+        vec = lambda dtype: torch.zeros(stride, dtype=dtype, device=dev)
+        self.path = torch.full((self.max_depth, cols), T.NOOP, dtype=torch.uint8, device=dev)
+        self.cand_length = torch.zeros(cols, dtype=torch.int32, device=dev)
+        self.cand_cubies = torch.zeros((20, cols), dtype=torch.uint8, device=dev)
+        self.cand_cubies += torch.tensor([3 * q for q in range(8)] + [2 * q for q in range(12)], dtype=torch.uint8, device=dev)[:, None]
+        self.limit = vec(torch.int32)
+        self.limit[:n] = limit
+        self.trail = torch.zeros((stride, 2), dtype=torch.int64, device=dev)
+        self.cursor, self.status = vec(torch.uint8), vec(torch.uint8)
+        self.depth, self.bound, self.next, self.found = vec(torch.int32), vec(torch.int32), vec(torch.int32), vec(torch.int32)
+        self.nodes = vec(torch.int64)
+        self.running = torch.zeros(4, dtype=torch.int32, device=dev)       # one uint32, 16-byte aligned
+        a, b = tables.tables[0], tables.tables[1]
+        self._keep = (tables, cubies)
+        self._args = (ptr(cubies), n, p_c, ptr(a), a.numel(), ptr(b), b.numel(), ptr(self.limit), self.K, stride, ptr(self.path), self.max_depth,
+                      cols, ptr(self.cand_length), ptr(self.cand_cubies), cols, ptr(self.trail), ptr(self.cursor), ptr(self.depth),
+                      ptr(self.bound), ptr(self.next), ptr(self.nodes), ptr(self.found), ptr(self.status))
+
+    def init(self):
+        _lib.check(self.L.tp_phase1_init(*self._args, stream_ptr(self.dev)))
+
+    def search(self, steps):
+        _lib.check(self.L.tp_phase1_search(*self._args, int(steps), ptr(self.running), stream_ptr(self.dev)))
+
+    run = IdaFrame.run
+
+
+class TwoPhase2Frame:
+    """The caller-owned frame of phase 2 over n columns and its two launching calls.  cubies [20, pitch >= n]: the G1 roots; path
+    uint8 [max_depth, pitch]: the prefixes (rows below floor) and the room for the answers; floor, limit: int32 [>= n]."""
+
+    def __init__(self, tables, cubies, n, p_c, path, floor, limit):
+        from . import _twophase_lib as T
+        dev = cubies.device
+        self.n, self.dev, self.L, self.path, self.floor, self.limit = n, dev, T.twophase_lib(), path, floor, limit
+        pitch = _lib.pitch_for(max(n, 1), 16)
+        vec = lambda dtype: torch.zeros(pitch, dtype=dtype, device=dev)
+        self.trail = torch.zeros((pitch, 2), dtype=torch.int64, device=dev)
+        self.cursor, self.status = vec(torch.uint8), vec(torch.uint8)
+        self.depth, self.bound, self.next = vec(torch.int32), vec(torch.int32), vec(torch.int32)
+        self.nodes = vec(torch.int64)
+        self.running = torch.zeros(4, dtype=torch.int32, device=dev)
+        a, b = tables.tables[2], tables.tables[3]
+        self._keep = (tables, cubies)
+        self._args = (ptr(cubies), n, p_c, ptr(a), a.numel(), ptr(b), b.numel(), ptr(path), path.shape[0], path.shape[1],
+                      ptr(floor) if floor is not None else None, ptr(limit), ptr(self.trail), ptr(self.cursor), ptr(self.depth), ptr(self.bound),
+                      ptr(self.next), ptr(self.nodes), ptr(self.status))
+
+    def init(self):
+        _lib.check(self.L.tp_phase2_init(*self._args, stream_ptr(self.dev)))
+
+    def search(self, steps):
+        _lib.check(self.L.tp_phase2_search(*self._args, int(steps), ptr(self.running), stream_ptr(self.dev)))
+
+    run = IdaFrame.run
+
+
+TWO_PHASE_DESCENT_ROWS = 58        # quarter turns of the chain's stages 2 and 3 at the most: 2 * 14 + 2 * 15
+
+
+def two_phase_select(K, chain_length, cand_length, found, descent, status2, depth2):
+    """Step 7 of two_phase_solve in torch indexing: per cube the candidate with the smallest total -- its phase-2 length where the
+    column is SOLVED, else its phase-1 length plus its descent; index K is chain_solve's answer; the FIRST minimum in index order wins.
+    cand_length, descent, status2, depth2: [K, N]; chain_length, found: [N].  -> (candidate int64 [N], total int32 [N], source uint8
+    [N]: 0 chain, 1 descent, 2 phase 2)."""
+    from . import _twophase_lib as T
+    dev = chain_length.device
+    big = torch.full((), T.INF, dtype=torch.int32, device=dev)
+    slot = torch.arange(K, device=dev)[:, None]
+    won = status2 == T.SOLVED
+    total = torch.where(won, depth2, cand_length + descent)
+    total = torch.where(slot < found[None, :], total, big)
+    total = torch.cat([total, chain_length[None, :].to(torch.int32)])          # [K + 1, N]
+    best = total.min(0).values
+    index = torch.arange(K + 1, device=dev)[:, None].expand_as(total)
+    cand = torch.where(total == best[None, :], index, torch.full_like(index, K + 1)).min(0).values
+    pick = won.gather(0, cand.clamp(max=K - 1)[None, :])[0]
+    source = torch.where(cand == K, 0, torch.where(pick, 2, 1)).to(torch.uint8)
+    return cand, best, source
+
+
+def two_phase_solve(tables, chain, env, *, candidates=64, phase1_limit=16, phase2_limit=20, max_steps=100000, steps_per_call=None):
+    """A SHORT solution of every cube of a 3x3x3 env by Kociemba's two-phase algorithm (include/rubikhip.h "Two-phase" has THE RULE,
+    DESIGN.md "Two-phase" the numbers).  tables: a pattern.TwoPhaseTables; chain: a pattern.ChainTables.  The env is left as it is.
+      1  rcc_cubies and legality; an illegal cube is not searched;
+      2  phase 1: up to `candidates` ways into G1 per cube, none longer than phase1_limit, within max_steps passes per cube;
+      3  the chain's stages 2 and 3 (rct_descend) finish EVERY candidate: a guaranteed completion;
+      4  chain_solve's own answer is candidate number `candidates`;
+      5  phase 2 looks, per candidate, for something strictly shorter than the cube's shortest guaranteed length G: its limit is
+         min(48, phase-1 length + phase2_limit, G - 1), within max_steps passes per candidate;
+      6  per cube the shortest of all wins, the first in candidate order among equals.
+    steps_per_call: passes per launch (default and cap: tp_max_steps()); one uint32 is read back per launch.
+
+    Returns dict(solved bool [N], length int32 [N] (-1: not solved), actions uint8 [L, N] (padded with the no-op 12; L = max(1,
+    length.max())), source uint8 [N] (0 chain, 1 phase 1 + descent, 2 phase 1 + phase 2), candidate int64 [N] (the winner's slot,
+    `candidates` for the chain, -1 unsolved), phase1_length int32 [N] (-1 for the chain), chain_length int32 [N], nodes int64 [2, N]
+    (children generated by phase 1, and by phase 2 over the cube's candidates), status uint8 [N] (phase 1's: 0 the budget ran out,
+    TP_FULL 1, TP_EXHAUSTED 2: every way within phase1_limit was seen, TP_ILLEGAL 4))."""
+    return two_phase_frames(tables, chain, env, candidates=candidates, phase1_limit=phase1_limit, phase2_limit=phase2_limit, max_steps=max_steps,
+                            steps_per_call=steps_per_call)[0]
+
+
+def two_phase_frames(tables, chain, env, *, candidates=64, phase1_limit=16, phase2_limit=20, max_steps=100000, steps_per_call=None):
+    """two_phase_solve, and what it chose from: (its result, dict(one: the TwoPhase1Frame, two: the TwoPhase2Frame, descent int32
+    [K, N]: every candidate's guaranteed completion beyond its phase-1 length, limit2 int32 [K, N], chain: chain_solve's result))."""
+    from . import _chain_lib, _twophase_lib as T
+    from .pattern import ChainTables, TwoPhaseTables
+    if not isinstance(tables, TwoPhaseTables):
+        raise ValueError(f"two_phase_solve(tables, chain, env): tables is a pattern.TwoPhaseTables, got {type(tables).__name__}")
+    if not isinstance(chain, ChainTables):
+        raise ValueError(f"two_phase_solve(tables, chain, env): chain is a pattern.ChainTables, got {type(chain).__name__}")
+    if not hasattr(env, "stickers") or env.cube_size != 3:
+        raise ValueError(f"two_phase_solve needs a 3x3x3 VecCubeEnv, got {'a ' + str(env.cube_size) + 'x' + str(env.cube_size) + 'x' + str(env.cube_size) + ' one' if hasattr(env, 'cube_size') else type(env).__name__}")
+    ints = lambda v: isinstance(v, int) and not isinstance(v, bool)
+    if not ints(candidates) or not 1 <= candidates <= T.MAX_CANDIDATES:
+        raise ValueError(f"candidates must be an integer in 1..{T.MAX_CANDIDATES}, got {candidates!r}")
+    if not ints(phase1_limit) or not 0 <= phase1_limit <= T.MAX_TRAIL:
+        raise ValueError(f"phase1_limit must be an integer in 0..{T.MAX_TRAIL}, got {phase1_limit!r}")
+    if not ints(phase2_limit) or not 0 <= phase2_limit <= T.MAX_TRAIL:
+        raise ValueError(f"phase2_limit must be an integer in 0..{T.MAX_TRAIL}, got {phase2_limit!r}")
+    if not ints(max_steps) or max_steps < 1:
+        raise ValueError(f"max_steps must be a positive integer, got {max_steps!r}")
+    cap = T.max_steps()
+    if steps_per_call is None:
+        steps_per_call = cap
+    if not ints(steps_per_call) or not 1 <= steps_per_call <= cap:
+        raise ValueError(f"steps_per_call must be an integer in 1..tp_max_steps() = {cap}, got {steps_per_call!r}")
+    if chain.device != tables.device:
+        raise ValueError(f"the two-phase tables are on {tables.device}, the chain's on {chain.device}")
+    if env.stickers.device != tables.device:
+        raise ValueError(f"the tables are on {tables.device}, the cubes on {env.stickers.device}")
+    n, dev, K = env.num_envs, tables.device, candidates
+    _lib.init(dev)
+    cub = ops.alloc_code(n, 3, dev, env.stickers.shape[-1])
+    legal = torch.empty(_lib.pitch_for(n, 16), dtype=torch.uint8, device=dev)
+    ops.cubies(env.stickers, n, 3, cubies=cub, status=legal)
+    p_c = ops._state_arg(cub, 20, n, None, "two_phase_solve cubies")
+    bad = legal[:n] != 0
+
+    one = TwoPhase1Frame(tables, cub, n, p_c, K, phase1_limit)
+    one.init()
+    one.status[:n] = torch.where(bad, torch.full_like(one.status[:n], T.ILLEGAL), one.status[:n])    # not a cube: not searched
+    one.found[:n] = torch.where(bad, torch.zeros_like(one.found[:n]), one.found[:n])
+    one.run(max_steps, steps_per_call)
+    stride, cols = one.stride, one.cols
+    found = one.found[:n]
+    emitted = (torch.arange(K, device=dev)[:, None] < one.found[None, :]).reshape(cols)
+
+    # the guaranteed completion of every candidate: the chain's stages 2 and 3 on a copy of the candidates' rows
+    walk = one.cand_cubies.clone()
+    d_act = torch.full((TWO_PHASE_DESCENT_ROWS, cols), T.NOOP, dtype=torch.uint8, device=dev)
+    d_len = emitted.to(torch.int32) - 1                                        # 0, and -1 for an empty slot: rct_descend refuses it
+    d_moves, d_status = torch.empty(cols, dtype=torch.uint8, device=dev), torch.empty((2, cols), dtype=torch.uint8, device=dev)
+    CL = _chain_lib.chain_lib()
+    for i, s in enumerate((2, 3)):
+        _lib.check(CL.rct_descend(ptr(walk), cols, cols, s, ptr(chain.tables[s]), chain.tables[s].numel(), ptr(d_act), TWO_PHASE_DESCENT_ROWS,
+                                  cols, ptr(d_len), ptr(d_moves), ptr(d_status[i]), stream_ptr(dev)))
+    walked = emitted & (d_status[0] == 0) & (d_status[1] == 0)
+    ch = chain_solve(chain, env)
+    chain_length = torch.where(ch["solved"], ch["length"], torch.full_like(ch["length"], T.INF))
+
+    len1 = one.cand_length.view(K, stride)[:, :n]
+    descent = torch.where(walked, d_len, torch.full_like(d_len, T.INF // 2)).view(K, stride)[:, :n]
+    slot = torch.arange(K, device=dev)[:, None]
+    sure = torch.where(slot < found[None, :], len1 + descent, torch.full_like(len1, T.INF))
+    G = torch.minimum(sure.min(0).values, chain_length.to(torch.int32))       # the cube's shortest guaranteed length
+    limit2 = torch.full((K, stride), -1, dtype=torch.int32, device=dev)
+    limit2[:, :n] = torch.where(slot < found[None, :], torch.minimum(len1 + phase2_limit, (G - 1)[None, :]).clamp(max=T.MAX_DEPTH),
+                                torch.full_like(len1, -1))
+    two = TwoPhase2Frame(tables, one.cand_cubies, cols, cols, one.path, one.cand_length, limit2.view(cols))
+    two.init()
+    two.run(max_steps, steps_per_call)
+
+    cand, total, source = two_phase_select(K, chain_length.to(torch.int32), len1, found, descent, two.status.view(K, stride)[:, :n],
+                                           two.depth.view(K, stride)[:, :n])
+    solved = ~bad & (total < T.INF // 2)
+    length = torch.where(solved, total, torch.full_like(total, -1))
+    rows = max(1, int(length.max())) if n else 1
+    col = cand.clamp(max=K - 1) * stride + torch.arange(n, device=dev)
+    p1 = torch.where(cand < K, one.cand_length[col], torch.full_like(total, -1))
+    r = torch.arange(rows, device=dev)[:, None]
+    head = one.path[:, col][:rows] if rows <= one.path.shape[0] else torch.cat(
+        [one.path[:, col], torch.full((rows - one.path.shape[0], n), T.NOOP, dtype=torch.uint8, device=dev)])
+    tail = d_act[:, col].gather(0, (r - p1[None, :]).clamp(0, TWO_PHASE_DESCENT_ROWS - 1))
+    acts = torch.where((source == 2)[None, :] | (r < p1[None, :]), head, tail)
+    ca = ch["actions"]
+    ca = ca[:rows] if ca.shape[0] >= rows else torch.cat([ca, torch.full((rows - ca.shape[0], n), T.NOOP, dtype=torch.uint8, device=dev)])
+    acts = torch.where((source == 0)[None, :], ca, acts)
+    acts = torch.where(solved[None, :] & (r < length[None, :]), acts, torch.full_like(acts, T.NOOP))
+    nodes = torch.stack([one.nodes[:n], two.nodes.view(K, stride)[:, :n].sum(0)])
+    res = dict(solved=solved, length=length, actions=acts.contiguous(), source=torch.where(solved, source, torch.zeros_like(source)),
+               candidate=torch.where(solved, cand, torch.full_like(cand, -1)), phase1_length=torch.where(solved, p1, torch.full_like(p1, -1)),
+               chain_length=ch["length"], nodes=nodes, status=one.status[:n].clone())
+    return res, dict(one=one, two=two, descent=descent, limit2=limit2[:, :n], chain=ch)

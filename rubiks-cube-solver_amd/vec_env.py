@@ -254,6 +254,13 @@ class VecCubeEnv:
         from .search import ida_search
         return ida_search(table, self, **kwargs)
 
+    def two_phase_solve(self, tables, chain, **kwargs):
+        """search.two_phase_solve(tables, chain, self, ...): a short solution of every cube by Kociemba's two phases under a
+        pattern.TwoPhaseTables, never longer than chain_solve's through the pattern.ChainTables `chain` (3x3x3 only); the env is left
+        as it is."""
+        from .search import two_phase_solve
+        return two_phase_solve(tables, chain, self, **kwargs)
+
     def from_cubies(self, cubies):
         """Set every cube from its cubie bytes: [N, SLOTS] rows (host or device) or a tiled cubie tensor as cubies() returns it.  The
         assembly need not be legal (legality() tells); a byte that names no (piece, orientation) raises ValueError and the env keeps
