@@ -589,7 +589,14 @@ int rct_descend(uint8_t *cubies, int64_t n, int64_t cubie_pitch, int stage, cons
  *   budget      ida_search advances every running cube by at most max_steps passes.  A pass generates one child (dropped, entered or
  *               the goal), or goes back one level (the inverse of the last move is applied; at the start node: the iteration ends as
  *               above).  The kernel's only loop is bounded by max_steps; no loop's trip count depends on what a table holds.
- *   invariance  the frame after k passes in all depends on the inputs alone, not on how the calls cut the k. */
+ *   invariance  the frame after k passes in all depends on the inputs alone, not on how the calls cut the k.
+ *   written     ida_search takes any frame with status 0, not only one ida_init or an earlier call left: a caller may store a frame and
+ *               put it back, or write one.  It reads floor, trail[0..depth), cursor, depth, bound, next and nodes, never path.  A frame
+ *               is refused with IDA_BAD_FRAME for floor outside 0..max_depth, depth < floor, depth > max_depth, cursor > 12,
+ *               bound > min(limit, max_depth), or a trail nibble >= 12 below depth.  The bit is OR-ed into status; every other field of
+ *               the frame and every row of path keep the bytes the caller wrote, and the cube is not counted in *running.  Nibbles from
+ *               depth on are stale and never looked at.  depth > bound is NOT refused (a caller may lower or raise bound between
+ *               calls): every child is dropped into next until the search is back below the bound. */
 #define IDA_SOLVED 1u
 #define IDA_EXHAUSTED 2u
 #define IDA_ILLEGAL 4u     /* a cubie byte >= 24, a piece twice, or a table read 0xFF */
@@ -664,7 +671,14 @@ int ida_search(const uint8_t *cubies, int64_t n, int64_t cubie_pitch, const uint
  *               length at the current node; trail nibble i = generator i (0..7) of the phase-2 part (at most 32); cursor 0..8.
  *   frame       path uint8 [max_depth][path_pitch], max_depth <= 48, path_pitch % 16 == 0 (phase 1: >= K * stride; phase 2: >= n), the
  *               caller prefills 12; trail uint64 [n][2]; cursor uint8; depth, bound, next int32; nodes uint64 (children generated);
- *               found int32 (phase 1); status uint8, 0 = running, else the bits below.  The root cubies are never written. */
+ *               found int32 (phase 1); status uint8, 0 = running, else the bits below.  The root cubies are never written.
+ *   written     the search calls take any frame with status 0, as ida_search does; a refused frame gets TP_BAD_FRAME OR-ed into status,
+ *               keeps every other byte of the frame, of path and of the candidate slots, and is not counted in *running.  Phase 1
+ *               refuses depth outside 0..31, depth > bound, cursor > 12, bound > min(limit, max_depth, 32), found outside 0..K-1, and a
+ *               trail nibble >= 12 below depth.  Phase 2 refuses a floor outside 0..max_depth or a byte >= 12 in the prefix's last two
+ *               rows, g < floor, g > max_depth, g > bound, cursor > 8, bound > min(limit, max_depth, floor + 32), and a trail that does
+ *               not spell g: the number of generators is not stored, they are read from nibble 0 on until their costs reach
+ *               g - floor; one >= 8 on the way, or costs that step over g, are refused.  A root outside G1 is OUTSIDE here too. */
 #define TP_SOLVED 1u      /* phase 2: the column is solved */
 #define TP_FULL 1u        /* phase 1: K candidates were emitted */
 #define TP_EXHAUSTED 2u

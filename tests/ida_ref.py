@@ -151,6 +151,7 @@ class Frame:
         self.nib = [0] * MAX_DEPTH                                     # the 32 nibbles of the trail; entries from `depth` on are stale
         self.cursor, self.depth, self.bound, self.next, self.nodes, self.status = 0, 0, 0, INF, 0, 0
         self.passes, self.mv = 0, movers()
+        self.written, self.deepest, self.word1 = set(), 0, False
         x = from_bytes(cub)
         if x is None:
             self.status |= ILLEGAL
@@ -165,6 +166,7 @@ class Frame:
             x = mv[m](x)
         self.x, self.depth = x, self.floor
         self.nib[:self.floor] = prefix[:self.floor]
+        self.deepest, self.word1 = self.depth, any(self.nib[16:])
         self.lim = min(limit, max_depth)
         h0 = h(x)
         if h0 == 0xFF:
@@ -176,10 +178,39 @@ class Frame:
         elif self.bound > self.lim:
             self.status, self.next = EXHAUSTED, self.bound
 
+    @classmethod
+    def resume(cls, cub, h, limit, max_depth, floor=0, trail=(), depth=0, bound=0, next=INF, cursor=0, nodes=0):
+        """A frame the CALLER wrote, as ida_search takes it (the header's "written frame" rule): trail = the nibbles from the root on,
+        prefix included (what lies from `depth` on is stale and kept).  A refused frame gets IDA_BAD_FRAME OR-ed into its status and
+        keeps every other field as written; depth > bound is NOT refused.  The node is the root moved along trail[0..depth)."""
+        f = cls.__new__(cls)
+        f.h, f.max_depth, f.floor, f.lim = h, max_depth, floor, min(limit, max_depth)
+        f.nib = (list(trail) + [0] * MAX_DEPTH)[:MAX_DEPTH]
+        f.cursor, f.depth, f.bound, f.next, f.nodes, f.status = cursor, depth, bound, next, nodes, 0
+        f.passes, f.mv = 0, movers()
+        f.written, f.deepest, f.word1 = set(), depth, any(f.nib[16:])
+        x = from_bytes(cub)
+        if x is None:
+            f.status |= ILLEGAL
+        if not 0 <= floor <= max_depth or depth < floor or depth > max_depth or cursor > A or bound > f.lim:
+            f.status |= BAD_FRAME
+        elif not f.status and any(m >= A for m in f.nib[:depth]):
+            f.status |= BAD_FRAME
+        if not f.status:
+            for m in f.nib[:depth]:
+                x = f.mv[m](x)
+            f.x = x
+        return f
+
+    def written_frame(self):
+        """the keyword arguments of resume() that rewrite this frame"""
+        return dict(floor=self.floor, trail=list(self.nib), depth=self.depth, bound=self.bound, next=self.next, cursor=self.cursor,
+                    nodes=self.nodes)
+
     def clone(self):
         """A frame of its own on the same heuristic (a deep copy would copy the tables)."""
         f = copy.copy(self)
-        f.nib = list(self.nib)
+        f.nib, f.written = list(self.nib), set(self.written)
         return f
 
     def step(self):
@@ -199,6 +230,9 @@ class Frame:
             else:
                 self.x, self.depth, self.cursor = y, g + 1, 0
                 t[g] = m
+                self.written.add(g)                                          # coverage: which nibbles a run writes, how deep it gets,
+                self.deepest = max(self.deepest, g + 1)                      # whether word 1 of the trail was ever nonzero
+                self.word1 = self.word1 or (g >= 16 and m != 0)
                 if y == HOME:
                     self.status = SOLVED
         elif g > self.floor:
@@ -237,6 +271,23 @@ class Frame:
 
 def solve(cub, h, limit=20, max_depth=None, **kw):
     return Frame(cub, h, limit, max(1, limit) if max_depth is None else max_depth).run(**kw)
+
+
+def canonical_walk(rng, length, p2=NOOP, p1=NOOP):
+    """A random canonical move sequence of `length` after ..., p2, p1 (uniform over the allowed moves at every step)."""
+    out = []
+    for _ in range(length):
+        m = int(rng.choice(ALLOWED[p2][p1]))
+        out.append(m)
+        p2, p1 = p1, m
+    return out
+
+
+def undo(x, moves):
+    """The cube that `moves` bring to x."""
+    for m in reversed(moves):
+        x = movers()[m ^ 1](x)
+    return x
 
 
 def replay_bytes(cub, moves):

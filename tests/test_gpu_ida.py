@@ -441,8 +441,184 @@ def test_every_argument_error_writes_nothing(tabs):
     raw.check("argument errors")
     assert raw.init(n=0) == 0 and raw.search(4, n=0) == 0                    # succeeds without a launch
     raw.check("n == 0")
-    assert raw.search(_ida.max_steps()) == 0                                 # the cap itself is taken (a frame of FILL: BAD_FRAME or skipped)
-    torch.cuda.synchronize()
+    assert raw.search(_ida.max_steps()) == 0                                 # the cap itself is taken; a frame of FILL has a nonzero status:
+    raw.running.expect(np.zeros(1, np.uint32))                               # it is skipped, byte for byte, and nothing is counted running
+    raw.check("a frame of fill bytes")
+
+
+# ------------------------------------------------------------------------------------- 5b. deep prefixes and written frames
+from tests import deep_cases as DC  # noqa: E402
+
+_DEEP = {}
+
+
+def deep_raw(table, layout, max_depth=32):
+    """The deep set of tests/deep_cases.py in guarded arenas: (cases, cubie rows, Raw, floor, limit)."""
+    cases = _DEEP.setdefault(max_depth, DC.ida_cases(max_depth))
+    rows = np.array([c.root for c in cases], np.uint8)
+    floor, limit = np.array([c.f for c in cases], np.int32), np.full(len(cases), 32, np.int32)
+    raw = Raw(table, rows, layout, max_depth, limit, np.array([c.column for c in cases], np.uint8).T, floor)
+    return cases, rows, raw, floor, limit
+
+
+def deep_frames(tabs, config, max_depth=32):
+    """The restated frames of the deep set at init, after 5 passes and at the end -- computed once per table and shared (clones)."""
+    key = (config, max_depth, "frames")
+    if key not in _DEEP:
+        cases, rows, raw, floor, limit = deep_raw(tabs[config][0], "tight", max_depth)
+        first = restated(rows, tabs[config][1], max_depth, limit, raw.path0, floor)
+        five = [f.clone().run(max_passes=5) for f in first]
+        last = [f.clone().run(max_nodes=10 ** 9) for f in five]
+        for c, f in zip(cases, last):
+            print(f"deep IDA* {c.name} under {config}: {f.passes} restated passes, status {f.status}")
+            assert f.passes <= DC.PASS_CAP and f.status == c.want, (c.name, f.passes, f.status)
+        _DEEP[key] = (first, five, last)
+    return [[f.clone() for f in fs] for fs in _DEEP[key]]
+
+
+@pytest.mark.parametrize("config,layout,max_depth", [("none", "tight", 32), ("none", "padded", 32), ("best", "tight", 32), ("best", "padded", 32),
+                                                     ("none", "tight", 20), ("best", "tight", 20)])
+def test_deep_prefixes_every_byte_of_every_operand(tabs, config, layout, max_depth):
+    """Prefixes of 13..32 moves with limit 32 (tests/deep_cases.py): the search runs in word 1 of the trail and up to row 31 of path.
+    After ida_init, after 5 passes and at the end every byte of every operand -- both trail words, every row of path: the prefix, the
+    solution, the prefill --, the pad columns and the guards are the restatement's.  No case is left out: each ends within PASS_CAP."""
+    _lib, _, _, _, _ = mods()
+    _lib.init(torch.device(DEV, torch.cuda.current_device()))
+    cases, rows, raw, floor, limit = deep_raw(tabs[config][0], layout, max_depth)
+    first, five, last = deep_frames(tabs, config, max_depth)
+    assert raw.init() == 0
+    raw.expect(first)
+    raw.check("ida_init")
+    assert raw.search(5) == 0
+    raw.expect(five, running=sum(f.status == 0 for f in five))
+    raw.check("five passes")
+    assert raw.search(1 << 14) == 0 and raw.search(1 << 14) == 0            # PASS_CAP < 2^15
+    raw.expect(last, running=0)
+    raw.check("to the end")
+    assert all(f.status == c.want for f, c in zip(last, cases))
+    if max_depth == 32:
+        assert any(f.status == R.SOLVED and f.depth == 32 for f in last) and sum(f.status == R.EXHAUSTED and f.next == 33 for f in last) == 2
+
+
+def test_deep_prefixes_do_not_depend_on_how_the_budget_is_cut(tabs):
+    """The deep set without a table in launches of 1, 7 and 12 288 passes, 12 288 in all: the same bytes everywhere, the restatement's."""
+    _lib, _, _, _, _ = mods()
+    _lib.init(torch.device(DEV, torch.cuda.current_device()))
+    _, _, last = deep_frames(tabs, "none")
+    total = 12288
+    assert max(f.passes for f in last) <= total
+    for per_call in (1, 7, total):
+        _, _, raw, _, _ = deep_raw(None, "tight")
+        assert raw.init() == 0
+        spent = 0
+        while spent < total:
+            k = min(per_call, total - spent)
+            assert raw.search(k) == 0
+            spent += k
+        raw.expect(last, running=0)
+        raw.check(f"launches of {per_call}")
+
+
+@pytest.mark.parametrize("p", (3, 700))
+def test_a_stored_deep_frame_resumes_to_the_same_end(tabs, p):
+    """The frames after p passes, copied byte for byte into fresh operands over a fresh path that holds the prefixes alone, continue to
+    the end of the uninterrupted run (the restatement's); floors 13..17 lie on both sides of nibble 16.  A cube solved before the copy
+    keeps its status and gets no rows: a cube with a status is not touched."""
+    _lib, _, _, _, _ = mods()
+    _lib.init(torch.device(DEV, torch.cuda.current_device()))
+    first, _, last = deep_frames(tabs, "none")
+    at_p = [f.run(max_passes=p) for f in first]
+    _, _, one, _, _ = deep_raw(None, "padded")
+    assert one.init() == 0 and one.search(p) == 0
+    _, _, two, _, _ = deep_raw(None, "padded")
+    for k in two.frame:
+        two.frame[k].view.copy_(one.frame[k].view)
+    assert two.search(1 << 14) == 0 and two.search(1 << 14) == 0
+    two.expect(last, running=0)
+    path = two.path0.copy()
+    for c, (f, g) in enumerate(zip(last, at_p)):
+        if f.status == R.SOLVED and not g.status:
+            path[f.floor:f.depth, c] = f.nib[f.floor:f.depth]
+    two.path.expect(path)
+    two.check(f"resumed after {p} passes")
+    assert sum(not g.status for g in at_p) >= (4 if p > 5 else 10)
+
+
+def test_a_written_frame_that_is_invalid_gets_bad_frame_and_keeps_every_byte(tabs):
+    """ida_search on frames the caller wrote, one column per invalid frame of the header's list beside valid neighbours (even
+    columns): the invalid column gets IDA_BAD_FRAME and keeps every other byte of its frame and of its path column, running does not
+    count it, a second call leaves it alone, and the neighbours finish as the restatement says.  Column 17 is a frame of fill bytes
+    with status 0; column 19 has depth > bound, which is taken."""
+    _lib, _, _, _, _ = mods()
+    _lib.init(torch.device(DEV, torch.cuda.current_device()))
+    h = tabs["none"][1]
+    c = DC.IdaCase(17, 3)
+    good = dict(floor=17, trail=c.W[:18], depth=18, bound=20, next=R.INF, cursor=3, nodes=5)
+    fill = dict(floor=0, trail=[5, 10] * 16, depth=-0x5A5A5A5B, bound=-0x5A5A5A5B, next=-0x5A5A5A5B, cursor=FILL, nodes=0xA5A5A5A5A5A5A5A5)
+    bad = [dict(floor=-1), dict(floor=33), dict(depth=16), dict(depth=33, bound=32), dict(cursor=13), dict(bound=33), dict(trail=c.W[:17] + [12]),
+           dict(trail=[15] + c.W[1:18]), fill, dict(bound=17)]
+    kws = [{**good, **(bad[i // 2] if i % 2 else {})} for i in range(2 * len(bad) + 1)]
+    n = len(kws)
+    frames = [R.Frame.resume(c.root, h, 32, 32, **kw) for kw in kws]
+    assert [f.status for f in frames] == [R.BAD_FRAME if i % 2 and i < 19 else 0 for i in range(n)]
+    raw = Raw(None, np.array([c.root] * n, np.uint8), "padded", 32, np.full(n, 32, np.int32), np.array([c.column] * n, np.uint8).T,
+              np.array([kw["floor"] for kw in kws], np.int32))
+    written = [f.clone() for f in frames]
+    for f in written:
+        f.status = 0
+    raw.expect(written)
+    for a in raw.arenas:
+        a.upload()
+    for f in frames:
+        f.run(max_nodes=10 ** 9)
+    assert all(f.status == R.SOLVED and f.depth == 20 for f in frames[::2]) and frames[19].status == R.SOLVED
+    assert max(f.passes for f in frames) <= 1 << 14
+    assert raw.search(1 << 14) == 0
+    raw.expect(frames, running=0)
+    raw.check("written frames")
+    assert raw.search(1 << 14) == 0
+    raw.check("a second call")
+
+
+def test_the_python_layer_at_depth_32(tabs, monkeypatch):
+    """search.IdaFrame with a 29-row prefix and limit 32 returns the deep set's answer at depth 32; search.ida_search(limit=32) on
+    cubes 0..3 moves from solved, unsplit and split, allocates 32 rows of path and returns [max(1, length.max()), n] actions."""
+    _, _, ops, _, search = mods()
+    c = DC.IdaCase(29, 3)
+    want = c.frame(tabs["none"][1]).run(max_nodes=10 ** 9)
+    env = env_of_bytes(np.array([c.root], np.uint8))
+    cub = ops.cubies(env.stickers, 1, 3, status=False)["cubies"]
+    fr = search.IdaFrame(None, cub, 1, ops._state_arg(cub, 20, 1, None, "cubies"), 32, 32, prefix=torch.as_tensor(c.W[:29], dtype=torch.uint8, device=DEV)[:, None])
+    fr.init()
+    assert fr.run(1 << 15, 1 << 14) <= 1 << 15 and int(fr.running[0]) == 0
+    assert (int(fr.status[0]), int(fr.depth[0]), int(fr.nodes[0])) == (R.SOLVED, 32, want.nodes) and fr.path.shape[0] == 32
+    assert fr.path[:, 0].cpu().tolist() == want.nib[:32] and want.nib[:29] == c.W[:29]
+    assert R.replay_bytes(c.root, fr.path[:, 0].cpu().tolist()) == R.to_bytes(R.HOME)
+    seen = []
+    real = search.IdaFrame
+
+    class Watched(real):
+        def __init__(self, *a, **kw):
+            super().__init__(*a, **kw)
+            seen.append(tuple(self.path.shape))
+    monkeypatch.setattr(search, "IdaFrame", Watched)
+    table, h = tabs["best"]
+    scr = np.pad(scrambles(3, [0, 1, 2, 3, 3, 2, 1, 3], seed=32), ((0, 0), (0, 1)), constant_values=12)
+    env = env_of(3, scr)
+    rows = bytes_of(env)
+    res = {}
+    for split in (0, 1):
+        seen.clear()
+        res[split] = host(search.ida_search(table, env, limit=32, split=split))
+        assert seen and all(shape[0] == 32 for shape in seen), seen
+        r = res[split]
+        assert r["solved"].all() and r["actions"].shape == (max(1, int(r["length"].max())), 8) and r["length"].max() <= 3
+        for k in range(8):
+            assert (r["actions"][r["length"][k]:, k] == R.NOOP).all() and R.replay_bytes(rows[k], r["actions"][:r["length"][k], k]) == R.to_bytes(R.HOME)
+    for k in range(8):
+        same_as_frame(res[0], k, R.solve(rows[k], h, limit=32), "limit 32")
+    for k in ("solved", "status", "length", "bound", "actions"):
+        assert (res[0][k] == res[1][k]).all(), k
 
 
 # ------------------------------------------------------------------------------------------------------- 6. capture and replay

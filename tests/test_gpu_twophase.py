@@ -196,7 +196,7 @@ def check_phase1(state, frames, K, stride, what):
         assert int(state["found"][c]) == f.found, (what, c)
         for j in range(K):
             col = j * stride + c
-            path, rows = f.cands[j] if j < f.found else ((), R.HOME_ROWS.tolist())
+            path, rows = f.cands[j] if j < len(f.cands) else ((), R.HOME_ROWS.tolist())   # a refused frame's found may be any number
             assert state["path"][:, col].tolist() == list(path) + [R.NOOP] * (R.MAX_DEPTH - len(path)), (what, c, j)
             assert int(state["cand_length"][col]) == len(path) and state["cand_cubies"][:, col].tolist() == list(rows), (what, c, j)
     pad = np.ones(stride, bool)
@@ -370,6 +370,186 @@ def test_phase2_solves_every_g1_state_within_6_at_its_distance(tp):
     home = np.tile(R.HOME_ROWS, (n, 1))
     for c in range(0, n, 7):
         assert (R.move_rows(rows[c:c + 1], path[:d[c], c].tolist())[0] == home[0]).all(), c
+
+
+# ------------------------------------------------------------------------------------------- 4b. deep sets: written frames
+from tests import deep_cases as DC  # noqa: E402
+
+FIELDS = ("cursor", "depth", "bound", "next", "nodes", "status")
+
+
+def write_frames(fr, frames, phase):
+    """The restated frames' fields into the device frame, as a caller writes them (phase 1: found and the candidates too)."""
+    n = len(frames)
+    fr.trail[:n] = torch.as_tensor(np.array([f.words for f in frames], np.uint64).view(np.int64)).to(DEV)
+    for k in FIELDS:
+        t = getattr(fr, k)
+        t[:n] = torch.as_tensor(np.array([getattr(f, k) for f in frames], np.int64)).to(DEV).to(t.dtype)
+    if phase == 1:
+        fr.found[:n] = torch.as_tensor(np.array([f.found for f in frames], np.int64)).to(DEV).to(torch.int32)
+        for c, f in enumerate(frames):
+            for j, (path, rows) in enumerate(f.cands):
+                col = j * fr.stride + c
+                fr.path[:len(path), col] = torch.as_tensor(list(path), dtype=torch.uint8)
+                fr.cand_length[col] = len(path)
+                fr.cand_cubies[:, col] = torch.as_tensor(list(rows), dtype=torch.uint8)
+
+
+def deep2(tp, ref, max_depth):
+    """(cases, a fresh device frame with the written frames in it, the restated frames)"""
+    cases = DC.phase2_cases(max_depth)
+    fr = phase2_frame(tp, np.array([c.root for c in cases], np.uint8), [c.prefix for c in cases], [c.limit for c in cases], max_depth)
+    frames = [c.frame(ref["h2"]) for c in cases]
+    assert all(f.status == 0 for f in frames)
+    write_frames(fr, frames, 2)
+    return cases, fr, frames
+
+
+@pytest.mark.parametrize("max_depth", (48, 24))
+def test_deep_phase2_written_frames(tp, ref, max_depth):
+    """The written frames of tests/deep_cases.py (trails of 15..21 generators, floors to 20, answers to row 47): after 64 passes and
+    at the end every field, both trail words, every row of path and the running counter are the restatement's; launches of 1 and 7
+    leave the same bytes as one launch; a frame stored after p passes and copied into a fresh frame over a fresh path continues to
+    the same end."""
+    cases, fr, frames = deep2(tp, ref, max_depth)
+    prefixes = [c.prefix for c in cases]
+    fr.search(64)
+    for f in frames:
+        f.run(max_passes=64)
+    check_phase2(phase2_state(fr), frames, prefixes, "after 64 passes")
+    assert int(fr.running[0]) == sum(1 for f in frames if not f.status)
+    stored = {k: getattr(fr, k).clone() for k in ("trail",) + FIELDS}
+    fr.search(DC.PASS_CAP)
+    for c, f in zip(cases, frames):
+        f.run(max_passes=DC.PASS_CAP + 64)
+        assert f.status in c.want and f.passes <= DC.PASS_CAP, c.name
+    whole = phase2_state(fr)
+    check_phase2(whole, frames, prefixes, "at the end")
+    assert int(fr.running[0]) == 0 and (max_depth != 48 or any(f.status == R.SOLVED and f.depth == 48 for f in frames))
+    total = max(f.passes for f in frames)
+    for per_call in (1, 7):
+        _, cut, _ = deep2(tp, ref, max_depth)
+        for spent in range(0, total, per_call):
+            cut.search(min(per_call, total - spent))
+        same_frames(whole, phase2_state(cut), f"launches of {per_call}")
+    _, again, _ = deep2(tp, ref, max_depth)                                  # a fresh path: the prefixes alone
+    for k, v in stored.items():
+        getattr(again, k).copy_(v)
+    again.search(DC.PASS_CAP)
+    want = {k: v.copy() for k, v in whole.items()}
+    early = np.flatnonzero(stored["status"].cpu().numpy()[:len(cases)])      # ended before the copy: not touched, so no rows are written
+    for c in early:
+        want["path"][len(prefixes[c]):, c] = R.NOOP
+    same_frames(want, phase2_state(again), "resumed after 64 passes")
+    assert len(early) < len(cases)
+
+
+def deep1(tp, ref, K):
+    cases = [c for c in DC.phase1_cases() if c.K == K]
+    fr = phase1_frame(tp, np.array([c.root for c in cases], np.uint8), K, [c.limit for c in cases])
+    frames = [c.frame(ref["h1"]) for c in cases]
+    assert all(f.status == 0 for f in frames)
+    write_frames(fr, frames, 1)
+    return cases, fr, frames
+
+
+@pytest.mark.parametrize("K", (1, 8))
+def test_deep_phase1_written_frames(tp, ref, K):
+    """The written phase-1 frames (trails of 15..30 actions, bound to 32): after 64 passes and at the end every field, every candidate
+    column row by row (a candidate of length 32 fills rows 0..31), cand_length, cand_cubies and the running counter are the
+    restatement's; launches of 1 and 7 leave the same bytes; a frame stored after 64 passes, copied with the candidates emitted so
+    far, continues to the same end."""
+    cases, fr, frames = deep1(tp, ref, K)
+    fr.search(64)
+    for f in frames:
+        f.run(max_passes=64)
+    check_phase1(phase1_state(fr), frames, K, fr.stride, "after 64 passes")
+    assert int(fr.running[0]) == sum(1 for f in frames if not f.status)
+    stored = phase1_state(fr)
+    fr.search(DC.PASS_CAP)
+    for c, f in zip(cases, frames):
+        f.run(max_passes=DC.PASS_CAP + 64)
+        assert f.status == R.FULL and f.passes <= DC.PASS_CAP, c.name
+    whole = phase1_state(fr)
+    check_phase1(whole, frames, K, fr.stride, "at the end")
+    assert int(fr.running[0]) == 0 and any(len(p) == 32 for f in frames for p, _ in f.cands)
+    total = max(f.passes for f in frames)
+    for per_call in (7, 1) if K == 1 else (7,):
+        _, cut, _ = deep1(tp, ref, K)
+        for spent in range(0, total, per_call):
+            cut.search(min(per_call, total - spent))
+        same_frames(whole, phase1_state(cut), f"launches of {per_call}")
+    _, again, _ = deep1(tp, ref, K)
+    for k, v in stored.items():
+        getattr(again, k).copy_(torch.as_tensor(v).to(DEV))
+    again.search(DC.PASS_CAP)
+    same_frames(whole, phase1_state(again), "resumed after 64 passes")
+
+
+def test_phase1_launches_of_one_pass_on_the_deep_set(tp, ref):
+    """K = 8 in launches of ONE pass, 8192 of them: byte-equal to one launch of 8192 (the set's longer runs are cut at 7 above)."""
+    _, one, _ = deep1(tp, ref, 8)
+    _, cut, _ = deep1(tp, ref, 8)
+    one.search(8192)
+    for _ in range(8192):
+        cut.search(1)
+    same_frames(phase1_state(one), phase1_state(cut), "launches of 1")
+    assert int(one.running[0]) >= 1 and (one.status[:4] != 0).any()
+
+
+def test_written_frames_that_are_invalid_get_bad_frame_and_keep_every_byte(tp, ref):
+    """tp_phase1_search and tp_phase2_search on frames the caller wrote, one column per invalid frame of the header's list (odd
+    columns) beside valid neighbours: the invalid column gets TP_BAD_FRAME and keeps every other byte of its frame, of its path
+    column and (phase 1) of its candidate slots; running does not count it; a second call leaves it alone; the neighbours finish as
+    the restatement says."""
+    c = DC.Phase1Case(20, 17, 8)
+    good = dict(c.written, next=R.INF, nodes=0)
+    bad = [dict(depth=-1), dict(depth=32, bound=32, limit=32), dict(depth=21), dict(cursor=13), dict(bound=21), dict(found=-1), dict(found=8),
+           dict(trail=c.W[:16] + [12]), dict(trail=[14] + c.W[1:17])]
+    kws = [{**good, **(bad[i // 2] if i % 2 else {})} for i in range(2 * len(bad) + 1)]
+    limit = [kw.pop("limit", 20) for kw in kws]
+    n = len(kws)
+    frames = [R.Phase1.resume(c.root, ref["h1"], 8, lim, **kw) for kw, lim in zip(kws, limit)]
+    assert [f.status for f in frames] == [R.BAD_FRAME if i % 2 else 0 for i in range(n)]
+    fr = phase1_frame(tp, np.array([c.root] * n, np.uint8), 8, limit)
+    write_frames(fr, frames, 1)
+    fr.status[:n] = 0
+    for f in frames:
+        f.run(max_passes=DC.PASS_CAP)
+    assert all(f.status == R.FULL for f in frames[::2])
+    fr.search(DC.PASS_CAP)
+    state = phase1_state(fr)
+    check_phase1(state, frames, 8, fr.stride, "phase 1 written frames")
+    assert int(fr.running[0]) == 0
+    fr.search(64)
+    same_frames(state, phase1_state(fr), "phase 1, a second call")
+
+    c = DC.Phase2Case(16, 18, 15, cost=28)
+    good = dict(c.written, next=R.INF, nodes=0)
+    g, b, pre = good["depth"], good["bound"], tuple(c.prefix)
+    bad = [dict(floor_given=-1, prefix=()), dict(floor_given=49, prefix=()), dict(prefix=pre[:15] + (12,)), dict(prefix=pre[:14] + (200, 0)), dict(depth=15),
+           dict(depth=49, bound=49), dict(depth=b + 1, trail=c.W[:16]), dict(cursor=9), dict(bound=49), dict(limit=b - 1), dict(trail=c.W[:14] + [8]),
+           dict(depth=g + 1, trail=c.W[:15] + [2])]
+    kws = [{**good, **(bad[i // 2] if i % 2 else {})} for i in range(2 * len(bad) + 1)]
+    n = len(kws)
+    limit, prefixes, floors = [kw.pop("limit", 48) for kw in kws], [kw.pop("prefix", pre) for kw in kws], [kw.pop("floor_given", None) for kw in kws]
+    frames = [R.Phase2.resume(c.root, ref["h2"], lim, prefix=p_, floor_given=fl, **kw) for kw, lim, p_, fl in zip(kws, limit, prefixes, floors)]
+    assert [f.status for f in frames] == [R.BAD_FRAME if i % 2 else 0 for i in range(n)]
+    fr = phase2_frame(tp, np.array([c.root] * n, np.uint8), prefixes, limit)
+    for i, fl in enumerate(floors):
+        if fl is not None:
+            fr.floor[i] = fl
+    write_frames(fr, frames, 2)
+    fr.status[:n] = 0
+    for f in frames:
+        f.run(max_passes=DC.PASS_CAP)
+    assert all(f.status == R.SOLVED and f.depth == b for f in frames[::2])
+    fr.search(DC.PASS_CAP)
+    state = phase2_state(fr)
+    check_phase2(state, frames, prefixes, "phase 2 written frames")
+    assert int(fr.running[0]) == 0
+    fr.search(64)
+    same_frames(state, phase2_state(fr), "phase 2, a second call")
 
 
 # ---------------------------------------------------------------------------------------------------------------- 5. end to end

@@ -167,3 +167,68 @@ def test_python_argument_errors_come_before_any_device_use():
     # the library refuses before any launch too: no device is initialised here, and RC_EINVAL needs none for these
     L = _ida_lib.ida_lib()
     assert L.ida_canonical(None) == -1 and L.rc_last_error().startswith(b"ida_canonical")
+
+
+# ------------------------------------------------------------------------------------------------------------------ deep sets
+def test_the_deep_cases_end_within_the_pass_cap_and_reach_word_1_of_the_trail():
+    """tests/deep_cases.py, h = 0: every case ends in the status its construction predicts within PASS_CAP restated passes (printed);
+    a SOLVED case's prefix and solution rows bring the root home; and the set covers what it is there for -- word 1 of the trail
+    nonzero in every case that can reach nibble 16 (f + d > 16, d >= 1), a write at nibbles 15, 16 and 31, a node at g = 32."""
+    from tests import deep_cases as D
+    h, written, deepest = R.Heuristic(), set(), 0
+    cases = D.ida_cases() + D.ida_cases(20)
+    assert [(c.f, c.d) for c in cases] == [(13, 3), (14, 3), (15, 3), (16, 3), (17, 3), (28, 3), (29, 3), (30, 2), (31, 1), (32, 0), (29, 4),
+                                          (30, 3), (17, 3)] and cases[-1].max_depth == 20 and cases[3].column[16:] == [R.NOOP] * 16
+    for c in cases:
+        f = c.frame(h)
+        assert f.floor == f.depth == c.f and f.bound == c.f
+        f.run(max_passes=D.PASS_CAP + 1, max_nodes=10 ** 9)
+        print(f"deep IDA* {c.name}: {f.passes} passes, {f.nodes} nodes, status {f.status}, depth {f.depth}, next {f.next}")
+        assert f.passes <= D.PASS_CAP and f.status == c.want, c.name
+        if c.want == R.SOLVED:
+            assert f.depth == c.f + c.d and f.nib[:c.f] == c.W[:c.f] and R.replay_bytes(c.root, f.path) == R.to_bytes(R.HOME), c.name
+        else:
+            assert f.depth == c.f and f.next == c.f + c.d == 33, c.name
+        if c.d >= 1:
+            assert f.word1 == (c.f + c.d > 16), c.name
+            assert f.written == set(range(c.f, min(c.f + c.d, c.max_depth))), c.name
+        written |= f.written
+        deepest = max(deepest, f.deepest)
+    assert {15, 16, 31} <= written and deepest == 32
+
+
+def test_resume_refuses_what_the_header_refuses_and_continues_what_a_run_left():
+    """Frame.resume on a frame the caller wrote: each invalid frame of the header's list gets IDA_BAD_FRAME and keeps every field;
+    depth > bound is taken; the frame an uninterrupted run leaves after p passes, written back, continues to the same end."""
+    from tests import deep_cases as D
+    h = R.Heuristic()
+    c = D.IdaCase(17, 3)
+    whole = c.frame(h).run(max_nodes=10 ** 9)
+    good = dict(floor=17, trail=c.W[:18], depth=18, bound=20, next=R.INF, cursor=3, nodes=5)
+    assert R.Frame.resume(c.root, h, 32, 32, **good).status == 0
+    bad = [dict(floor=-1), dict(floor=33), dict(depth=16), dict(depth=33, bound=32), dict(cursor=13), dict(bound=33), dict(trail=c.W[:17] + [12]),
+           dict(trail=[15] + c.W[1:18])]
+    for kw in bad:
+        f = R.Frame.resume(c.root, h, 32, 32, **{**good, **kw})
+        assert f.status == R.BAD_FRAME, kw
+        w = {**good, **kw}
+        assert (f.floor, f.nib, f.depth, f.bound, f.next, f.cursor, f.nodes) == \
+               (w["floor"], (w["trail"] + [0] * 32)[:32], w["depth"], w["bound"], w["next"], w["cursor"], w["nodes"]), kw
+        assert f.run().passes == 0                                           # a frame with a status is not touched
+    assert R.Frame.resume(c.root, h, 20, 32, **{**good, "bound": 21}).status == R.BAD_FRAME       # the cap is min(limit, max_depth)
+    assert R.Frame.resume(c.root, h, 32, 20, **{**good, "bound": 21}).status == R.BAD_FRAME
+    assert R.Frame.resume(c.root, h, 32, 32, **{**good, "trail": c.W[:18] + [13]}).status == 0   # a stale nibble at or above depth
+    assert R.Frame.resume([24] + c.root[1:], h, 32, 32, **good).status == R.ILLEGAL
+    deep = R.Frame.resume(c.root, h, 32, 32, **{**good, "bound": 17})        # depth 18 > bound 17: taken; every child is dropped
+    assert deep.status == 0
+    while deep.depth == 18:
+        deep.step()
+    assert deep.depth == 17 and deep.next == 19 and deep.nodes - 5 == deep.passes - 1 > 0 and not deep.written
+    for p in (0, 1, 5, 700, whole.passes - 1):
+        cut = c.frame(h).run(max_passes=p, max_nodes=10 ** 9)
+        again = R.Frame.resume(c.root, h, 32, 32, **cut.written_frame())
+        assert again.status == 0 and again.x == cut.x
+        again.run(max_nodes=10 ** 9)
+        assert again.passes == whole.passes - p
+        assert (again.status, again.trail, again.depth, again.bound, again.next, again.cursor, again.nodes, again.words) == \
+               (whole.status, whole.trail, whole.depth, whole.bound, whole.next, whole.cursor, whole.nodes, whole.words), p

@@ -244,3 +244,115 @@ def test_python_argument_errors_come_before_any_device_use():
         pattern.TwoPhaseTables([torch.zeros(4, dtype=torch.uint8)] * 4)
     with pytest.raises(ValueError, match="HIP device"):
         pattern.TwoPhaseTables([torch.zeros(n, dtype=torch.uint8) for n in R.SIZE])
+
+
+# ------------------------------------------------------------------------------------------------------------------ deep sets
+def test_the_deep_phase2_cases_end_within_the_pass_cap_and_reach_the_upper_rows():
+    """tests/deep_cases.py: every written phase-2 frame is taken, ends in a status its construction predicts within PASS_CAP restated
+    passes (printed), and a SOLVED column's rows floor..depth-1 bring its root home; the set covers k0 = 15, 16, 17, k >= 24, f >= 16,
+    f + cost(W) = 48 = max_depth, floor + 32 as the cap and max_depth below the limit; word 1 of the trail is nonzero in every case
+    whose trail reaches nibble 16, and a half turn lies across rows 15/16 or 31/32 of a SOLVED path."""
+    from tests import deep_cases as D
+    h2 = R.Heuristic(2, tabs())
+    cases = D.phase2_cases() + D.phase2_cases(24)
+    assert {c.k0 for c in cases} >= {15, 16, 17} and any(c.k >= 24 for c in cases) and any(c.f >= 16 for c in cases)
+    assert any(c.total == 48 == c.max_depth == c.lim for c in cases) and any(c.lim == c.f + 32 < min(c.total, c.limit, c.max_depth) for c in cases)
+    assert any(c.lim == c.max_depth < min(c.total, c.limit, c.f + 32) for c in cases)
+    written, straddles = set(), 0
+    for c in cases:
+        f = c.frame(h2)
+        assert f.status == 0 and f.k == c.k0 and f.depth <= f.bound == min(c.total, c.lim), c.name
+        f.run(max_passes=D.PASS_CAP + 1)
+        print(f"deep phase 2 {c.name} ({c.why}): {f.passes} passes, {f.nodes} nodes, status {f.status}, depth {f.depth}, {f.k} generators")
+        assert f.passes <= D.PASS_CAP and f.status in c.want, c.name
+        if f.status == R.SOLVED:
+            assert f.depth <= f.bound and c.f + len(f.solution) == f.depth, c.name
+            assert R.apply(ida_ref.from_bytes(c.root), f.solution) == ida_ref.HOME, c.name
+            col = list(c.prefix) + f.solution
+            straddles += sum(1 for r in (15, 31) if r + 1 < len(col) and r >= c.f and col[r] == col[r + 1] and _one_half_turn(c.f, f, r))
+        else:
+            assert f.next > c.lim, c.name
+        assert f.word1 == (max(f.written | {c.k0 - 1}) >= 16 and any(f.nib[16:])), c.name
+        if max(f.written | {c.k0 - 1}) >= 16:
+            assert f.word1, c.name
+        written |= f.written
+    assert max(written) >= 16 and {15, 16, 17} <= written and straddles >= 1
+
+
+def _one_half_turn(floor, f, r):
+    """rows r, r + 1 of a SOLVED column are the two actions of ONE generator"""
+    row = floor
+    for j in f.nib[:f.k]:
+        if R.COST[2][j] == 2 and row == r:
+            return True
+        row += R.COST[2][j]
+    return False
+
+
+def test_the_deep_phase1_cases_end_within_the_pass_cap_and_emit_at_length_32():
+    """Every written phase-1 frame is taken and ends FULL within PASS_CAP restated passes (printed); every candidate ends in G1, has
+    the iteration's length and no U or D turn at its end; over the set an emission has length 32 (path row 31)."""
+    from tests import deep_cases as D
+    h1 = R.Heuristic(1, tabs())
+    cases = D.phase1_cases()
+    assert [(c.L, c.d0, c.K) for c in cases] == [(L, d0, K) for K in (1, 8) for L, d0 in ((18, 15), (20, 17), (32, 29), (32, 30))]
+    longest = 0
+    for c in cases:
+        f = c.frame(h1)
+        assert f.status == 0 and f.depth == c.d0 and f.bound == c.L == f.lim, c.name
+        f.run(max_passes=D.PASS_CAP + 1)
+        print(f"deep phase 1 {c.name}: {f.passes} passes, {f.nodes} nodes, status {f.status}, found {f.found}")
+        assert f.passes <= D.PASS_CAP and f.status == R.FULL and f.found == c.K, c.name
+        for path, rows in f.cands:
+            assert len(path) == c.L and path[-1] >> 1 not in (0, 3) and R.in_g1(np.array([rows]))[0], c.name
+            assert ida_ref.to_bytes(R.apply(ida_ref.from_bytes(c.root), path)) == rows, c.name
+        assert f.cands[0][0] == tuple(c.W) or c.K > 1 or len(f.cands[0][0]) == c.L
+        assert f.word1 and max(f.written) >= 16, c.name
+        longest = max(longest, max(len(p) for p, _ in f.cands))
+    assert longest == 32
+
+
+def test_resume_refuses_what_the_header_refuses_and_continues_what_a_run_left():
+    """Phase1.resume and Phase2.resume on frames the caller wrote: each invalid frame of the header's list gets TP_BAD_FRAME and keeps
+    its fields; the frame an uninterrupted run leaves after p passes, written back, continues to the same end."""
+    from tests import deep_cases as D
+    h1, h2 = R.Heuristic(1, tabs()), R.Heuristic(2, tabs())
+    c = D.Phase1Case(20, 17, 8)
+    good = dict(c.written, next=R.INF, nodes=0)
+    assert R.Phase1.resume(c.root, h1, 8, 20, **good).status == 0
+    for kw in (dict(depth=-1), dict(depth=32, bound=32), dict(depth=21), dict(cursor=13), dict(bound=21), dict(found=-1), dict(found=8),
+               dict(trail=c.W[:16] + [12]), dict(trail=[14] + c.W[1:17])):
+        f = R.Phase1.resume(c.root, h1, 8, 32 if kw.get("bound") == 32 else 20, **{**good, **kw})
+        assert f.status == R.BAD_FRAME, kw
+        assert f.fields() == dict(trail=f.words, cursor=kw.get("cursor", 0), depth=kw.get("depth", 17), bound=kw.get("bound", 20), next=R.INF,
+                                  nodes=0, status=R.BAD_FRAME) and f.found == kw.get("found", 0) and f.run().passes == 0, kw
+    assert R.Phase1.resume(c.root, h1, 8, 20, max_depth=19, **good).status == R.BAD_FRAME      # the cap is min(limit, max_depth, 32)
+    assert R.Phase1.resume(c.root, h1, 8, 40, **{**good, "bound": 33}).status == R.BAD_FRAME
+    whole = c.frame(h1).run()
+    for p in (1, 40, whole.passes // 2, whole.passes - 1):
+        cut = c.frame(h1).run(max_passes=p)
+        again = R.Phase1.resume(c.root, h1, 8, 20, **cut.written_frame()).run()
+        assert again.status == R.FULL and again.passes == whole.passes - p and again.fields() == whole.fields() and again.cands == whole.cands, p
+    c = D.Phase2Case(16, 18, 15, cost=28)
+    good = dict(c.written, next=R.INF, nodes=0)
+    make = lambda limit=48, prefix=tuple(c.prefix), max_depth=48, floor_given=None, **kw: R.Phase2.resume(
+        c.root, h2, limit, prefix=prefix, max_depth=max_depth, floor_given=floor_given, **{**good, **kw})
+    assert make().status == 0 and make().k == 15
+    g, b = good["depth"], good["bound"]
+    for kw in (dict(floor_given=-1), dict(floor_given=49), dict(prefix=tuple(c.prefix[:15]) + (12,)), dict(prefix=tuple(c.prefix[:14]) + (200, 0)),
+               dict(depth=15), dict(depth=49, bound=49), dict(max_depth=g - 1), dict(depth=b + 1, trail=c.W[:16]), dict(cursor=9), dict(bound=49),
+               dict(limit=b - 1), dict(max_depth=b - 1), dict(trail=c.W[:14] + [8]), dict(depth=g + 1, trail=c.W[:15] + [2])):   # F2: the costs step over g + 1
+        f = make(**kw)
+        assert f.status == R.BAD_FRAME, kw
+        assert (f.depth, f.bound, f.cursor, f.next, f.nodes) == (kw.get("depth", g), kw.get("bound", b), kw.get("cursor", 0), R.INF, 0), kw
+        assert f.words == [sum(v << (4 * i) for i, v in enumerate((kw.get("trail", c.W[:15]) + [0] * 32)[16 * w:16 * w + 16])) for w in range(2)], kw
+    assert make(limit=60, max_depth=48, bound=48).status == 0 and R.Phase2.resume(c.root, h2, 60, max_depth=48, **{**good, "depth": g - 16, "bound": 33}).status == R.BAD_FRAME
+    outside = R.Phase2.resume(ida_ref.to_bytes(R.apply(ida_ref.HOME, (2,))), h2, 48, **dict(good, depth=0, bound=10, trail=[]))
+    assert outside.status == R.OUTSIDE
+    c = D.phase2_cases()[-1]                                                 # the longest run of the set
+    whole = c.frame(h2).run()
+    assert whole.status == R.SOLVED and whole.passes > 1000
+    for p in (1, 100, whole.passes // 2, whole.passes - 1):
+        cut = c.frame(h2).run(max_passes=p)
+        again = R.Phase2.resume(c.root, h2, 48, prefix=tuple(c.prefix), **cut.written_frame()).run()
+        assert again.passes == whole.passes - p and again.fields() == whole.fields() and again.solution == whole.solution, p

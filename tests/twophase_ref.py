@@ -192,14 +192,22 @@ class _Machine:
         return dict(trail=self.words, cursor=self.cursor, depth=self.depth, bound=self.bound, next=self.next, nodes=self.nodes,
                     status=self.status)
 
+    def _blank(self, trail=(), cursor=0, depth=0, bound=0, next=INF, nodes=0):
+        self.nib = (list(trail) + [0] * MAX_TRAIL)[:MAX_TRAIL]              # entries from the current node on are stale
+        self.cursor, self.depth, self.bound, self.next, self.nodes, self.status, self.passes = cursor, depth, bound, next, nodes, 0, 0
+        self.written, self.word1 = set(), any(self.nib[16:])                # coverage: the nibbles a run writes; word 1 ever nonzero
+
+    def _wrote(self, i, v):
+        self.written.add(i)
+        self.word1 = self.word1 or (i >= 16 and v != 0)
+
 
 class Phase1(_Machine):
     """One cube's phase-1 frame, pass by pass.  cands: [(actions, cubie bytes)] in the order of emission."""
 
     def __init__(self, cub, h, K, limit, max_depth=MAX_DEPTH):
         self.h, self.K = h, K
-        self.nib = [0] * MAX_TRAIL                                  # entries from `depth` on are stale
-        self.cursor, self.depth, self.bound, self.next, self.nodes, self.status, self.passes = 0, 0, 0, INF, 0, 0, 0
+        self._blank()
         self.cands = []
         self.lim = min(limit, max_depth, MAX_TRAIL)
         x = ida_ref.from_bytes(cub)
@@ -218,9 +226,38 @@ class Phase1(_Machine):
         if not self.status and self.bound > self.lim:
             self.status, self.next = EXHAUSTED, self.bound
 
+    _found = None                                                   # a found the caller wrote that tp_phase1_search refuses
+
     @property
     def found(self):
-        return len(self.cands)
+        return len(self.cands) if self._found is None else self._found
+
+    @classmethod
+    def resume(cls, cub, h, K, limit, max_depth=MAX_DEPTH, trail=(), depth=0, bound=0, next=INF, cursor=0, nodes=0, cands=(), found=None):
+        """A frame the CALLER wrote, as tp_phase1_search takes it (the header's "written frame" rule): trail = the actions from the
+        root on, cands = the candidates emitted so far (found = their number unless given).  A refused frame gets TP_BAD_FRAME OR-ed
+        into its status and keeps every other field and every candidate slot as written."""
+        f = cls.__new__(cls)
+        f.h, f.K, f.lim = h, K, min(limit, max_depth, MAX_TRAIL)
+        f._blank(trail, cursor, depth, bound, next, nodes)
+        f.cands = list(cands)
+        if found is not None and found != len(f.cands):
+            f._found = found
+        x = ida_ref.from_bytes(cub)
+        if x is None:
+            f.status |= ILLEGAL
+        if not 0 <= depth < MAX_TRAIL or depth > bound or cursor > 12 or bound > f.lim or not 0 <= f.found < K:
+            f.status |= BAD_FRAME
+        elif not f.status and any(m >= 12 for m in f.nib[:depth]):
+            f.status |= BAD_FRAME
+        if not f.status:
+            f.x = apply(x, f.nib[:depth])
+        return f
+
+    def written_frame(self):
+        """the keyword arguments of resume() that rewrite this frame"""
+        return dict(trail=list(self.nib), depth=self.depth, bound=self.bound, next=self.next, cursor=self.cursor, nodes=self.nodes,
+                    cands=list(self.cands))
 
     def step(self):
         g, t = self.depth, self.nib
@@ -244,6 +281,7 @@ class Phase1(_Machine):
             else:
                 self.x, self.depth, self.cursor = y, g + 1, 0
                 t[g] = m
+                self._wrote(g, m)
         elif g > 0:
             self.x, self.cursor, self.depth = ida_ref.movers()[p1 ^ 1](self.x), p1 + 1, g - 1
         elif self.next > self.lim:
@@ -258,8 +296,8 @@ class Phase2(_Machine):
     def __init__(self, cub, h, limit, prefix=(), max_depth=MAX_DEPTH, floor_given=None):
         self.h = h
         self.floor = len(prefix) if floor_given is None else floor_given
-        self.nib = [0] * MAX_TRAIL                                  # generators 0..7; entries from `k` on are stale
-        self.k, self.cursor, self.depth, self.bound, self.next, self.nodes, self.status, self.passes = 0, 0, 0, 0, INF, 0, 0, 0
+        self._blank()                                               # nib: generators 0..7; entries from `k` on are stale
+        self.k = 0
         x = ida_ref.from_bytes(cub)
         if x is None:
             self.status |= ILLEGAL
@@ -282,6 +320,49 @@ class Phase2(_Machine):
             self.status, self.next = EXHAUSTED, self.bound
         elif h0 == 0:
             self.status = SOLVED
+
+    @classmethod
+    def resume(cls, cub, h, limit, prefix=(), max_depth=MAX_DEPTH, floor_given=None, trail=(), depth=0, bound=0, next=INF, cursor=0,
+               nodes=0):
+        """A column's frame the CALLER wrote, as tp_phase2_search takes it (the header's "written frame" rule): trail = the
+        generators after the prefix, depth = g = floor + their costs.  The number of generators on the trail is not stored: they are
+        read until their costs reach g, and must reach it exactly.  A refused frame gets TP_BAD_FRAME OR-ed into its status and keeps
+        every other field as written."""
+        f = cls.__new__(cls)
+        f.h, f.floor = h, len(prefix) if floor_given is None else floor_given
+        f._blank(trail, cursor, depth, bound, next, nodes)
+        f.k = 0
+        x = ida_ref.from_bytes(cub)
+        if x is None:
+            f.status |= ILLEGAL
+        floor = f.floor
+        last = list(prefix[max(0, floor - 2):max(0, floor)])
+        if not 0 <= floor <= max_depth or any(m >= 12 for m in last):
+            f.status |= BAD_FRAME
+            floor = 0
+        f.pre = ([NOOP, NOOP] + last)[-2:]
+        if not f.status and not in_g1(np.array([cub]))[0]:
+            f.status = OUTSIDE
+        f.lim = min(limit, max_depth, floor + MAX_TRAIL)
+        if depth < floor or depth > max_depth or depth > bound or cursor > 8 or bound > f.lim:
+            f.status |= BAD_FRAME
+        total = floor
+        for j in f.nib:                                                      # generators until their costs reach g
+            if f.status or total >= depth:
+                break
+            if j >= 8:
+                f.status |= BAD_FRAME
+            else:
+                x, total, f.k = apply(x, GENERATORS[2][j]), total + COST[2][j], f.k + 1
+        if not f.status and total != depth:
+            f.status |= BAD_FRAME
+        if not f.status:
+            f.x = x
+        return f
+
+    def written_frame(self):
+        """the keyword arguments of resume() that rewrite this frame"""
+        return dict(trail=list(self.nib), depth=self.depth, bound=self.bound, next=self.next, cursor=self.cursor, nodes=self.nodes)
 
     def last_two(self):
         acts = list(self.pre) + [a for j in self.nib[:self.k] for a in GENERATORS[2][j]]
@@ -307,6 +388,7 @@ class Phase2(_Machine):
             else:
                 self.x, self.depth, self.k, self.cursor = y, g + w, k + 1, 0
                 t[k] = j
+                self._wrote(k, j)
                 if h == 0:
                     self.status = SOLVED
         elif k > 0:
