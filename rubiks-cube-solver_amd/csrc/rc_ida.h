@@ -1,21 +1,36 @@
-// rc_ida.h -- iterative-deepening A*: the ida_* entry points (include/rubikhip.h "Iterative-deepening A*", DESIGN.md "IDA*"): Korf's
-// cost-bounded depth-first search under the maximum of the corner table and up to four edge tables (read through rc_table.h
-// table_at), one lane per cube, no node memory.  A part of rubikhip.hip's translation unit, after rc_edge.h (EdgeSet, edge_table_arg)
-// and rc_chain.h (load_cubie_bytes).  3x3x3 only.
+// rc_ida.h -- cost-bounded depth-first search, one lane per cube, no node memory: the ida_* entry points (include/rubikhip.h
+// "Iterative-deepening A*", DESIGN.md "IDA*") and the tp_* entry points (include/rubikhip.h "Two-phase", DESIGN.md "Two-phase").  A part
+// of rubikhip.hip's translation unit, after rc_edge.h (EdgeSet, edge_table_arg) and rc_chain.h (load_cubie_bytes, TpLevels).  3x3x3 only.
+//   the core        move rows (move_row, MoveTable, moves_load), the cube (IdaCube, ida_move), the frame (SearchFrame, IdaLane,
+//                   frame_load, frame_store), the trail replayed (ida_replay), the state machine (ida_passes) and the host's argument
+//                   checks and launcher -- each written once; a two-phase search is a policy type (Tp1Search, Tp2Search).  k_ida_search
+//                   keeps its own copy of the pass loop: through ida_passes it measured 2.8 % slower under the corner table
+//                   (DESIGN.md "IDA*"), so whoever changes a pass changes it there and in ida_passes
 //   k_ida_init      legality, the prefix replayed, the first bound, the frame's first contents
-//   k_ida_search    at most max_steps passes of the state machine per cube; a pass applies ONE move to the cube in registers -- the next
-//                   canonical child, or the inverse of the last move to go back a level -- then ranks, reads the tables and compares
-// The cube lives in five registers of cubie bytes (IdaCube); a move is a byte gather (v_perm_b32) whose selectors come from a row of
-// s_moves, the 13 rows (12 actions and the identity) in LDS: the move index varies by lane, so nothing here is a compile-time gather
-// and nothing is a switch.  The trail lives in two 64-bit registers of nibbles.  No indexed array, no scratch.
+//   k_ida_search    Korf's IDA* under the maximum of the corner table and up to four edge tables (read through rc_table.h table_at)
+//   k_tp1_init / k_tp1_search   Kociemba's phase 1 under max(twist-slice, flip-slice): up to K G1 candidates per cube are emitted
+//                               (path column, length, cubie rows), the search never enters G1
+//   k_tp2_init / k_tp2_search   phase 2, one lane per candidate column, under max(corner-slice, edge-slice): stage 2's generators with
+//                               a half turn costing 2; the first goal ends the lane
+// A search kernel makes at most max_steps passes per cube; a pass applies ONE move to the cube in registers -- the next canonical
+// child, or the inverse of the last move to go back a level -- then ranks, reads the tables and compares.  The cube lives in five
+// registers of cubie bytes (IdaCube); a move is a byte gather (v_perm_b32) whose selectors come from a row of s_moves in LDS (13 rows:
+// 12 actions and the identity; the tp searches add the half turns F2, R2, B2, L2, so a phase-2 generator is one gather): the move
+// varies by lane, so nothing here is a compile-time gather and nothing is a switch.  The trail lives in two 64-bit registers of
+// nibbles.  No indexed array, no scratch.
 #pragma once
 
 namespace {
 
-constexpr int kIdaMaxDepth = 32, kIdaMaxEdge = 4;
+constexpr int kIdaTrail = 32;                                               // nibbles in the two words of a trail
+constexpr int kIdaMaxDepth = kIdaTrail, kIdaMaxEdge = 4;
 constexpr uint32_t kIdaNoMove = 12u;
 constexpr int32_t kIdaInf = 0x7FFFFFFF;
 constexpr int64_t kIdaMaxSteps = (int64_t)1 << 14;                          // DESIGN.md "IDA*": 0.83 s a launch at 2^20 cubes, three tables
+constexpr int kTpMaxDepth = 48, kTpMaxTrail = kIdaTrail, kTpRows = 17, kTpMaxK = 4096;
+constexpr int64_t kTpMaxSteps = (int64_t)1 << 17;                           // DESIGN.md "Two-phase": 0.73 | 0.89 s a launch at 2^20 lanes
+static_assert(TP_SOLVED == IDA_SOLVED && TP_EXHAUSTED == IDA_EXHAUSTED && TP_ILLEGAL == IDA_ILLEGAL && TP_BAD_FRAME == IDA_BAD_FRAME,
+              "the core below sets the IDA_ codes for both families");
 
 // THE RULE's canonical moves: bit m set = move m may follow a path that ends ..., p2, p1 (12: no move)
 __host__ __device__ constexpr uint32_t ida_allowed(uint32_t p2, uint32_t p1) {
@@ -28,37 +43,50 @@ __host__ __device__ constexpr uint32_t ida_allowed(uint32_t p2, uint32_t p1) {
     return m;
 }
 
-// Row a of the move table: 0, 1 the corner selectors; 2, 3 the twists in the high nibbles; 4 + 2j, 5 + 2j the selectors of edge dword j
-// from (e1, e0) and from e2 (0x0c: a zero byte); 10..12 the flips.  Row 12 is the identity.
-struct IdaMoves {
-    uint32_t w[13][16];
-    constexpr IdaMoves() : w{} {
-        for (int a = 0; a < 13; ++a) {
-            for (int q = 0; q < 8; ++q) {
-                const uint32_t s = a < 12 ? Cube3::cmove_src[a][q] : (uint32_t)q, t = a < 12 ? Cube3::cmove_twist[a][q] : 0u;
-                w[a][q >> 2] |= s << (8 * (q & 3));
-                w[a][2 + (q >> 2)] |= (t << 4) << (8 * (q & 3));
-            }
-            for (int q = 0; q < 12; ++q) {
-                const uint32_t s = a < 12 ? Cube3::emove_src[a][q] : (uint32_t)q, f = a < 12 ? Cube3::emove_flip[a][q] : 0u;
-                w[a][4 + 2 * (q >> 2)] |= (s < 8u ? s : 0x0cu) << (8 * (q & 3));
-                w[a][5 + 2 * (q >> 2)] |= (s < 8u ? 0x0cu : s - 8u) << (8 * (q & 3));
-                w[a][10 + (q >> 2)] |= f << (8 * (q & 3));
-            }
+// ---------------------------------------------------------------------------------------------------------------- move rows
+// One row of the move table: 0, 1 the corner selectors; 2, 3 the twists in the high nibbles; 4 + 2j, 5 + 2j the selectors of edge
+// dword j from (e1, e0) and from e2 (0x0c: a zero byte); 10..12 the flips.
+constexpr void move_row(uint32_t (&w)[16], const uint8_t *csrc, const uint8_t *ctwist, const uint8_t *esrc, const uint8_t *eflip) {
+    for (int q = 0; q < 8; ++q) {
+        w[q >> 2] |= (uint32_t)csrc[q] << (8 * (q & 3));
+        w[2 + (q >> 2)] |= ((uint32_t)ctwist[q] << 4) << (8 * (q & 3));
+    }
+    for (int q = 0; q < 12; ++q) {
+        const uint32_t s = esrc[q];
+        w[4 + 2 * (q >> 2)] |= (s < 8u ? s : 0x0cu) << (8 * (q & 3));
+        w[5 + 2 * (q >> 2)] |= (s < 8u ? 0x0cu : s - 8u) << (8 * (q & 3));
+        w[10 + (q >> 2)] |= (uint32_t)eflip[q] << (8 * (q & 3));
+    }
+}
+
+// Rows 0..11 the actions, 12 the identity; R = 17 adds 13..16 = F2, R2, B2, L2 (among stage 3's U2 F2 R2 D2 B2 L2)
+template <int R>
+struct MoveTable {
+    uint32_t w[R][16];
+    constexpr MoveTable() : w{} {
+        const uint8_t same[12] = {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11}, none[12] = {}, half[4] = {1, 2, 4, 5};
+        for (int a = 0; a < 12; ++a) move_row(w[a], Cube3::cmove_src[a], Cube3::cmove_twist[a], Cube3::emove_src[a], Cube3::emove_flip[a]);
+        move_row(w[12], same, none, same, none);
+        for (int k = 0; k < R - 13; ++k) {
+            const ChainGen g = chain_gen(3, half[k]);
+            move_row(w[13 + k], g.csrc, g.ctw, g.esrc, g.eflip);
         }
     }
 };
-__constant__ IdaMoves c_ida_moves{};
+__constant__ MoveTable<13> c_ida_moves{};
+__constant__ MoveTable<kTpRows> c_tp_moves{};
 
+template <int R>
+__device__ __forceinline__ void moves_load(uint32_t (*s_moves)[16], const uint32_t (&w)[R][16]) {
+    for (uint32_t i = threadIdx.x; i < (uint32_t)R * 16u; i += blockDim.x) s_moves[i >> 4][i & 15u] = w[i >> 4][i & 15u];
+    __syncthreads();
+}
+
+// ----------------------------------------------------------------------------------------------------------------- the cube
 struct IdaCube {
     uint32_t c0, c1;       // byte q: corner slot q, piece | ori << 4
     uint32_t e0, e1, e2;   // byte q: edge slot q, the cubie byte piece * 2 + ori
 };
-
-__device__ __forceinline__ void ida_moves_load(uint32_t (*s_moves)[16]) {
-    for (uint32_t i = threadIdx.x; i < 13u * 16u; i += blockDim.x) s_moves[i >> 4][i & 15u] = c_ida_moves.w[i >> 4][i & 15u];
-    __syncthreads();
-}
 
 __device__ __forceinline__ IdaCube ida_move(const IdaCube &x, const uint32_t *row) {
     const u32x4 a = *reinterpret_cast<const u32x4 *>(row), b = *reinterpret_cast<const u32x4 *>(row + 4),
@@ -89,6 +117,212 @@ __device__ __forceinline__ bool ida_load(const uint8_t *at, int64_t pitch, IdaCu
     return ok;
 }
 
+__device__ __forceinline__ uint32_t ida_nib(uint64_t lo, uint64_t hi, int i) {   // i in 0..31
+    return (uint32_t)((i & 16 ? hi : lo) >> (4 * (i & 15))) & 15u;
+}
+__device__ __forceinline__ void ida_nib_set(uint64_t &lo, uint64_t &hi, int i, uint32_t v) {
+    const uint64_t keep = ~(15ull << (4 * (i & 15))), put = (uint64_t)v << (4 * (i & 15));
+    if (i & 16) hi = (hi & keep) | put;
+    else lo = (lo & keep) | put;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- the frame
+// The caller's arrays, one entry per lane (trail: two), and the two arguments of a search launch; a part of every kernel's arguments.
+struct SearchFrame {
+    uint64_t *trail;
+    uint8_t *cursor;
+    int32_t *depth, *bound, *next;
+    uint64_t *nodes;
+    uint8_t *status;
+    int64_t max_steps;
+    uint32_t *running;
+};
+
+// One lane's frame in registers.  k, the nibbles in the trail, is not stored: where every generator costs 1 it is depth itself,
+// otherwise ida_replay counts it.
+struct IdaLane {
+    uint64_t lo = 0, hi = 0, nodes = 0;
+    uint32_t cursor = 0, status = 0;
+    int32_t depth = 0, bound = 0, next = kIdaInf, k = 0;
+};
+
+__device__ __forceinline__ IdaLane frame_load(const SearchFrame &fr, int64_t c) {   // of a lane whose stored status is 0
+    return IdaLane{fr.trail[2 * c], fr.trail[2 * c + 1], fr.nodes[c], fr.cursor[c], 0u, fr.depth[c], fr.bound[c], fr.next[c], 0};
+}
+
+__device__ __forceinline__ void frame_store(const SearchFrame &fr, int64_t c, const IdaLane &l) {
+    fr.trail[2 * c] = l.lo;
+    fr.trail[2 * c + 1] = l.hi;
+    fr.cursor[c] = (uint8_t)l.cursor;
+    fr.depth[c] = l.depth;
+    fr.bound[c] = l.bound;
+    fr.next[c] = l.next;
+    fr.nodes[c] = l.nodes;
+    fr.status[c] = (uint8_t)l.status;
+}
+
+// A frame's first contents beside its status: nothing spent, the first bound f + h.  first_over: that bound is beyond the limit.
+__device__ __forceinline__ void first_bound(IdaLane &l, int32_t f, uint32_t h) {
+    l.depth = f;
+    l.bound = f + (int32_t)h;
+}
+__device__ __forceinline__ bool first_over(IdaLane &l, int32_t lim) {
+    if (l.bound <= lim) return false;
+    l.status = IDA_EXHAUSTED;
+    l.next = l.bound;
+    return true;
+}
+
+// -------------------------------------------------------------------------------------------------------- the state machine
+// A search is a policy type P.  What it says of its generators (the nibbles of the trail, the bits of the open mask):
+//   NGEN, NONE           their number; the `last` of an empty trail
+//   UNIT                 every generator costs 1: depth is the trail's length, and no second count is kept
+//   row(j), undo(j)      the rows of s_moves that apply generator j and take it back
+//   cost(j)              1, or 2 for a half turn
+//   allowed(l, k, last)  the generators that may follow a trail of k nibbles ending in `last`
+// and of the search:
+//   floor                the trail length below which it does not go back
+//   h(y, live)           the heuristic, 0xFF for a cube no table knows; !live: no table is read
+//   enters(h)            an admissible child (f <= bound) becomes the current node; otherwise it is passed over after
+//   emit(l, y, j)        -> 0 or the status that ends the lane
+//   goal(y, h)           the child just entered ends the lane as SOLVED
+
+// The current node: the root moved along the trail, generators until their costs reach l.depth from `from`.  A nibble that is no
+// generator, or costs that step over l.depth, make a bad frame.  Every lane makes every move: a lane with nothing to replay, the identity.
+template <class P>
+__device__ __forceinline__ void ida_replay(uint32_t (*s_moves)[16], IdaCube &x, IdaLane &l, bool live, int32_t from) {
+    int32_t sum = from;
+    for (int r = 0; r < kIdaTrail; ++r) {
+        uint32_t row = kIdaNoMove;
+        if (live && !l.status && (P::UNIT ? r < l.depth : sum < l.depth)) {
+            const uint32_t j = ida_nib(l.lo, l.hi, r);
+            if (j >= P::NGEN) {
+                l.status |= IDA_BAD_FRAME;
+            } else {
+                row = P::row(j);
+                sum += P::cost(j);
+                ++l.k;
+            }
+        }
+        x = ida_move(x, s_moves[row]);
+    }
+    if (!P::UNIT && live && !l.status && sum != l.depth) l.status |= IDA_BAD_FRAME;
+}
+
+// At most fr.max_steps passes of the lanes that run, then their count added to *fr.running.
+template <class P>
+__device__ __forceinline__ void ida_passes(P &p, uint32_t (*s_moves)[16], const SearchFrame &fr, IdaCube &x, IdaLane &l, int32_t lim, bool run) {
+    constexpr uint32_t ALL = (1u << P::NGEN) - 1u;
+    const int32_t steps = __builtin_amdgcn_readfirstlane((int32_t)fr.max_steps);   // <= 2^17, one value per wave
+    for (int32_t step = 0; step < steps; ++step) {                 // the only loop: whatever the tables hold, it ends
+        if (__ballot(run) == 0ull) break;
+        if (run) {
+            const int32_t g = l.depth, k = P::UNIT ? g : l.k;
+            const uint32_t last = k >= 1 ? ida_nib(l.lo, l.hi, k - 1) : P::NONE;
+            const uint32_t open = p.allowed(l, k, last) & (ALL << l.cursor) & ALL;
+            const bool gen = open != 0u, back = !gen && k > p.floor;
+            const uint32_t m = gen ? (uint32_t)__ffs((int)open) - 1u : P::NGEN;
+            const IdaCube y = ida_move(x, s_moves[gen ? P::row(m) : back ? P::undo(last) : kIdaNoMove]);
+            const uint32_t h = p.h(y, gen);
+            if (gen) {
+                ++l.nodes;
+                const int32_t w = P::cost(m), fv = g + w + (int32_t)h;
+                if (h == 0xFFu) {
+                    l.status = IDA_ILLEGAL;
+                    run = false;
+                } else if (fv > l.bound) {
+                    l.next = fv < l.next ? fv : l.next;
+                    l.cursor = m + 1u;
+                } else if (!p.enters(h)) {
+                    l.cursor = m + 1u;
+                    if (const uint32_t over = p.emit(l, y, m)) {
+                        l.status = over;
+                        run = false;
+                    }
+                } else {                                                  // fv <= bound <= the limit: nibble k and row g exist
+                    x = y;
+                    ida_nib_set(l.lo, l.hi, k, m);
+                    l.k = k + 1;
+                    l.depth = g + w;
+                    l.cursor = 0;
+                    l.status = p.goal(y, h) ? IDA_SOLVED : 0u;           // a running lane's status is 0
+                    run = !l.status;
+                }
+            } else if (back) {
+                x = y;
+                l.cursor = last + 1u;
+                l.k = k - 1;
+                l.depth = g - P::cost(last);
+            } else if (l.next > lim) {                                    // the iteration is exhausted
+                l.status = IDA_EXHAUSTED;
+                run = false;
+            } else {
+                l.bound = l.next;
+                l.next = kIdaInf;
+                l.cursor = 0;
+            }
+        }
+    }
+    const unsigned long long bal = __ballot(run);
+    if (threadIdx.x == 0 && bal) atomicAdd(fr.running, (uint32_t)__popcll(bal));
+}
+
+// ------------------------------------------------------------------------------------------------- host: arguments, launches
+int cubie_arg(const char *fn, const uint8_t *cubies, int64_t n, int64_t cubie_pitch, int &sh) {
+    if (n < 0) return fail(RC_EINVAL, "%s: n is negative", fn);
+    if (!cubies || !aligned16(cubies)) return fail(RC_EINVAL, "%s: cubies is NULL or not 16-byte aligned", fn);
+    sh = tile_shift(cubie_pitch, n, Cube3::SLOTS);
+    if (sh < 0) return fail(RC_EINVAL, "%s: cubie_pitch: need pitch %% 16 == 0 and pitch >= n, or a power-of-two tile >= 512", fn);
+    return RC_OK;
+}
+
+// cap: 32 or 48 rows; cols: the columns path must hold, and how the message names them
+int path_arg(const char *fn, const uint8_t *path, int max_depth, int64_t path_pitch, int cap, int64_t cols, const char *cols_name) {
+    if (!path || !aligned16(path)) return fail(RC_EINVAL, "%s: path is NULL or not 16-byte aligned", fn);
+    if (max_depth < 1 || max_depth > cap) return fail(RC_EINVAL, "%s: max_depth must be in 1..%s", fn, cap == kIdaMaxDepth ? "32" : "48");
+    if (path_pitch < cols || (path_pitch & 15) != 0)
+        return fail(RC_EINVAL, "%s: path_pitch: need path_pitch %% 16 == 0 and path_pitch >= %s", fn, cols_name);
+    return RC_OK;
+}
+
+// found: phase 1's extra field (NULL: the search has none), checked where its argument stands
+int frame_arg(const char *fn, const SearchFrame &fr, const int32_t *const *found = nullptr) {
+    const auto need = [fn](const void *p, const char *name) {
+        return p && aligned16(p) ? RC_OK : fail(RC_EINVAL, "%s: %s is NULL or not 16-byte aligned", fn, name);
+    };
+    if (int rc = need(fr.trail, "trail")) return rc;
+    if (int rc = need(fr.cursor, "cursor")) return rc;
+    if (int rc = need(fr.depth, "depth")) return rc;
+    if (int rc = need(fr.bound, "bound")) return rc;
+    if (int rc = need(fr.next, "next")) return rc;
+    if (int rc = need(fr.nodes, "nodes")) return rc;
+    if (found)
+        if (int rc = need(*found, "found")) return rc;
+    return need(fr.status, "status");
+}
+
+int steps_arg(const char *fn, const SearchFrame &fr, int64_t cap, const char *cap_name) {
+    if (fr.max_steps < 1 || fr.max_steps > cap) return fail(RC_EINVAL, "%s: max_steps must be in 1..%s", fn, cap_name);
+    if (!fr.running || !aligned16(fr.running)) return fail(RC_EINVAL, "%s: running is NULL or not 16-byte aligned", fn);
+    return RC_OK;
+}
+
+// One lane per cube in blocks of a wave; a search (a.fr.running set) zeroes its counter in front of the kernel
+template <class Args, class Kernel>
+int ida_launch(Kernel kernel, const Args &a, hipStream_t st) {
+    if (a.n == 0) return RC_OK;
+    const int64_t blocks = ceil_div(a.n, kWave);
+    RC_GRID(blocks);
+    if (a.fr.running) {
+        hipLaunchKernelGGL(k_zero32, dim3(1), dim3(1), 0, st, a.fr.running);
+        RC_HIP(RC_EHIP, hipGetLastError());
+    }
+    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(kWave), 0, st, a);
+    RC_HIP(RC_EHIP, hipGetLastError());
+    return RC_OK;
+}
+
+// ======================================================================================================================= IDA*
 struct IdaTables {
     const uint8_t *corner;                 // NULL: no corner table
     const uint8_t *edge[kIdaMaxEdge];
@@ -129,15 +363,6 @@ __device__ __forceinline__ uint32_t ida_h(const IdaCube &x, const IdaTables &t, 
     return h;
 }
 
-__device__ __forceinline__ uint32_t ida_nib(uint64_t lo, uint64_t hi, int i) {   // i in 0..31
-    return (uint32_t)((i & 16 ? hi : lo) >> (4 * (i & 15))) & 15u;
-}
-__device__ __forceinline__ void ida_nib_set(uint64_t &lo, uint64_t &hi, int i, uint32_t v) {
-    const uint64_t keep = ~(15ull << (4 * (i & 15))), put = (uint64_t)v << (4 * (i & 15));
-    if (i & 16) hi = (hi & keep) | put;
-    else lo = (lo & keep) | put;
-}
-
 struct IdaArgs {
     const uint8_t *cubies;
     int64_t n, pitch;
@@ -147,68 +372,49 @@ struct IdaArgs {
     int32_t max_depth;
     int64_t path_pitch;
     const int32_t *floor, *limit;
-    uint64_t *trail;
-    uint8_t *cursor;
-    int32_t *depth, *bound, *next;
-    uint64_t *nodes;
-    uint8_t *status;
-    int64_t max_steps;
-    uint32_t *running;
+    SearchFrame fr;
 };
 
 __global__ void __launch_bounds__(kWave) k_ida_init(IdaArgs a) {
     __shared__ __attribute__((aligned(16))) uint32_t s_moves[13][16];
-    ida_moves_load(s_moves);
+    moves_load(s_moves, c_ida_moves.w);
     const int64_t c = (int64_t)blockIdx.x * kWave + threadIdx.x;
     if (c >= a.n) return;
     IdaCube x;
-    uint32_t status = ida_load(a.cubies + cubie_off(c, a.pitch, a.sh, Cube3::SLOTS), a.pitch, x) ? 0u : IDA_ILLEGAL;
+    IdaLane l;
+    l.status = ida_load(a.cubies + cubie_off(c, a.pitch, a.sh, Cube3::SLOTS), a.pitch, x) ? 0u : IDA_ILLEGAL;
     const int32_t f = a.floor ? a.floor[c] : 0;
-    if (f < 0 || f > a.max_depth) status |= IDA_BAD_FRAME;
+    if (f < 0 || f > a.max_depth) l.status |= IDA_BAD_FRAME;
     uint64_t lo = 0, hi = 0;
     for (int r = 0; r < kIdaMaxDepth; ++r) {                              // the prefix: rows below floor <= max_depth are the caller's
         uint32_t m = kIdaNoMove;
-        if (!status && r < f) {
+        if (!l.status && r < f) {
             m = a.path[(int64_t)r * a.path_pitch + c];
             if (m >= kIdaNoMove) {
-                status |= IDA_BAD_FRAME;
+                l.status |= IDA_BAD_FRAME;
                 m = kIdaNoMove;
             }
         }
         x = ida_move(x, s_moves[m]);
         if (r < f) ida_nib_set(lo, hi, r, m);
     }
-    const uint32_t h = ida_h(x, a.t, status == 0u);
-    if (!status && h == 0xFFu) status = IDA_ILLEGAL;
-    int32_t depth = 0, bound = 0, next = kIdaInf;
-    if (!status) {
-        const int32_t lim = a.limit[c] < a.max_depth ? a.limit[c] : a.max_depth;
-        depth = f;
-        bound = f + (int32_t)h;
-        if (ida_goal(x)) {
-            status = IDA_SOLVED;
-        } else if (bound > lim) {
-            status = IDA_EXHAUSTED;
-            next = bound;
-        }
-    } else {
-        lo = hi = 0;
+    const uint32_t h = ida_h(x, a.t, l.status == 0u);
+    if (!l.status && h == 0xFFu) l.status = IDA_ILLEGAL;
+    if (!l.status) {
+        l.lo = lo;
+        l.hi = hi;
+        first_bound(l, f, h);
+        if (ida_goal(x)) l.status = IDA_SOLVED;
+        else first_over(l, a.limit[c] < a.max_depth ? a.limit[c] : a.max_depth);
     }
-    a.trail[2 * c] = lo;
-    a.trail[2 * c + 1] = hi;
-    a.cursor[c] = 0;
-    a.depth[c] = depth;
-    a.bound[c] = bound;
-    a.next[c] = next;
-    a.nodes[c] = 0;
-    a.status[c] = (uint8_t)status;
+    frame_store(a.fr, c, l);
 }
 
 __global__ void __launch_bounds__(kWave) k_ida_search(IdaArgs a) {
     __shared__ __attribute__((aligned(16))) uint32_t s_moves[13][16];
-    ida_moves_load(s_moves);
+    moves_load(s_moves, c_ida_moves.w);
     const int64_t c = (int64_t)blockIdx.x * kWave + threadIdx.x;
-    const bool mine = c < a.n && a.status[c] == 0u;                       // a cube with a nonzero status is not touched
+    const bool mine = c < a.n && a.fr.status[c] == 0u;                       // a cube with a nonzero status is not touched
     IdaCube x{};
     uint64_t lo = 0, hi = 0, nodes = 0;
     uint32_t status = 0, cursor = 0;
@@ -216,13 +422,13 @@ __global__ void __launch_bounds__(kWave) k_ida_search(IdaArgs a) {
     if (mine) {
         if (!ida_load(a.cubies + cubie_off(c, a.pitch, a.sh, Cube3::SLOTS), a.pitch, x)) status = IDA_ILLEGAL;
         f = a.floor ? a.floor[c] : 0;
-        lo = a.trail[2 * c];
-        hi = a.trail[2 * c + 1];
-        cursor = a.cursor[c];
-        depth = a.depth[c];
-        bound = a.bound[c];
-        next = a.next[c];
-        nodes = a.nodes[c];
+        lo = a.fr.trail[2 * c];
+        hi = a.fr.trail[2 * c + 1];
+        cursor = a.fr.cursor[c];
+        depth = a.fr.depth[c];
+        bound = a.fr.bound[c];
+        next = a.fr.next[c];
+        nodes = a.fr.nodes[c];
         lim = a.limit[c] < a.max_depth ? a.limit[c] : a.max_depth;
         if (f < 0 || f > a.max_depth || depth < f || depth > a.max_depth || cursor > kIdaNoMove || bound > lim) status |= IDA_BAD_FRAME;
     }
@@ -238,7 +444,7 @@ __global__ void __launch_bounds__(kWave) k_ida_search(IdaArgs a) {
         x = ida_move(x, s_moves[m]);
     }
     bool run = mine && !status;
-    for (int64_t step = 0; step < a.max_steps; ++step) {                  // the only loop: whatever the tables hold, it ends
+    for (int64_t step = 0; step < a.fr.max_steps; ++step) {                  // the only loop: whatever the tables hold, it ends
         if (__ballot(run) == 0ull) break;
         if (run) {
             const int g = depth;
@@ -282,31 +488,28 @@ __global__ void __launch_bounds__(kWave) k_ida_search(IdaArgs a) {
         }
     }
     if (mine) {
-        a.trail[2 * c] = lo;
-        a.trail[2 * c + 1] = hi;
-        a.cursor[c] = (uint8_t)cursor;
-        a.depth[c] = depth;
-        a.bound[c] = bound;
-        a.next[c] = next;
-        a.nodes[c] = nodes;
-        a.status[c] = (uint8_t)status;
+        a.fr.trail[2 * c] = lo;
+        a.fr.trail[2 * c + 1] = hi;
+        a.fr.cursor[c] = (uint8_t)cursor;
+        a.fr.depth[c] = depth;
+        a.fr.bound[c] = bound;
+        a.fr.next[c] = next;
+        a.fr.nodes[c] = nodes;
+        a.fr.status[c] = (uint8_t)status;
         if (status == IDA_SOLVED)
             for (int r = 0; r < kIdaMaxDepth; ++r)
                 if (r >= f && r < depth) a.path[(int64_t)r * a.path_pitch + c] = (uint8_t)ida_nib(lo, hi, r);   // depth <= max_depth
     }
     const unsigned long long bal = __ballot(run);
-    if (threadIdx.x == 0 && bal) atomicAdd(a.running, (uint32_t)__popcll(bal));
+    if (threadIdx.x == 0 && bal) atomicAdd(a.fr.running, (uint32_t)__popcll(bal));
 }
 
 int ida_args(const char *fn, const uint8_t *cubies, int64_t n, int64_t cubie_pitch, const uint8_t *corner, int64_t corner_bytes, int n_edge,
              const int *masks, const uint8_t *const *edge_tables, const int64_t *edge_bytes, uint8_t *path, int max_depth, int64_t path_pitch,
-             const int32_t *floor, const int32_t *limit, uint64_t *trail, uint8_t *cursor, int32_t *depth, int32_t *bound, int32_t *next,
-             uint64_t *nodes, uint8_t *status, IdaArgs &a) {
+             const int32_t *floor, const int32_t *limit, const SearchFrame &fr, IdaArgs &a) {
     const auto bad = [fn](const char *what) { return fail(RC_EINVAL, "%s: %s", fn, what); };
-    if (n < 0) return bad("n is negative");
-    if (!cubies || !aligned16(cubies)) return bad("cubies is NULL or not 16-byte aligned");
-    const int sh = tile_shift(cubie_pitch, n, Cube3::SLOTS);
-    if (sh < 0) return bad("cubie_pitch: need pitch % 16 == 0 and pitch >= n, or a power-of-two tile >= 512");
+    int sh;
+    if (int rc = cubie_arg(fn, cubies, n, cubie_pitch, sh)) return rc;
     IdaTables t{};
     if (corner) {
         if (!aligned16(corner)) return bad("corner_table is not 16-byte aligned");
@@ -320,19 +523,11 @@ int ida_args(const char *fn, const uint8_t *cubies, int64_t n, int64_t cubie_pit
         if (int rc = edge_table_arg(fn, masks[i], edge_tables[i], edge_bytes[i], t.set[i])) return rc;
         t.edge[i] = edge_tables[i];
     }
-    if (!path || !aligned16(path)) return bad("path is NULL or not 16-byte aligned");
-    if (max_depth < 1 || max_depth > kIdaMaxDepth) return bad("max_depth must be in 1..32");
-    if (path_pitch < n || (path_pitch & 15) != 0) return bad("path_pitch: need path_pitch % 16 == 0 and path_pitch >= n");
+    if (int rc = path_arg(fn, path, max_depth, path_pitch, kIdaMaxDepth, n, "n")) return rc;
     if (floor && !aligned16(floor)) return bad("floor is not 16-byte aligned");
     if (!limit || !aligned16(limit)) return bad("limit is NULL or not 16-byte aligned");
-    if (!trail || !aligned16(trail)) return bad("trail is NULL or not 16-byte aligned");
-    if (!cursor || !aligned16(cursor)) return bad("cursor is NULL or not 16-byte aligned");
-    if (!depth || !aligned16(depth)) return bad("depth is NULL or not 16-byte aligned");
-    if (!bound || !aligned16(bound)) return bad("bound is NULL or not 16-byte aligned");
-    if (!next || !aligned16(next)) return bad("next is NULL or not 16-byte aligned");
-    if (!nodes || !aligned16(nodes)) return bad("nodes is NULL or not 16-byte aligned");
-    if (!status || !aligned16(status)) return bad("status is NULL or not 16-byte aligned");
-    a = IdaArgs{cubies, n, cubie_pitch, sh, t, path, max_depth, path_pitch, floor, limit, trail, cursor, depth, bound, next, nodes, status, 0, nullptr};
+    if (int rc = frame_arg(fn, fr)) return rc;
+    a = IdaArgs{cubies, n, cubie_pitch, sh, t, path, max_depth, path_pitch, floor, limit, fr};
     return RC_OK;
 }
 
@@ -357,14 +552,9 @@ int ida_init(const uint8_t *cubies, int64_t n, int64_t cubie_pitch, const uint8_
     RC_NEED_INIT();
     IdaArgs a;
     if (int rc = ida_args("ida_init", cubies, n, cubie_pitch, corner_table, corner_bytes, n_edge, masks, edge_tables, edge_bytes, path, max_depth,
-                          path_pitch, floor, limit, trail, cursor, depth, bound, next, nodes, status, a))
+                          path_pitch, floor, limit, SearchFrame{trail, cursor, depth, bound, next, nodes, status, 0, nullptr}, a))
         return rc;
-    if (n == 0) return RC_OK;
-    const int64_t blocks = ceil_div(n, kWave);
-    RC_GRID(blocks);
-    hipLaunchKernelGGL(k_ida_init, dim3((unsigned)blocks), dim3(kWave), 0, S(stream), a);
-    RC_HIP(RC_EHIP, hipGetLastError());
-    return RC_OK;
+    return ida_launch(k_ida_init, a, S(stream));
 }
 
 int ida_search(const uint8_t *cubies, int64_t n, int64_t cubie_pitch, const uint8_t *corner_table, int64_t corner_bytes, int n_edge,
@@ -374,66 +564,18 @@ int ida_search(const uint8_t *cubies, int64_t n, int64_t cubie_pitch, const uint
     RC_NEED_INIT();
     IdaArgs a;
     if (int rc = ida_args("ida_search", cubies, n, cubie_pitch, corner_table, corner_bytes, n_edge, masks, edge_tables, edge_bytes, path,
-                          max_depth, path_pitch, floor, limit, trail, cursor, depth, bound, next, nodes, status, a))
+                          max_depth, path_pitch, floor, limit, SearchFrame{trail, cursor, depth, bound, next, nodes, status, max_steps, running}, a))
         return rc;
-    if (max_steps < 1 || max_steps > kIdaMaxSteps) return fail(RC_EINVAL, "ida_search: max_steps must be in 1..ida_max_steps()");
-    if (!running || !aligned16(running)) return fail(RC_EINVAL, "ida_search: running is NULL or not 16-byte aligned");
-    if (n == 0) return RC_OK;
-    const int64_t blocks = ceil_div(n, kWave);
-    RC_GRID(blocks);
-    a.max_steps = max_steps;
-    a.running = running;
-    hipLaunchKernelGGL(k_zero32, dim3(1), dim3(1), 0, S(stream), running);
-    RC_HIP(RC_EHIP, hipGetLastError());
-    hipLaunchKernelGGL(k_ida_search, dim3((unsigned)blocks), dim3(kWave), 0, S(stream), a);
-    RC_HIP(RC_EHIP, hipGetLastError());
-    return RC_OK;
+    if (int rc = steps_arg("ida_search", a.fr, kIdaMaxSteps, "ida_max_steps()")) return rc;
+    return ida_launch(k_ida_search, a, S(stream));
 }
 
 }  // extern "C"
 
 // ================================================================================================================== two-phase
-// The tp_* entry points (include/rubikhip.h "Two-phase", DESIGN.md "Two-phase"): Kociemba's two phases on the state machine above.
-//   k_tp1_init / k_tp1_search   phase 1: one lane per cube under max(twist-slice, flip-slice); up to K G1 candidates per cube are
-//                               emitted (path column, length, cubie rows), the search never enters G1
-//   k_tp2_init / k_tp2_search   phase 2: one lane per candidate column under max(corner-slice, edge-slice), stage 2's generators with
-//                               a half turn costing 2; the first goal ends the lane
-// The tables and tp_index are rc_chain.h's TpLevels / k_tp_index.  The cube is an IdaCube; the 13 move rows are extended by the four
-// half turns F2, R2, B2, L2, so a phase-2 generator is one gather.  Both tables are ranked before either is read.
+// Kociemba's two phases as two more policies of the state machine above.  The tables and tp_index are rc_chain.h's TpLevels /
+// k_tp_index.  Both tables of a phase are ranked before either is read.
 namespace {
-
-constexpr int kTpMaxDepth = 48, kTpMaxTrail = 32, kTpRows = 17, kTpMaxK = 4096;
-constexpr int64_t kTpMaxSteps = (int64_t)1 << 17;                           // DESIGN.md "Two-phase": 0.73 | 0.89 s a launch at 2^20 lanes
-
-struct TpMoves {
-    uint32_t w[kTpRows][16];
-    constexpr TpMoves() : w{} {
-        const IdaMoves base{};
-        for (int a = 0; a < 13; ++a)
-            for (int i = 0; i < 16; ++i) w[a][i] = base.w[a][i];
-        const int half[4] = {1, 2, 4, 5};                                  // F2, R2, B2, L2 among stage 3's U2 F2 R2 D2 B2 L2
-        for (int k = 0; k < 4; ++k) {
-            const ChainGen g = chain_gen(3, half[k]);
-            const int a = 13 + k;
-            for (int q = 0; q < 8; ++q) {
-                w[a][q >> 2] |= (uint32_t)g.csrc[q] << (8 * (q & 3));
-                w[a][2 + (q >> 2)] |= ((uint32_t)g.ctw[q] << 4) << (8 * (q & 3));
-            }
-            for (int q = 0; q < 12; ++q) {
-                const uint32_t s = g.esrc[q];
-                w[a][4 + 2 * (q >> 2)] |= (s < 8u ? s : 0x0cu) << (8 * (q & 3));
-                w[a][5 + 2 * (q >> 2)] |= (s < 8u ? 0x0cu : s - 8u) << (8 * (q & 3));
-                w[a][10 + (q >> 2)] |= (uint32_t)g.eflip[q] << (8 * (q & 3));
-            }
-        }
-    }
-};
-__constant__ TpMoves c_tp_moves{};
-
-__device__ __forceinline__ void tp_moves_load(uint32_t (*s_moves)[16]) {
-    for (uint32_t i = threadIdx.x; i < (uint32_t)kTpRows * 16u; i += blockDim.x) s_moves[i >> 4][i & 15u] = c_tp_moves.w[i >> 4][i & 15u];
-    __syncthreads();
-}
 
 // phase 2's generator j in 0..7 = U, U', F2, R2, D, D', B2, L2: its first action, its cost, its row of s_moves and its inverse's
 __device__ __forceinline__ uint32_t tp_gen_action(uint32_t j) { return (0xA8764210u >> (4u * j)) & 15u; }
@@ -510,6 +652,7 @@ __device__ __forceinline__ void tp_store(uint8_t *at, int64_t pitch, const IdaCu
     });
 }
 
+// ----------------------------------------------------------------------------------------------------------------- phase 1
 struct Tp1Args {
     const uint8_t *cubies;
     int64_t n, pitch;
@@ -525,14 +668,8 @@ struct Tp1Args {
     uint8_t *cand;
     int64_t cand_pitch;
     int cand_sh;
-    uint64_t *trail;
-    uint8_t *cursor;
-    int32_t *depth, *bound, *next;
-    uint64_t *nodes;
     int32_t *found;
-    uint8_t *status;
-    int64_t max_steps;
-    uint32_t *running;
+    SearchFrame fr;
 };
 
 __device__ __forceinline__ int32_t tp1_lim(const Tp1Args &a, int64_t c) {
@@ -549,137 +686,83 @@ __device__ __forceinline__ void tp1_emit(const Tp1Args &a, int64_t c, int32_t fo
     tp_store(a.cand + cubie_off(col, a.cand_pitch, a.cand_sh, Cube3::SLOTS), a.cand_pitch, y);
 }
 
+// A G1 child (h == 0) is never entered: it is emitted if it is of this iteration's length and does not end in a U or D turn, and
+// the K-th one ends the lane; so an entered child has h >= 1 and the trail stays below 32
+struct Tp1Search {
+    static constexpr uint32_t NGEN = 12u, NONE = kIdaNoMove;
+    static constexpr bool UNIT = true;
+    __device__ static uint32_t row(uint32_t j) { return j; }
+    __device__ static uint32_t undo(uint32_t j) { return j ^ 1u; }
+    __device__ static int32_t cost(uint32_t) { return 1; }
+    __device__ static uint32_t allowed(const IdaLane &l, int32_t k, uint32_t last) {
+        return ida_allowed(k >= 2 ? ida_nib(l.lo, l.hi, k - 2) : kIdaNoMove, last);
+    }
+    const Tp1Args &a;
+    int64_t c;
+    int32_t found;
+    static constexpr int32_t floor = 0;
+    __device__ uint32_t h(const IdaCube &y, bool live) const { return tp_h1(y, a.t, live); }
+    __device__ static bool enters(uint32_t h) { return h != 0u; }
+    __device__ uint32_t emit(const IdaLane &l, const IdaCube &y, uint32_t m) {
+        if (l.depth + 1 != l.bound || ((0xC3u >> m) & 1u)) return 0u;
+        uint64_t lo = l.lo, hi = l.hi;
+        ida_nib_set(lo, hi, l.depth, m);                                  // depth + 1 <= bound <= 32
+        tp1_emit(a, c, found, y, lo, hi, l.depth + 1);
+        return ++found == a.K ? TP_FULL : 0u;
+    }
+    __device__ static bool goal(const IdaCube &, uint32_t) { return false; }
+};
+
 __global__ void __launch_bounds__(kWave) k_tp1_init(Tp1Args a) {
     const int64_t c = (int64_t)blockIdx.x * kWave + threadIdx.x;
     if (c >= a.n) return;
     IdaCube x;
-    uint32_t status = ida_load(a.cubies + cubie_off(c, a.pitch, a.sh, Cube3::SLOTS), a.pitch, x) ? 0u : TP_ILLEGAL;
-    const uint32_t h = tp_h1(x, a.t, status == 0u);
-    if (!status && h == 0xFFu) status = TP_ILLEGAL;
-    int32_t bound = 0, next = kIdaInf, found = 0;
-    if (!status) {
-        bound = (int32_t)h;
+    IdaLane l;
+    l.status = ida_load(a.cubies + cubie_off(c, a.pitch, a.sh, Cube3::SLOTS), a.pitch, x) ? 0u : TP_ILLEGAL;
+    const uint32_t h = tp_h1(x, a.t, l.status == 0u);
+    if (!l.status && h == 0xFFu) l.status = TP_ILLEGAL;
+    int32_t found = 0;
+    if (!l.status) {
+        first_bound(l, 0, h);
         if (h == 0u) {                                                     // the root is in G1: candidate 0, of length 0
             tp1_emit(a, c, 0, x, 0, 0, 0);
             found = 1;
-            if (found == a.K) status = TP_FULL;
+            if (found == a.K) l.status = TP_FULL;
         }
-        if (!status && bound > tp1_lim(a, c)) {
-            status = TP_EXHAUSTED;
-            next = bound;
-        }
+        if (!l.status) first_over(l, tp1_lim(a, c));
     }
-    a.trail[2 * c] = 0;
-    a.trail[2 * c + 1] = 0;
-    a.cursor[c] = 0;
-    a.depth[c] = 0;
-    a.bound[c] = bound;
-    a.next[c] = next;
-    a.nodes[c] = 0;
+    frame_store(a.fr, c, l);
     a.found[c] = found;
-    a.status[c] = (uint8_t)status;
 }
 
 __global__ void __launch_bounds__(kWave) k_tp1_search(Tp1Args a) {
     __shared__ __attribute__((aligned(16))) uint32_t s_moves[kTpRows][16];
-    tp_moves_load(s_moves);
+    moves_load(s_moves, c_tp_moves.w);
     const int64_t c = (int64_t)blockIdx.x * kWave + threadIdx.x;
-    const bool mine = c < a.n && a.status[c] == 0u;
+    const bool mine = c < a.n && a.fr.status[c] == 0u;
     IdaCube x{};
-    uint64_t lo = 0, hi = 0, nodes = 0;
-    uint32_t status = 0, cursor = 0;
-    int32_t depth = 0, bound = 0, next = kIdaInf, lim = 0, found = 0;
+    IdaLane l;
+    Tp1Search p{a, c, 0};
+    int32_t lim = 0;
     if (mine) {
-        if (!ida_load(a.cubies + cubie_off(c, a.pitch, a.sh, Cube3::SLOTS), a.pitch, x)) status = TP_ILLEGAL;
-        lo = a.trail[2 * c];
-        hi = a.trail[2 * c + 1];
-        cursor = a.cursor[c];
-        depth = a.depth[c];
-        bound = a.bound[c];
-        next = a.next[c];
-        nodes = a.nodes[c];
-        found = a.found[c];
+        // the cube before the frame: the frame's registers live across the 20 byte loads would cost a wave per SIMD (80 VGPRs, not 59)
+        const bool legal = ida_load(a.cubies + cubie_off(c, a.pitch, a.sh, Cube3::SLOTS), a.pitch, x);
+        l = frame_load(a.fr, c);
+        if (!legal) l.status = TP_ILLEGAL;
+        p.found = a.found[c];
         lim = tp1_lim(a, c);
-        if (depth < 0 || depth >= kTpMaxTrail || cursor > kIdaNoMove || bound > lim || depth > bound || found < 0 || found >= a.K)
-            status |= TP_BAD_FRAME;
+        if (l.depth < 0 || l.depth >= kTpMaxTrail || l.cursor > kIdaNoMove || l.bound > lim || l.depth > l.bound || p.found < 0 || p.found >= a.K)
+            l.status |= TP_BAD_FRAME;
     }
-    for (int r = 0; r < kTpMaxTrail; ++r) {
-        uint32_t m = kIdaNoMove;
-        if (mine && !status && r < depth) {
-            m = ida_nib(lo, hi, r);
-            if (m >= kIdaNoMove) {
-                status |= TP_BAD_FRAME;
-                m = kIdaNoMove;
-            }
-        }
-        x = ida_move(x, s_moves[m]);
-    }
-    bool run = mine && !status;
-    for (int64_t step = 0; step < a.max_steps; ++step) {                  // the only loop: whatever the tables hold, it ends
-        if (__ballot(run) == 0ull) break;
-        if (run) {
-            const int g = depth;
-            const uint32_t p1 = g >= 1 ? ida_nib(lo, hi, g - 1) : kIdaNoMove, p2 = g >= 2 ? ida_nib(lo, hi, g - 2) : kIdaNoMove;
-            const uint32_t open = ida_allowed(p2, p1) & (0xFFFu << cursor) & 0xFFFu;
-            const bool gen = open != 0u, back = !gen && g > 0;
-            const uint32_t m = gen ? (uint32_t)__ffs((int)open) - 1u : kIdaNoMove;
-            const IdaCube y = ida_move(x, s_moves[gen ? m : back ? (p1 ^ 1u) : kIdaNoMove]);
-            const uint32_t h = tp_h1(y, a.t, gen);
-            if (gen) {
-                ++nodes;
-                const int32_t fv = g + 1 + (int32_t)h;
-                if (h == 0xFFu) {
-                    status = TP_ILLEGAL;
-                    run = false;
-                } else if (fv > bound) {
-                    next = fv < next ? fv : next;
-                    cursor = m + 1u;
-                } else if (h == 0u) {                                     // a G1 child is never entered
-                    cursor = m + 1u;
-                    if (g + 1 == bound && !((0xC3u >> m) & 1u)) {         // of this iteration's length, and not ending in a U or D turn
-                        uint64_t tlo = lo, thi = hi;
-                        ida_nib_set(tlo, thi, g, m);                      // g + 1 <= bound <= 32
-                        tp1_emit(a, c, found, y, tlo, thi, g + 1);
-                        if (++found == a.K) {
-                            status = TP_FULL;
-                            run = false;
-                        }
-                    }
-                } else {                                                  // fv <= bound and h >= 1: g + 1 < 32
-                    x = y;
-                    ida_nib_set(lo, hi, g, m);
-                    depth = g + 1;
-                    cursor = 0;
-                }
-            } else if (back) {
-                x = y;
-                cursor = p1 + 1u;
-                depth = g - 1;
-            } else if (next > lim) {
-                status = TP_EXHAUSTED;
-                run = false;
-            } else {
-                bound = next;
-                next = kIdaInf;
-                cursor = 0;
-            }
-        }
-    }
+    ida_replay<Tp1Search>(s_moves, x, l, mine, 0);
+    ida_passes(p, s_moves, a.fr, x, l, lim, mine && !l.status);
     if (mine) {
-        a.trail[2 * c] = lo;
-        a.trail[2 * c + 1] = hi;
-        a.cursor[c] = (uint8_t)cursor;
-        a.depth[c] = depth;
-        a.bound[c] = bound;
-        a.next[c] = next;
-        a.nodes[c] = nodes;
-        a.found[c] = found;
-        a.status[c] = (uint8_t)status;
+        frame_store(a.fr, c, l);
+        a.found[c] = p.found;
     }
-    const unsigned long long bal = __ballot(run);
-    if (threadIdx.x == 0 && bal) atomicAdd(a.running, (uint32_t)__popcll(bal));
 }
 
+// ----------------------------------------------------------------------------------------------------------------- phase 2
 struct Tp2Args {
     const uint8_t *cubies;
     int64_t n, pitch;
@@ -689,13 +772,7 @@ struct Tp2Args {
     int32_t max_depth;
     int64_t path_pitch;
     const int32_t *floor, *limit;
-    uint64_t *trail;
-    uint8_t *cursor;
-    int32_t *depth, *bound, *next;
-    uint64_t *nodes;
-    uint8_t *status;
-    int64_t max_steps;
-    uint32_t *running;
+    SearchFrame fr;
 };
 
 // min(limit, max_depth, floor + 32): the trail holds 32 generators
@@ -713,154 +790,89 @@ __device__ __forceinline__ bool tp2_prefix(const Tp2Args &a, int64_t c, int32_t 
     return (f < 1 || pre1 < kIdaNoMove) && (f < 2 || pre2 < kIdaNoMove);
 }
 
+// The trail holds generators, depth their cost beyond the floor's; the canonical rule is ida_allowed on the last two ACTIONS that the
+// prefix and the trail spell.  Every admissible child is entered; h == 0 ends the lane
+struct Tp2Search {
+    static constexpr uint32_t NGEN = 8u, NONE = 0u;
+    static constexpr bool UNIT = false;
+    const TpTables &t;
+    uint32_t pre1, pre2;
+    static constexpr int32_t floor = 0;
+    __device__ static uint32_t row(uint32_t j) { return tp_gen_row(j); }
+    __device__ static uint32_t undo(uint32_t j) { return tp_gen_back(j); }
+    __device__ static int32_t cost(uint32_t j) { return 1 + (int32_t)tp_gen_half(j); }
+    __device__ uint32_t allowed(const IdaLane &l, int32_t k, uint32_t last) const {
+        uint32_t p1 = pre1, p2 = pre2;
+        if (k >= 1) {
+            p1 = tp_gen_action(last);
+            p2 = tp_gen_half(last) ? p1 : k >= 2 ? tp_gen_action(ida_nib(l.lo, l.hi, k - 2)) : pre1;
+        }
+        return tp_gen_allowed(ida_allowed(p2, p1));
+    }
+    __device__ uint32_t h(const IdaCube &y, bool live) const { return tp_h2(y, t, live); }
+    __device__ static bool enters(uint32_t) { return true; }
+    __device__ static uint32_t emit(const IdaLane &, const IdaCube &, uint32_t) { return 0u; }
+    __device__ static bool goal(const IdaCube &, uint32_t h) { return h == 0u; }
+};
+
 __global__ void __launch_bounds__(kWave) k_tp2_init(Tp2Args a) {
     const int64_t c = (int64_t)blockIdx.x * kWave + threadIdx.x;
     if (c >= a.n) return;
     IdaCube x;
-    uint32_t status = ida_load(a.cubies + cubie_off(c, a.pitch, a.sh, Cube3::SLOTS), a.pitch, x) ? 0u : TP_ILLEGAL;
+    IdaLane l;
+    l.status = ida_load(a.cubies + cubie_off(c, a.pitch, a.sh, Cube3::SLOTS), a.pitch, x) ? 0u : TP_ILLEGAL;
     const int32_t f = a.floor ? a.floor[c] : 0;
     uint32_t pre1, pre2;
-    if (!tp2_prefix(a, c, f, pre1, pre2)) status |= TP_BAD_FRAME;
-    if (!status && !tp_in_g1(x)) status = TP_OUTSIDE;
-    const uint32_t h = tp_h2(x, a.t, status == 0u);
-    if (!status && h == 0xFFu) status = TP_ILLEGAL;
-    int32_t depth = 0, bound = 0, next = kIdaInf;
-    if (!status) {
-        depth = f;
-        bound = f + (int32_t)h;
-        if (bound > tp2_lim(a, c, f)) {                                    // before the goal test: an empty slot is skipped here
-            status = TP_EXHAUSTED;
-            next = bound;
-        } else if (h == 0u) {
-            status = TP_SOLVED;
-        }
+    if (!tp2_prefix(a, c, f, pre1, pre2)) l.status |= TP_BAD_FRAME;
+    if (!l.status && !tp_in_g1(x)) l.status = TP_OUTSIDE;
+    const uint32_t h = tp_h2(x, a.t, l.status == 0u);
+    if (!l.status && h == 0xFFu) l.status = TP_ILLEGAL;
+    if (!l.status) {
+        first_bound(l, f, h);
+        if (!first_over(l, tp2_lim(a, c, f)) && h == 0u) l.status = TP_SOLVED;   // the limit before the goal: an empty slot is skipped here
     }
-    a.trail[2 * c] = 0;
-    a.trail[2 * c + 1] = 0;
-    a.cursor[c] = 0;
-    a.depth[c] = depth;
-    a.bound[c] = bound;
-    a.next[c] = next;
-    a.nodes[c] = 0;
-    a.status[c] = (uint8_t)status;
+    frame_store(a.fr, c, l);
 }
 
 __global__ void __launch_bounds__(kWave) k_tp2_search(Tp2Args a) {
     __shared__ __attribute__((aligned(16))) uint32_t s_moves[kTpRows][16];
-    tp_moves_load(s_moves);
+    moves_load(s_moves, c_tp_moves.w);
     const int64_t c = (int64_t)blockIdx.x * kWave + threadIdx.x;
-    const bool mine = c < a.n && a.status[c] == 0u;
+    const bool mine = c < a.n && a.fr.status[c] == 0u;
     IdaCube x{};
-    uint64_t lo = 0, hi = 0, nodes = 0;
-    uint32_t status = 0, cursor = 0, pre1 = kIdaNoMove, pre2 = kIdaNoMove;
-    int32_t f = 0, g = 0, k = 0, bound = 0, next = kIdaInf, lim = 0;
+    IdaLane l;
+    Tp2Search p{a.t, kIdaNoMove, kIdaNoMove};
+    int32_t f = 0, lim = 0;
     if (mine) {
-        if (!ida_load(a.cubies + cubie_off(c, a.pitch, a.sh, Cube3::SLOTS), a.pitch, x)) status = TP_ILLEGAL;
+        uint32_t status = ida_load(a.cubies + cubie_off(c, a.pitch, a.sh, Cube3::SLOTS), a.pitch, x) ? 0u : TP_ILLEGAL;
         f = a.floor ? a.floor[c] : 0;
-        if (!tp2_prefix(a, c, f, pre1, pre2)) {
+        if (!tp2_prefix(a, c, f, p.pre1, p.pre2)) {
             status |= TP_BAD_FRAME;
             f = 0;
         }
         if (!status && !tp_in_g1(x)) status = TP_OUTSIDE;
-        lo = a.trail[2 * c];
-        hi = a.trail[2 * c + 1];
-        cursor = a.cursor[c];
-        g = a.depth[c];
-        bound = a.bound[c];
-        next = a.next[c];
-        nodes = a.nodes[c];
+        l = frame_load(a.fr, c);                                           // after the cube, as in phase 1: 53 VGPRs, not 71
+        l.status = status;
         lim = tp2_lim(a, c, f);
-        if (g < f || g > a.max_depth || g > bound || cursor > 8u || bound > lim) status |= TP_BAD_FRAME;
+        if (l.depth < f || l.depth > a.max_depth || l.depth > l.bound || l.cursor > 8u || l.bound > lim) l.status |= TP_BAD_FRAME;
     }
-    int32_t sum = f;
-    for (int r = 0; r < kTpMaxTrail; ++r) {                                // the current node: generators until their costs reach g
-        uint32_t row = kIdaNoMove;
-        if (mine && !status && sum < g) {
-            const uint32_t j = ida_nib(lo, hi, r);
-            if (j >= 8u) {
-                status |= TP_BAD_FRAME;
-            } else {
-                row = tp_gen_row(j);
-                sum += 1 + (int32_t)tp_gen_half(j);
-                ++k;
-            }
-        }
-        x = ida_move(x, s_moves[row]);
-    }
-    if (mine && !status && sum != g) status |= TP_BAD_FRAME;
-    bool run = mine && !status;
-    for (int64_t step = 0; step < a.max_steps; ++step) {                  // the only loop
-        if (__ballot(run) == 0ull) break;
-        if (run) {
-            const uint32_t j1 = k >= 1 ? ida_nib(lo, hi, k - 1) : 0u;
-            uint32_t p1 = pre1, p2 = pre2;                                // the last two ACTIONS of prefix + generators
-            if (k >= 1) {
-                p1 = tp_gen_action(j1);
-                p2 = tp_gen_half(j1) ? p1 : k >= 2 ? tp_gen_action(ida_nib(lo, hi, k - 2)) : pre1;
-            }
-            const uint32_t open = tp_gen_allowed(ida_allowed(p2, p1)) & (0xFFu << cursor) & 0xFFu;
-            const bool gen = open != 0u, back = !gen && k > 0;
-            const uint32_t j = gen ? (uint32_t)__ffs((int)open) - 1u : 8u;
-            const IdaCube y = ida_move(x, s_moves[gen ? tp_gen_row(j) : back ? tp_gen_back(j1) : kIdaNoMove]);
-            const uint32_t h = tp_h2(y, a.t, gen);
-            if (gen) {
-                ++nodes;
-                const int32_t w = 1 + (int32_t)tp_gen_half(j), fv = g + w + (int32_t)h;
-                if (h == 0xFFu) {
-                    status = TP_ILLEGAL;
-                    run = false;
-                } else if (fv > bound) {
-                    next = fv < next ? fv : next;
-                    cursor = j + 1u;
-                } else {                                                  // fv <= bound <= floor + 32: k < 32
-                    x = y;
-                    ida_nib_set(lo, hi, k, j);
-                    ++k;
-                    g += w;
-                    cursor = 0;
-                    if (h == 0u) {
-                        status = TP_SOLVED;
-                        run = false;
-                    }
-                }
-            } else if (back) {
-                x = y;
-                cursor = j1 + 1u;
-                --k;
-                g -= 1 + (int32_t)tp_gen_half(j1);
-            } else if (next > lim) {
-                status = TP_EXHAUSTED;
-                run = false;
-            } else {
-                bound = next;
-                next = kIdaInf;
-                cursor = 0;
-            }
-        }
-    }
+    ida_replay<Tp2Search>(s_moves, x, l, mine, f);
+    ida_passes(p, s_moves, a.fr, x, l, lim, mine && !l.status);
     if (mine) {
-        a.trail[2 * c] = lo;
-        a.trail[2 * c + 1] = hi;
-        a.cursor[c] = (uint8_t)cursor;
-        a.depth[c] = g;
-        a.bound[c] = bound;
-        a.next[c] = next;
-        a.nodes[c] = nodes;
-        a.status[c] = (uint8_t)status;
-        if (status == TP_SOLVED) {
+        frame_store(a.fr, c, l);
+        if (l.status == TP_SOLVED) {
             int32_t r = f;
             for (int i = 0; i < kTpMaxTrail; ++i)
-                if (i < k) {
-                    const uint32_t j = ida_nib(lo, hi, i), act = tp_gen_action(j);
+                if (i < l.k) {
+                    const uint32_t j = ida_nib(l.lo, l.hi, i), act = tp_gen_action(j);
                     for (uint32_t t = 0; t <= tp_gen_half(j); ++t)
-                        if (r < a.max_depth) a.path[(int64_t)r++ * a.path_pitch + c] = (uint8_t)act;   // r < g <= max_depth; the guard stays
+                        if (r < a.max_depth) a.path[(int64_t)r++ * a.path_pitch + c] = (uint8_t)act;   // r < depth <= max_depth; the guard stays
                 }
         }
     }
-    const unsigned long long bal = __ballot(run);
-    if (threadIdx.x == 0 && bal) atomicAdd(a.running, (uint32_t)__popcll(bal));
 }
 
+// ------------------------------------------------------------------------------------------------------------------- host
 int tp_which_arg(const char *fn, int which) {
     return which < 0 || which > 3 ? fail(RC_EINVAL, "%s: which must be in 0..3", fn) : RC_OK;
 }
@@ -877,13 +889,10 @@ int tp_tables_arg(const char *fn, int phase, const uint8_t *ta, int64_t bytes_a,
 
 int tp1_args(const char *fn, const uint8_t *cubies, int64_t n, int64_t cubie_pitch, const uint8_t *ta, int64_t bytes_a, const uint8_t *tb,
              int64_t bytes_b, const int32_t *limit, int K, int64_t stride, uint8_t *path, int max_depth, int64_t path_pitch,
-             int32_t *cand_length, uint8_t *cand, int64_t cand_pitch, uint64_t *trail, uint8_t *cursor, int32_t *depth, int32_t *bound,
-             int32_t *next, uint64_t *nodes, int32_t *found, uint8_t *status, Tp1Args &a) {
+             int32_t *cand_length, uint8_t *cand, int64_t cand_pitch, int32_t *found, const SearchFrame &fr, Tp1Args &a) {
     const auto bad = [fn](const char *what) { return fail(RC_EINVAL, "%s: %s", fn, what); };
-    if (n < 0) return bad("n is negative");
-    if (!cubies || !aligned16(cubies)) return bad("cubies is NULL or not 16-byte aligned");
-    const int sh = tile_shift(cubie_pitch, n, Cube3::SLOTS);
-    if (sh < 0) return bad("cubie_pitch: need pitch % 16 == 0 and pitch >= n, or a power-of-two tile >= 512");
+    int sh;
+    if (int rc = cubie_arg(fn, cubies, n, cubie_pitch, sh)) return rc;
     TpTables t{};
     if (int rc = tp_tables_arg(fn, 1, ta, bytes_a, tb, bytes_b, t)) return rc;
     if (!limit || !aligned16(limit)) return bad("limit is NULL or not 16-byte aligned");
@@ -891,49 +900,29 @@ int tp1_args(const char *fn, const uint8_t *cubies, int64_t n, int64_t cubie_pit
     if (stride < n || stride < 16 || (stride & 15) != 0 || stride > ((int64_t)1 << 31) / K)
         return bad("stride: need stride % 16 == 0, stride >= max(n, 16) and candidates * stride <= 2^31");
     const int64_t cols = (int64_t)K * stride;
-    if (!path || !aligned16(path)) return bad("path is NULL or not 16-byte aligned");
-    if (max_depth < 1 || max_depth > kTpMaxDepth) return bad("max_depth must be in 1..48");
-    if (path_pitch < cols || (path_pitch & 15) != 0) return bad("path_pitch: need path_pitch % 16 == 0 and path_pitch >= candidates * stride");
+    if (int rc = path_arg(fn, path, max_depth, path_pitch, kTpMaxDepth, cols, "candidates * stride")) return rc;
     if (!cand_length || !aligned16(cand_length)) return bad("cand_length is NULL or not 16-byte aligned");
     if (!cand || !aligned16(cand)) return bad("cand_cubies is NULL or not 16-byte aligned");
     const int cand_sh = tile_shift(cand_pitch, cols, Cube3::SLOTS);
     if (cand_sh < 0) return bad("cand_pitch: need pitch % 16 == 0 and pitch >= candidates * stride, or a power-of-two tile >= 512");
-    if (!trail || !aligned16(trail)) return bad("trail is NULL or not 16-byte aligned");
-    if (!cursor || !aligned16(cursor)) return bad("cursor is NULL or not 16-byte aligned");
-    if (!depth || !aligned16(depth)) return bad("depth is NULL or not 16-byte aligned");
-    if (!bound || !aligned16(bound)) return bad("bound is NULL or not 16-byte aligned");
-    if (!next || !aligned16(next)) return bad("next is NULL or not 16-byte aligned");
-    if (!nodes || !aligned16(nodes)) return bad("nodes is NULL or not 16-byte aligned");
-    if (!found || !aligned16(found)) return bad("found is NULL or not 16-byte aligned");
-    if (!status || !aligned16(status)) return bad("status is NULL or not 16-byte aligned");
-    a = Tp1Args{cubies, n, cubie_pitch, sh, t, limit, K, stride, path, max_depth, path_pitch, cand_length, cand, cand_pitch, cand_sh,
-                trail, cursor, depth, bound, next, nodes, found, status, 0, nullptr};
+    if (int rc = frame_arg(fn, fr, &found)) return rc;
+    a = Tp1Args{cubies, n, cubie_pitch, sh, t, limit, K, stride, path, max_depth, path_pitch, cand_length, cand, cand_pitch, cand_sh, found, fr};
     return RC_OK;
 }
 
 int tp2_args(const char *fn, const uint8_t *cubies, int64_t n, int64_t cubie_pitch, const uint8_t *ta, int64_t bytes_a, const uint8_t *tb,
-             int64_t bytes_b, uint8_t *path, int max_depth, int64_t path_pitch, const int32_t *floor, const int32_t *limit, uint64_t *trail,
-             uint8_t *cursor, int32_t *depth, int32_t *bound, int32_t *next, uint64_t *nodes, uint8_t *status, Tp2Args &a) {
+             int64_t bytes_b, uint8_t *path, int max_depth, int64_t path_pitch, const int32_t *floor, const int32_t *limit,
+             const SearchFrame &fr, Tp2Args &a) {
     const auto bad = [fn](const char *what) { return fail(RC_EINVAL, "%s: %s", fn, what); };
-    if (n < 0) return bad("n is negative");
-    if (!cubies || !aligned16(cubies)) return bad("cubies is NULL or not 16-byte aligned");
-    const int sh = tile_shift(cubie_pitch, n, Cube3::SLOTS);
-    if (sh < 0) return bad("cubie_pitch: need pitch % 16 == 0 and pitch >= n, or a power-of-two tile >= 512");
+    int sh;
+    if (int rc = cubie_arg(fn, cubies, n, cubie_pitch, sh)) return rc;
     TpTables t{};
     if (int rc = tp_tables_arg(fn, 2, ta, bytes_a, tb, bytes_b, t)) return rc;
-    if (!path || !aligned16(path)) return bad("path is NULL or not 16-byte aligned");
-    if (max_depth < 1 || max_depth > kTpMaxDepth) return bad("max_depth must be in 1..48");
-    if (path_pitch < n || (path_pitch & 15) != 0) return bad("path_pitch: need path_pitch % 16 == 0 and path_pitch >= n");
+    if (int rc = path_arg(fn, path, max_depth, path_pitch, kTpMaxDepth, n, "n")) return rc;
     if (floor && !aligned16(floor)) return bad("floor is not 16-byte aligned");
     if (!limit || !aligned16(limit)) return bad("limit is NULL or not 16-byte aligned");
-    if (!trail || !aligned16(trail)) return bad("trail is NULL or not 16-byte aligned");
-    if (!cursor || !aligned16(cursor)) return bad("cursor is NULL or not 16-byte aligned");
-    if (!depth || !aligned16(depth)) return bad("depth is NULL or not 16-byte aligned");
-    if (!bound || !aligned16(bound)) return bad("bound is NULL or not 16-byte aligned");
-    if (!next || !aligned16(next)) return bad("next is NULL or not 16-byte aligned");
-    if (!nodes || !aligned16(nodes)) return bad("nodes is NULL or not 16-byte aligned");
-    if (!status || !aligned16(status)) return bad("status is NULL or not 16-byte aligned");
-    a = Tp2Args{cubies, n, cubie_pitch, sh, t, path, max_depth, path_pitch, floor, limit, trail, cursor, depth, bound, next, nodes, status, 0, nullptr};
+    if (int rc = frame_arg(fn, fr)) return rc;
+    a = Tp2Args{cubies, n, cubie_pitch, sh, t, path, max_depth, path_pitch, floor, limit, fr};
     return RC_OK;
 }
 
@@ -945,27 +934,6 @@ int by_which(int which, F &&f) {
     case 2: return f(std::integral_constant<int, 2>{});
     default: return f(std::integral_constant<int, 3>{});
     }
-}
-
-template <class Args, class Kernel>
-int tp_launch(Kernel kernel, Args &a, int64_t max_steps, uint32_t *running, hipStream_t st) {
-    const int64_t blocks = ceil_div(a.n, kWave);
-    RC_GRID(blocks);
-    if (running) {
-        a.max_steps = max_steps;
-        a.running = running;
-        hipLaunchKernelGGL(k_zero32, dim3(1), dim3(1), 0, st, running);
-        RC_HIP(RC_EHIP, hipGetLastError());
-    }
-    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(kWave), 0, st, a);
-    RC_HIP(RC_EHIP, hipGetLastError());
-    return RC_OK;
-}
-
-int tp_steps_arg(const char *fn, int64_t max_steps, const uint32_t *running) {
-    if (max_steps < 1 || max_steps > kTpMaxSteps) return fail(RC_EINVAL, "%s: max_steps must be in 1..tp_max_steps()", fn);
-    if (!running || !aligned16(running)) return fail(RC_EINVAL, "%s: running is NULL or not 16-byte aligned", fn);
-    return RC_OK;
 }
 
 }  // namespace
@@ -1014,13 +982,10 @@ int tp_build_level(uint8_t *table, int64_t bytes, int which, int depth, uint32_t
 
 int tp_index(const uint8_t *cubies, int64_t n, int64_t cubie_pitch, int which, uint32_t *index, void *stream) {
     RC_NEED_INIT();
-    const auto bad = [](const char *what) { return fail(RC_EINVAL, "tp_index: %s", what); };
     if (int rc = tp_which_arg("tp_index", which)) return rc;
-    if (n < 0) return bad("n is negative");
-    if (!cubies || !aligned16(cubies)) return bad("cubies is NULL or not 16-byte aligned");
-    const int sh = tile_shift(cubie_pitch, n, Cube3::SLOTS);
-    if (sh < 0) return bad("cubie_pitch: need pitch % 16 == 0 and pitch >= n, or a power-of-two tile >= 512");
-    if (!index || !aligned16(index)) return bad("index is NULL or not 16-byte aligned");
+    int sh;
+    if (int rc = cubie_arg("tp_index", cubies, n, cubie_pitch, sh)) return rc;
+    if (!index || !aligned16(index)) return fail(RC_EINVAL, "tp_index: index is NULL or not 16-byte aligned");
     if (n == 0) return RC_OK;
     const int64_t blocks = ceil_div(n, 256);
     RC_GRID(blocks);
@@ -1038,10 +1003,10 @@ int tp_phase1_init(const uint8_t *cubies, int64_t n, int64_t cubie_pitch, const 
     RC_NEED_INIT();
     Tp1Args a;
     if (int rc = tp1_args("tp_phase1_init", cubies, n, cubie_pitch, table_a, bytes_a, table_b, bytes_b, limit, candidates, stride, path, max_depth,
-                          path_pitch, cand_length, cand_cubies, cand_pitch, trail, cursor, depth, bound, next, nodes, found, status, a))
+                          path_pitch, cand_length, cand_cubies, cand_pitch, found,
+                          SearchFrame{trail, cursor, depth, bound, next, nodes, status, 0, nullptr}, a))
         return rc;
-    if (n == 0) return RC_OK;
-    return tp_launch(k_tp1_init, a, 0, nullptr, S(stream));
+    return ida_launch(k_tp1_init, a, S(stream));
 }
 
 int tp_phase1_search(const uint8_t *cubies, int64_t n, int64_t cubie_pitch, const uint8_t *table_a, int64_t bytes_a, const uint8_t *table_b,
@@ -1052,11 +1017,11 @@ int tp_phase1_search(const uint8_t *cubies, int64_t n, int64_t cubie_pitch, cons
     RC_NEED_INIT();
     Tp1Args a;
     if (int rc = tp1_args("tp_phase1_search", cubies, n, cubie_pitch, table_a, bytes_a, table_b, bytes_b, limit, candidates, stride, path,
-                          max_depth, path_pitch, cand_length, cand_cubies, cand_pitch, trail, cursor, depth, bound, next, nodes, found, status, a))
+                          max_depth, path_pitch, cand_length, cand_cubies, cand_pitch, found,
+                          SearchFrame{trail, cursor, depth, bound, next, nodes, status, max_steps, running}, a))
         return rc;
-    if (int rc = tp_steps_arg("tp_phase1_search", max_steps, running)) return rc;
-    if (n == 0) return RC_OK;
-    return tp_launch(k_tp1_search, a, max_steps, running, S(stream));
+    if (int rc = steps_arg("tp_phase1_search", a.fr, kTpMaxSteps, "tp_max_steps()")) return rc;
+    return ida_launch(k_tp1_search, a, S(stream));
 }
 
 int tp_phase2_init(const uint8_t *cubies, int64_t n, int64_t cubie_pitch, const uint8_t *table_a, int64_t bytes_a, const uint8_t *table_b,
@@ -1066,10 +1031,9 @@ int tp_phase2_init(const uint8_t *cubies, int64_t n, int64_t cubie_pitch, const 
     RC_NEED_INIT();
     Tp2Args a;
     if (int rc = tp2_args("tp_phase2_init", cubies, n, cubie_pitch, table_a, bytes_a, table_b, bytes_b, path, max_depth, path_pitch, floor, limit,
-                          trail, cursor, depth, bound, next, nodes, status, a))
+                          SearchFrame{trail, cursor, depth, bound, next, nodes, status, 0, nullptr}, a))
         return rc;
-    if (n == 0) return RC_OK;
-    return tp_launch(k_tp2_init, a, 0, nullptr, S(stream));
+    return ida_launch(k_tp2_init, a, S(stream));
 }
 
 int tp_phase2_search(const uint8_t *cubies, int64_t n, int64_t cubie_pitch, const uint8_t *table_a, int64_t bytes_a, const uint8_t *table_b,
@@ -1079,11 +1043,10 @@ int tp_phase2_search(const uint8_t *cubies, int64_t n, int64_t cubie_pitch, cons
     RC_NEED_INIT();
     Tp2Args a;
     if (int rc = tp2_args("tp_phase2_search", cubies, n, cubie_pitch, table_a, bytes_a, table_b, bytes_b, path, max_depth, path_pitch, floor,
-                          limit, trail, cursor, depth, bound, next, nodes, status, a))
+                          limit, SearchFrame{trail, cursor, depth, bound, next, nodes, status, max_steps, running}, a))
         return rc;
-    if (int rc = tp_steps_arg("tp_phase2_search", max_steps, running)) return rc;
-    if (n == 0) return RC_OK;
-    return tp_launch(k_tp2_search, a, max_steps, running, S(stream));
+    if (int rc = steps_arg("tp_phase2_search", a.fr, kTpMaxSteps, "tp_max_steps()")) return rc;
+    return ida_launch(k_tp2_search, a, S(stream));
 }
 
 }  // extern "C"

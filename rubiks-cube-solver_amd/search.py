@@ -603,46 +603,60 @@ def _ida_members(table):
     return corner, tuple(edges), table.device
 
 
-class IdaFrame:
-    """The caller-owned frame of n cubes (include/rubikhip.h "Iterative-deepening A*") and the two launching calls on it.  cubies: a
-    tiled cubie buffer of n cubes with pitch p_c; prefix: None or uint8 [k, n], written into path's first k rows with floor = k."""
+def _is_int(v):
+    return isinstance(v, int) and not isinstance(v, bool)
 
-    def __init__(self, table, cubies, n, p_c, max_depth, limit, prefix=None):
-        from ctypes import c_int, c_int64, c_void_p
-        from . import _ida_lib
-        corner, edges, _ = _ida_members(table)
-        dev = cubies.device
-        self.n, self.dev, self.max_depth, self.L = n, dev, int(max_depth), _ida_lib.ida_lib()
-        pitch = _lib.pitch_for(max(n, 1), 16)
-        vec = lambda dtype, rows=1: torch.zeros((rows, pitch), dtype=dtype, device=dev)
-        self.path = torch.full((self.max_depth, pitch), _ida_lib.NOOP, dtype=torch.uint8, device=dev)
-        self.floor = None
-        if prefix is not None and prefix.shape[0]:
-            self.path[:prefix.shape[0], :n] = prefix
-            self.floor = torch.full((pitch,), prefix.shape[0], dtype=torch.int32, device=dev)
-        self.limit = vec(torch.int32)[0]
-        self.limit[:n] = limit
+
+def _steps_args(max_steps, steps_per_call, cap, cap_name):
+    """The two budgets of a depth-first search checked -> steps_per_call (None: the cap, `cap_name`() of the library)."""
+    if not _is_int(max_steps) or max_steps < 1:
+        raise ValueError(f"max_steps must be a positive integer, got {max_steps!r}")
+    if steps_per_call is None:
+        steps_per_call = cap
+    if not _is_int(steps_per_call) or not 1 <= steps_per_call <= cap:
+        raise ValueError(f"steps_per_call must be an integer in 1..{cap_name}() = {cap}, got {steps_per_call!r}")
+    return steps_per_call
+
+
+def _cube3_env(env, who):
+    if not hasattr(env, "stickers") or env.cube_size != 3:
+        raise ValueError(f"{who} needs a 3x3x3 VecCubeEnv, got {'a ' + str(env.cube_size) + 'x' + str(env.cube_size) + 'x' + str(env.cube_size) + ' one' if hasattr(env, 'cube_size') else type(env).__name__}")
+
+
+def _cube3_cubies(env, who, dev=None):
+    """The prologue of the depth-first solvers, after their argument checks (_cube3_env is the first of them): the env is on `dev`
+    (None: anywhere) -> (its cubie rows from rcc_cubies, their pitch, uint8 [>= N] nonzero where the stickers are no cube)."""
+    if dev is not None and env.stickers.device != dev:
+        raise ValueError(f"the tables are on {dev}, the cubes on {env.stickers.device}")
+    n, dev = env.num_envs, env.stickers.device
+    _lib.init(dev)
+    cub = ops.alloc_code(n, 3, dev, env.stickers.shape[-1])
+    legal = torch.empty(_lib.pitch_for(n, 16), dtype=torch.uint8, device=dev)
+    ops.cubies(env.stickers, n, 3, cubies=cub, status=legal)
+    return cub, ops._state_arg(cub, 20, n, None, f"{who} cubies"), legal
+
+
+class _DepthFirstFrame:
+    """What the caller-owned frames of the depth-first searches share (include/rubikhip.h "Iterative-deepening A*", "Two-phase"): the
+    per-lane fields, the `running` word and the loop over the launching call.  A subclass names its two exports and sets L and _args."""
+    INIT = SEARCH = None
+
+    def _alloc(self, pitch, dev):
+        vec = lambda dtype: torch.zeros(pitch, dtype=dtype, device=dev)
         self.trail = torch.zeros((pitch, 2), dtype=torch.int64, device=dev)
-        self.cursor, self.status = vec(torch.uint8)[0], vec(torch.uint8)[0]
-        self.depth, self.bound, self.next = vec(torch.int32)[0], vec(torch.int32)[0], vec(torch.int32)[0]
-        self.nodes = vec(torch.int64)[0]
+        self.cursor, self.status = vec(torch.uint8), vec(torch.uint8)
+        self.depth, self.bound, self.next = vec(torch.int32), vec(torch.int32), vec(torch.int32)
+        self.nodes = vec(torch.int64)
         self.running = torch.zeros(4, dtype=torch.int32, device=dev)       # one uint32, 16-byte aligned
-        k = len(edges)
-        self._keep = (corner, edges, cubies)
-        self._args = (ptr(cubies), n, p_c, ptr(corner.table) if corner is not None else None, corner.table.numel() if corner is not None else 0, k,
-                      (c_int * max(k, 1))(*[e.mask for e in edges]), (c_void_p * max(k, 1))(*[ptr(e.table) for e in edges]),
-                      (c_int64 * max(k, 1))(*[e.table.numel() for e in edges]), ptr(self.path), self.max_depth, pitch,
-                      ptr(self.floor) if self.floor is not None else None, ptr(self.limit), ptr(self.trail), ptr(self.cursor), ptr(self.depth),
-                      ptr(self.bound), ptr(self.next), ptr(self.nodes), ptr(self.status))
 
     def init(self):
-        _lib.check(self.L.ida_init(*self._args, stream_ptr(self.dev)))
+        _lib.check(getattr(self.L, self.INIT)(*self._args, stream_ptr(self.dev)))
 
     def search(self, steps):
-        _lib.check(self.L.ida_search(*self._args, int(steps), ptr(self.running), stream_ptr(self.dev)))
+        _lib.check(getattr(self.L, self.SEARCH)(*self._args, int(steps), ptr(self.running), stream_ptr(self.dev)))
 
     def run(self, max_steps, steps_per_call):
-        """ida_search until no cube runs or max_steps passes per cube are spent; one read-back per call."""
+        """search() until no lane runs or max_steps passes per lane are spent; one read-back per call."""
         spent = 0
         while spent < max_steps:
             k = min(steps_per_call, max_steps - spent)
@@ -651,6 +665,35 @@ class IdaFrame:
             if int(self.running[0]) == 0:
                 break
         return spent
+
+
+class IdaFrame(_DepthFirstFrame):
+    """The caller-owned frame of n cubes (include/rubikhip.h "Iterative-deepening A*") and the two launching calls on it.  cubies: a
+    tiled cubie buffer of n cubes with pitch p_c; prefix: None or uint8 [k, n], written into path's first k rows with floor = k."""
+    INIT, SEARCH = "ida_init", "ida_search"
+
+    def __init__(self, table, cubies, n, p_c, max_depth, limit, prefix=None):
+        from ctypes import c_int, c_int64, c_void_p
+        from . import _ida_lib
+        corner, edges, _ = _ida_members(table)
+        dev = cubies.device
+        self.n, self.dev, self.max_depth, self.L = n, dev, int(max_depth), _ida_lib.ida_lib()
+        pitch = _lib.pitch_for(max(n, 1), 16)
+        self._alloc(pitch, dev)
+        self.path = torch.full((self.max_depth, pitch), _ida_lib.NOOP, dtype=torch.uint8, device=dev)
+        self.floor = None
+        if prefix is not None and prefix.shape[0]:
+            self.path[:prefix.shape[0], :n] = prefix
+            self.floor = torch.full((pitch,), prefix.shape[0], dtype=torch.int32, device=dev)
+        self.limit = torch.zeros(pitch, dtype=torch.int32, device=dev)
+        self.limit[:n] = limit
+        k = len(edges)
+        self._keep = (corner, edges, cubies)
+        self._args = (ptr(cubies), n, p_c, ptr(corner.table) if corner is not None else None, corner.table.numel() if corner is not None else 0, k,
+                      (c_int * max(k, 1))(*[e.mask for e in edges]), (c_void_p * max(k, 1))(*[ptr(e.table) for e in edges]),
+                      (c_int64 * max(k, 1))(*[e.table.numel() for e in edges]), ptr(self.path), self.max_depth, pitch,
+                      ptr(self.floor) if self.floor is not None else None, ptr(self.limit), ptr(self.trail), ptr(self.cursor), ptr(self.depth),
+                      ptr(self.bound), ptr(self.next), ptr(self.nodes), ptr(self.status))
 
 
 def ida_search(table, env, *, limit=20, max_steps=1 << 22, steps_per_call=None, split=0):
@@ -672,28 +715,14 @@ def ida_search(table, env, *, limit=20, max_steps=1 << 22, steps_per_call=None, 
     was excluded), status uint8 [N] (IDA_SOLVED 1, IDA_EXHAUSTED 2: no solution within limit, IDA_ILLEGAL 4, 0: the budget ran out))."""
     from . import _ida_lib
     corner, edges, dev = _ida_members(table)
-    if not hasattr(env, "stickers") or env.cube_size != 3:
-        raise ValueError(f"ida_search needs a 3x3x3 VecCubeEnv, got {'a ' + str(env.cube_size) + 'x' + str(env.cube_size) + 'x' + str(env.cube_size) + ' one' if hasattr(env, 'cube_size') else type(env).__name__}")
-    ints = lambda v: isinstance(v, int) and not isinstance(v, bool)
-    if not ints(limit) or not 0 <= limit <= _ida_lib.MAX_DEPTH:
+    _cube3_env(env, "ida_search")
+    if not _is_int(limit) or not 0 <= limit <= _ida_lib.MAX_DEPTH:
         raise ValueError(f"limit must be an integer in 0..{_ida_lib.MAX_DEPTH}, got {limit!r}")
-    if not ints(split) or not 0 <= split <= 3:
+    if not _is_int(split) or not 0 <= split <= 3:
         raise ValueError(f"split must be an integer in 0..3, got {split!r}")
-    if not ints(max_steps) or max_steps < 1:
-        raise ValueError(f"max_steps must be a positive integer, got {max_steps!r}")
-    cap = _ida_lib.max_steps()
-    if steps_per_call is None:
-        steps_per_call = cap
-    if not ints(steps_per_call) or not 1 <= steps_per_call <= cap:
-        raise ValueError(f"steps_per_call must be an integer in 1..ida_max_steps() = {cap}, got {steps_per_call!r}")
-    if dev is not None and env.stickers.device != dev:
-        raise ValueError(f"the tables are on {dev}, the cubes on {env.stickers.device}")
+    steps_per_call = _steps_args(max_steps, steps_per_call, _ida_lib.max_steps(), "ida_max_steps")
+    cub, p_c, legal = _cube3_cubies(env, "ida_search", dev)
     n, dev = env.num_envs, env.stickers.device
-    _lib.init(dev)
-    cub = ops.alloc_code(n, 3, dev, env.stickers.shape[-1])
-    legal = torch.empty(_lib.pitch_for(n, 16), dtype=torch.uint8, device=dev)
-    ops.cubies(env.stickers, n, 3, cubies=cub, status=legal)
-    p_c = ops._state_arg(cub, 20, n, None, "ida_search cubies")
     max_depth = max(1, limit)
 
     fr = IdaFrame(table, cub, n, p_c, max_depth, min(limit, split) if split else limit)
@@ -747,9 +776,10 @@ def ida_search(table, env, *, limit=20, max_steps=1 << 22, steps_per_call=None, 
     return dict(solved=solved, length=length, actions=acts.contiguous(), nodes=nodes, bound=bound, status=status)
 
 
-class TwoPhase1Frame:
+class TwoPhase1Frame(_DepthFirstFrame):
     """The caller-owned frame of phase 1 over n cubes (include/rubikhip.h "Two-phase") and its two launching calls.  cubies: a tiled
     cubie buffer of n cubes with pitch p_c; candidate (j, c) lives in column j * stride + c of path, cand_length and cand_cubies."""
+    INIT, SEARCH = "tp_phase1_init", "tp_phase1_search"
 
     def __init__(self, tables, cubies, n, p_c, candidates, limit, max_depth=None):
         from . import _twophase_lib as T
@@ -758,61 +788,36 @@ class TwoPhase1Frame:
         self.max_depth = T.MAX_DEPTH if max_depth is None else int(max_depth)
         self.stride = stride = _lib.pitch_for(max(n, 1), 16)
         self.cols = cols = self.K * stride
-        vec = lambda dtype: torch.zeros(stride, dtype=dtype, device=dev)
+        self._alloc(stride, dev)
         self.path = torch.full((self.max_depth, cols), T.NOOP, dtype=torch.uint8, device=dev)
         self.cand_length = torch.zeros(cols, dtype=torch.int32, device=dev)
         self.cand_cubies = torch.zeros((20, cols), dtype=torch.uint8, device=dev)
         self.cand_cubies += torch.tensor([3 * q for q in range(8)] + [2 * q for q in range(12)], dtype=torch.uint8, device=dev)[:, None]
-        self.limit = vec(torch.int32)
+        self.limit = torch.zeros(stride, dtype=torch.int32, device=dev)
         self.limit[:n] = limit
-        self.trail = torch.zeros((stride, 2), dtype=torch.int64, device=dev)
-        self.cursor, self.status = vec(torch.uint8), vec(torch.uint8)
-        self.depth, self.bound, self.next, self.found = vec(torch.int32), vec(torch.int32), vec(torch.int32), vec(torch.int32)
-        self.nodes = vec(torch.int64)
-        self.running = torch.zeros(4, dtype=torch.int32, device=dev)       # one uint32, 16-byte aligned
+        self.found = torch.zeros(stride, dtype=torch.int32, device=dev)
         a, b = tables.tables[0], tables.tables[1]
         self._keep = (tables, cubies)
         self._args = (ptr(cubies), n, p_c, ptr(a), a.numel(), ptr(b), b.numel(), ptr(self.limit), self.K, stride, ptr(self.path), self.max_depth,
                       cols, ptr(self.cand_length), ptr(self.cand_cubies), cols, ptr(self.trail), ptr(self.cursor), ptr(self.depth),
                       ptr(self.bound), ptr(self.next), ptr(self.nodes), ptr(self.found), ptr(self.status))
 
-    def init(self):
-        _lib.check(self.L.tp_phase1_init(*self._args, stream_ptr(self.dev)))
 
-    def search(self, steps):
-        _lib.check(self.L.tp_phase1_search(*self._args, int(steps), ptr(self.running), stream_ptr(self.dev)))
-
-    run = IdaFrame.run
-
-
-class TwoPhase2Frame:
+class TwoPhase2Frame(_DepthFirstFrame):
     """The caller-owned frame of phase 2 over n columns and its two launching calls.  cubies [20, pitch >= n]: the G1 roots; path
     uint8 [max_depth, pitch]: the prefixes (rows below floor) and the room for the answers; floor, limit: int32 [>= n]."""
+    INIT, SEARCH = "tp_phase2_init", "tp_phase2_search"
 
     def __init__(self, tables, cubies, n, p_c, path, floor, limit):
         from . import _twophase_lib as T
         dev = cubies.device
         self.n, self.dev, self.L, self.path, self.floor, self.limit = n, dev, T.twophase_lib(), path, floor, limit
-        pitch = _lib.pitch_for(max(n, 1), 16)
-        vec = lambda dtype: torch.zeros(pitch, dtype=dtype, device=dev)
-        self.trail = torch.zeros((pitch, 2), dtype=torch.int64, device=dev)
-        self.cursor, self.status = vec(torch.uint8), vec(torch.uint8)
-        self.depth, self.bound, self.next = vec(torch.int32), vec(torch.int32), vec(torch.int32)
-        self.nodes = vec(torch.int64)
-        self.running = torch.zeros(4, dtype=torch.int32, device=dev)
+        self._alloc(_lib.pitch_for(max(n, 1), 16), dev)
         a, b = tables.tables[2], tables.tables[3]
         self._keep = (tables, cubies)
         self._args = (ptr(cubies), n, p_c, ptr(a), a.numel(), ptr(b), b.numel(), ptr(path), path.shape[0], path.shape[1],
                       ptr(floor) if floor is not None else None, ptr(limit), ptr(self.trail), ptr(self.cursor), ptr(self.depth), ptr(self.bound),
                       ptr(self.next), ptr(self.nodes), ptr(self.status))
-
-    def init(self):
-        _lib.check(self.L.tp_phase2_init(*self._args, stream_ptr(self.dev)))
-
-    def search(self, steps):
-        _lib.check(self.L.tp_phase2_search(*self._args, int(steps), ptr(self.running), stream_ptr(self.dev)))
-
-    run = IdaFrame.run
 
 
 TWO_PHASE_DESCENT_ROWS = 58        # quarter turns of the chain's stages 2 and 3 at the most: 2 * 14 + 2 * 15
@@ -869,32 +874,18 @@ def two_phase_frames(tables, chain, env, *, candidates=64, phase1_limit=16, phas
         raise ValueError(f"two_phase_solve(tables, chain, env): tables is a pattern.TwoPhaseTables, got {type(tables).__name__}")
     if not isinstance(chain, ChainTables):
         raise ValueError(f"two_phase_solve(tables, chain, env): chain is a pattern.ChainTables, got {type(chain).__name__}")
-    if not hasattr(env, "stickers") or env.cube_size != 3:
-        raise ValueError(f"two_phase_solve needs a 3x3x3 VecCubeEnv, got {'a ' + str(env.cube_size) + 'x' + str(env.cube_size) + 'x' + str(env.cube_size) + ' one' if hasattr(env, 'cube_size') else type(env).__name__}")
-    ints = lambda v: isinstance(v, int) and not isinstance(v, bool)
-    if not ints(candidates) or not 1 <= candidates <= T.MAX_CANDIDATES:
+    _cube3_env(env, "two_phase_solve")
+    if not _is_int(candidates) or not 1 <= candidates <= T.MAX_CANDIDATES:
         raise ValueError(f"candidates must be an integer in 1..{T.MAX_CANDIDATES}, got {candidates!r}")
-    if not ints(phase1_limit) or not 0 <= phase1_limit <= T.MAX_TRAIL:
+    if not _is_int(phase1_limit) or not 0 <= phase1_limit <= T.MAX_TRAIL:
         raise ValueError(f"phase1_limit must be an integer in 0..{T.MAX_TRAIL}, got {phase1_limit!r}")
-    if not ints(phase2_limit) or not 0 <= phase2_limit <= T.MAX_TRAIL:
+    if not _is_int(phase2_limit) or not 0 <= phase2_limit <= T.MAX_TRAIL:
         raise ValueError(f"phase2_limit must be an integer in 0..{T.MAX_TRAIL}, got {phase2_limit!r}")
-    if not ints(max_steps) or max_steps < 1:
-        raise ValueError(f"max_steps must be a positive integer, got {max_steps!r}")
-    cap = T.max_steps()
-    if steps_per_call is None:
-        steps_per_call = cap
-    if not ints(steps_per_call) or not 1 <= steps_per_call <= cap:
-        raise ValueError(f"steps_per_call must be an integer in 1..tp_max_steps() = {cap}, got {steps_per_call!r}")
+    steps_per_call = _steps_args(max_steps, steps_per_call, T.max_steps(), "tp_max_steps")
     if chain.device != tables.device:
         raise ValueError(f"the two-phase tables are on {tables.device}, the chain's on {chain.device}")
-    if env.stickers.device != tables.device:
-        raise ValueError(f"the tables are on {tables.device}, the cubes on {env.stickers.device}")
+    cub, p_c, legal = _cube3_cubies(env, "two_phase_solve", tables.device)
     n, dev, K = env.num_envs, tables.device, candidates
-    _lib.init(dev)
-    cub = ops.alloc_code(n, 3, dev, env.stickers.shape[-1])
-    legal = torch.empty(_lib.pitch_for(n, 16), dtype=torch.uint8, device=dev)
-    ops.cubies(env.stickers, n, 3, cubies=cub, status=legal)
-    p_c = ops._state_arg(cub, 20, n, None, "two_phase_solve cubies")
     bad = legal[:n] != 0
 
     one = TwoPhase1Frame(tables, cub, n, p_c, K, phase1_limit)
