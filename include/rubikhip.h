@@ -726,6 +726,55 @@ int tp_phase2_search(const uint8_t *cubies, int64_t n, int64_t cubie_pitch, cons
                      uint64_t *trail, uint8_t *cursor, int32_t *depth, int32_t *bound, int32_t *next, uint64_t *nodes, uint8_t *status,
                      int64_t max_steps, uint32_t *running, void *stream);
 
+/* ---------------------------------------------------------------------------------------------------------------------------------
+ * Cube group (prefix cg_): whole cubes as group elements -- product, inverse, uniformly random cubes, and the inverse of an action
+ * list.  Both cube sizes.  No reference counterpart.
+ *
+ * THE RULE.  Cubie bytes, slots and pieces are those of the rcc_* section (rows [tiles][SLOTS][pitch], SLOTS = 20 | 7, NC = 8 | 7);
+ * a legal cube x is the group element that takes solved to x.
+ *   product    x o y ("x then y") is the cube reached from x by any move sequence that takes solved to y.  In bytes, for every slot q
+ *              with p = piece(y[q]):  piece(out[q]) = piece(x[p]),  ori(out[q]) = (ori(x[p]) + ori(y[q])) mod 3 (corners) | mod 2
+ *              (edges).  The move tables are this rule with y = one move: rc_apply_moves by action a = the product with the cube
+ *              "solved then a".
+ *   inverse    for every slot q with p = piece(x[q]):  out[p] = (q, -ori(x[q])), mod 3 | mod 2.  Defined only when the corner rows and
+ *              the edge rows are each a permutation.
+ *   identity   the solved cube's rows.
+ *   2x2x2      only the 7 stored corner rows take part; the DLB cubie is fixed.
+ *   bad input  a corner byte >= 3 * NC or an edge byte >= 24, in either operand of the product or in the operand of the inverse: that
+ *              cube's output is the identity and *bad is set to 1 (one device byte the caller zeroes and reads, required, as in
+ *              rcc_from_cubies; set by a plain vector store).  A repeated piece in the operand of the inverse: the same.  The
+ *              product does not require permutations: it is the gather as written.  Twist, flip and parity are NOT checked: the
+ *              operations are defined on all assemblies, and RCC_TWIST, RCC_FLIP and RCC_PARITY of a product follow from its
+ *              factors (the twist sums add mod 3, the flip sums mod 2, the permutation parities mod 2), those of an inverse are its
+ *              operand's.
+ *   random     cube i of a call uses the walk generator (xoroshiro128+ seeded through splitmix64, as rc_adi_generate's) seeded with
+ *              (seed, stream_id, first + i); `first` lets a caller cut one stream into chunks or shards.  next64() = s0 + s1,
+ *              followed by the state step every action draw makes; draw(m) = the high 64 bits of next64() * m, which deviates from
+ *              uniform by less than m / 2^64 per draw.  Order of draws, 3x3x3:
+ *                1 corners  from the identity permutation, for i = 7 down to 1: j = draw(i + 1), swap entries i and j;
+ *                2 twists   ori[q] = draw(3) for q = 0..6; ori[7] makes the sum 0 mod 3;
+ *                3 edges    as 1, for i = 11 down to 1;
+ *                4 flips    one r = next64(): ori[q] = bit (63 - q) of r for q = 0..10; ori[11] makes the sum even;
+ *                5 parity   if the corner permutation's parity differs from the edge permutation's, the whole bytes of edge slots
+ *                           10 and 11 change places.
+ *              26 generator steps, uniform over the 43 252 003 274 489 856 000 legal cubes: step 5 maps the mismatched half of the
+ *              (corner, edge) permutation pairs one-to-one onto the matched half.  2x2x2: steps 1 and 2 over 7 slots (i = 6..1,
+ *              twists q = 0..5, the last one fixed): 12 steps, uniform over 3 674 160 cubes.
+ *   inverted actions   of a column of actions [rows][act_pitch], A = 12 | 6 the no-op: the column's non-no-op entries in reverse order,
+ *              each ^ 1, then no-ops up to row rows - 1.  An entry above A is treated like the no-op and sets *bad.
+ *
+ * Conventions as in the rcc_* section: caller-owned device memory, stream-ordered, nothing allocated; RC_EINVAL before any launch
+ * (rc_last_error names the operand); n == 0 succeeds without a launch; every pointer needs 16-byte alignment and no more; pad columns
+ * and every byte outside the rows keep their bytes.  out may be exactly x or exactly y -- the same pointer AND the same pitch --, then
+ * every lane reads its own columns before it writes them; any other overlap of out with an input is RC_EINVAL.  For
+ * cg_invert_actions, out == actions is allowed on the same terms; its pitches are one tile's (pitch % 16 == 0, pitch >= n). */
+int cg_product(const uint8_t *x, int64_t x_pitch, const uint8_t *y, int64_t y_pitch, int64_t n, int cube_size,
+               uint8_t *out, int64_t out_pitch, uint8_t *bad, void *stream);
+int cg_inverse(const uint8_t *x, int64_t x_pitch, int64_t n, int cube_size, uint8_t *out, int64_t out_pitch, uint8_t *bad, void *stream);
+int cg_random(uint64_t seed, uint64_t stream_id, int64_t first, int64_t n, int cube_size, uint8_t *out, int64_t out_pitch, void *stream);
+int cg_invert_actions(const uint8_t *actions, int64_t rows, int64_t n, int64_t act_pitch, int cube_size,
+                      uint8_t *out, int64_t out_pitch, uint8_t *bad, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

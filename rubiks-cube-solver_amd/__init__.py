@@ -16,6 +16,9 @@ Drop-in surface for the env path of SUNGBEOMCHOI/Rubiks-Cube-Solver:
   ida_search          Korf's IDA* under those pattern databases (search.py): the OPTIMAL solution of a 3x3x3, no node pool
   TwoPhaseTables      the four coset tables of Kociemba's two-phase algorithm (pattern.py), and two_phase_solve (search.py): a SHORT
   two_phase_solve     solution of ANY legal 3x3x3 -- never longer than chain_solve's -- by two table-guided depth-first searches
+  relative_to, two_phase_solve_both, random_state_scramble, invert_actions   the cube group's tie-ins (search.py): solve to a goal other
+                      than solved, solve the cube and its inverse and keep the shorter answer, random-state scrambles from uniformly
+                      drawn cubes (ops.group_product / group_inverse / random_cubies; VecCubeEnv.compose / invert / reset_uniform)
   get_cubies, RCC_*   the cube as pieces: (piece, orientation) bytes, the legality status bits, perfect indices (ops.cubies / from_cubies)
   py333               the same operators under the reference's names, one cube per call
   py222               the six names cube_env.py:8 imports from the file the reference does not ship (2x2x2, one cube per call)
@@ -26,7 +29,8 @@ from .tables import (ACTION_NAMES, RCC_BAD_COLOUR, RCC_BAD_FIXED, RCC_BAD_PIECE,
 
 __all__ = ["get_env_config", "get_tables", "get_cubies", "ACTION_NAMES", "RCC_BAD_COLOUR", "RCC_BAD_FIXED", "RCC_BAD_PIECE", "RCC_DUP_PIECE",
            "RCC_TWIST", "RCC_FLIP", "RCC_PARITY", "RCC_NAMES", "ops", "make_env", "CubeEnv", "VecCubeEnv", "TensorReplayBuffer", "CodeNet", "CornerTable", "EdgeTable",
-           "MaxTable", "ChainTables", "chain_solve", "ida_search", "TwoPhaseTables", "two_phase_solve"]
+           "MaxTable", "ChainTables", "chain_solve", "ida_search", "TwoPhaseTables", "two_phase_solve", "relative_to",
+           "two_phase_solve_both", "random_state_scramble", "invert_actions"]
 
 
 def __getattr__(name):  # torch-dependent parts load lazily
@@ -42,7 +46,7 @@ def __getattr__(name):  # torch-dependent parts load lazily
         return importlib.import_module(f"{__name__}.codenet").CodeNet
     if name in ("CornerTable", "EdgeTable", "MaxTable", "ChainTables", "TwoPhaseTables"):
         return getattr(importlib.import_module(f"{__name__}.pattern"), name)
-    if name in ("chain_solve", "ida_search", "two_phase_solve"):
+    if name in ("chain_solve", "ida_search", "two_phase_solve", "relative_to", "two_phase_solve_both", "random_state_scramble", "invert_actions"):
         return getattr(importlib.import_module(f"{__name__}.search"), name)
     if name in ("CubeEnv", "make_env"):
         return getattr(importlib.import_module(f"{__name__}.cube_env"), name)

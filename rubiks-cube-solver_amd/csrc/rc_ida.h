@@ -12,6 +12,8 @@
 //                               (path column, length, cubie rows), the search never enters G1
 //   k_tp2_init / k_tp2_search   phase 2, one lane per candidate column, under max(corner-slice, edge-slice): stage 2's generators with
 //                               a half turn costing 2; the first goal ends the lane
+//   k_cg_product / k_cg_inverse / k_cg_random / k_cg_invert_actions   the cg_* entry points (include/rubikhip.h "Cube group"), at the
+//                               end of the file: whole cubes multiplied, inverted and drawn uniformly, on IdaCube; both cube sizes
 // A search kernel makes at most max_steps passes per cube; a pass applies ONE move to the cube in registers -- the next canonical
 // child, or the inverse of the last move to go back a level -- then ranks, reads the tables and compares.  The cube lives in five
 // registers of cubie bytes (IdaCube); a move is a byte gather (v_perm_b32) whose selectors come from a row of s_moves in LDS (13 rows:
@@ -88,12 +90,15 @@ struct IdaCube {
     uint32_t e0, e1, e2;   // byte q: edge slot q, the cubie byte piece * 2 + ori
 };
 
+// the corner bytes after two ori were added in the high nibbles: ori 3, 4 -> 0, 1
+__device__ __forceinline__ uint32_t ida_twist(uint32_t v) { return v - (((v + 0x10101010u) >> 6) & 0x01010101u) * 0x30u; }
+
 __device__ __forceinline__ IdaCube ida_move(const IdaCube &x, const uint32_t *row) {
     const u32x4 a = *reinterpret_cast<const u32x4 *>(row), b = *reinterpret_cast<const u32x4 *>(row + 4),
                 c = *reinterpret_cast<const u32x4 *>(row + 8);
     const uint32_t f2 = row[12];
     IdaCube y;
-    const auto twist = [](uint32_t v) { return v - (((v + 0x10101010u) >> 6) & 0x01010101u) * 0x30u; };   // ori 3, 4 -> 0, 1
+    const auto twist = ida_twist;
     y.c0 = twist(__builtin_amdgcn_perm(x.c1, x.c0, a[0]) + a[2]);
     y.c1 = twist(__builtin_amdgcn_perm(x.c1, x.c0, a[1]) + a[3]);
     y.e0 = (__builtin_amdgcn_perm(x.e1, x.e0, b[0]) | __builtin_amdgcn_perm(0u, x.e2, b[1])) ^ c[2];
@@ -1047,6 +1052,353 @@ int tp_phase2_search(const uint8_t *cubies, int64_t n, int64_t cubie_pitch, cons
         return rc;
     if (int rc = steps_arg("tp_phase2_search", a.fr, kTpMaxSteps, "tp_max_steps()")) return rc;
     return ida_launch(k_tp2_search, a, S(stream));
+}
+
+}  // extern "C"
+
+// ================================================================================================================= cube group
+// The cg_* entry points (include/rubikhip.h "Cube group", DESIGN.md "Cube group"): product, inverse, uniform random cubes and the
+// inverse of an action list.  One lane per cube, the cube in the five registers of an IdaCube, both cube sizes through the same code
+// (the 2x2x2: 7 rows, corner slot 7 holds piece 7 untwisted, the edge half compiled out).  The product is ida_move with the selector,
+// twist and flip words taken from y's registers instead of a move row; the inverse places byte (q, -ori) at byte `piece` of the
+// result by a shift, which is no register index; a random cube is 26 | 12 draws of a WalkRng.  No LDS, no indexed array, no scratch.
+namespace {
+
+__host__ __device__ constexpr IdaCube cg_identity() { return IdaCube{0x03020100u, 0x07060504u, 0x06040200u, 0x0E0C0A08u, 0x16141210u}; }
+constexpr uint32_t kCgBadByte = 1u, kCgDupPiece = 2u;
+
+// the T::SLOTS cubie bytes of cube `at` into x; kCgBadByte: a byte names no (piece, ori), kCgDupPiece: a piece occurs twice
+template <class T>
+__device__ __forceinline__ uint32_t cg_load(const uint8_t *at, int64_t pitch, IdaCube &x) {
+    uint32_t w[5] = {0u, 0u, 0u, 0u, 0u}, cseen = 0, eseen = 0, bad = 0, dup = 0;
+    sfor<T::NC>([&](auto qc) {
+        constexpr int q = decltype(qc)::value;
+        const uint32_t b = at[(int64_t)q * pitch], t = (b * 171u) >> 9, p = t & 7u;               // t = b / 3 for a byte
+        bad |= (uint32_t)(b >= 3u * (uint32_t)T::NC);
+        dup |= (cseen >> p) & 1u;
+        cseen |= 1u << p;
+        w[q >> 2] |= (p | ((b - 3u * t) << 4)) << (8 * (q & 3));
+    });
+    if constexpr (T::NC == 7) w[1] |= 0x07000000u;                                               // the fixed DLB cubie
+    if constexpr (T::NE != 0) {
+        sfor<12>([&](auto qc) {
+            constexpr int q = decltype(qc)::value;
+            const uint32_t b = at[(int64_t)(T::NC + q) * pitch], p = (b >> 1) & 15u;
+            bad |= (uint32_t)(b >= 24u);
+            dup |= (eseen >> p) & 1u;
+            eseen |= 1u << p;
+            w[2 + (q >> 2)] |= (b & 31u) << (8 * (q & 3));
+        });
+    } else {
+        w[2] = cg_identity().e0, w[3] = cg_identity().e1, w[4] = cg_identity().e2;
+    }
+    x = IdaCube{w[0], w[1], w[2], w[3], w[4]};
+    return (bad ? kCgBadByte : 0u) | (dup ? kCgDupPiece : 0u);
+}
+
+template <class T>
+__device__ __forceinline__ void cg_store(uint8_t *at, int64_t pitch, const IdaCube &x) {
+    sfor<T::NC>([&](auto qc) {
+        constexpr int q = decltype(qc)::value;
+        const uint32_t v = ((q < 4 ? x.c0 : x.c1) >> (8 * (q & 3))) & 0xFFu;
+        at[(int64_t)q * pitch] = (uint8_t)((v & 15u) * 3u + (v >> 4));
+    });
+    if constexpr (T::NE != 0)
+        sfor<12>([&](auto qc) {
+            constexpr int q = decltype(qc)::value;
+            at[(int64_t)(T::NC + q) * pitch] = (uint8_t)(((q < 4 ? x.e0 : q < 8 ? x.e1 : x.e2) >> (8 * (q & 3))) & 0xFFu);
+        });
+}
+
+// x then y: slot q of the result holds what x has in slot piece(y[q]), turned by ori(y[q]) -- the gather as written, for any bytes
+template <class T>
+__device__ __forceinline__ IdaCube cg_mul(const IdaCube &x, const IdaCube &y) {
+    IdaCube o = cg_identity();
+    o.c0 = ida_twist(__builtin_amdgcn_perm(x.c1, x.c0, y.c0 & 0x07070707u) + (y.c0 & 0x30303030u));
+    o.c1 = ida_twist(__builtin_amdgcn_perm(x.c1, x.c0, y.c1 & 0x07070707u) + (y.c1 & 0x30303030u));
+    if constexpr (T::NE != 0) {
+        const auto edge = [&](uint32_t ye) {
+            const uint32_t p = ye >> 1, high = ((p >> 3) & 0x01010101u) * 0xFFu;                   // 0xFF where the piece is 8..11
+            const uint32_t lo = __builtin_amdgcn_perm(x.e1, x.e0, p & 0x07070707u), hi = __builtin_amdgcn_perm(0u, x.e2, p & 0x03030303u);
+            return ((hi & high) | (lo & ~high)) ^ (ye & 0x01010101u);
+        };
+        o.e0 = edge(y.e0);
+        o.e1 = edge(y.e1);
+        o.e2 = edge(y.e2);
+    }
+    return o;
+}
+
+// out[piece(x[q])] = (q, -ori(x[q])): byte `piece` of the result's words, reached by a shift (x a permutation: no two meet)
+template <class T>
+__device__ __forceinline__ IdaCube cg_inv(const IdaCube &x) {
+    IdaCube o = cg_identity();
+    uint64_t c = 0;
+    sfor<8>([&](auto qc) {
+        constexpr uint32_t q = decltype(qc)::value;
+        const uint32_t v = ((q < 4 ? x.c0 : x.c1) >> (8 * (q & 3))) & 0xFFu, ori = v >> 4, neg = ((ori << 1) | (ori >> 1)) & 3u;
+        c |= (uint64_t)(q | (neg << 4)) << (8u * (v & 7u));
+    });
+    o.c0 = (uint32_t)c;
+    o.c1 = (uint32_t)(c >> 32);
+    if constexpr (T::NE != 0) {
+        uint64_t lo = 0;
+        uint32_t hi = 0;
+        sfor<12>([&](auto qc) {
+            constexpr uint32_t q = decltype(qc)::value;
+            const uint32_t v = ((q < 4 ? x.e0 : q < 8 ? x.e1 : x.e2) >> (8 * (q & 3))) & 0xFFu, p = v >> 1, put = 2u * q + (v & 1u);
+            lo |= p < 8u ? (uint64_t)put << (8u * (p & 7u)) : 0ull;
+            hi |= p < 8u ? 0u : put << (8u * (p & 3u));
+        });
+        o.e0 = (uint32_t)lo;
+        o.e1 = (uint32_t)(lo >> 32);
+        o.e2 = hi;
+    }
+    return o;
+}
+
+struct CgRows {
+    const uint8_t *at;
+    int64_t pitch;
+    int sh;
+};
+struct CgArgs {
+    CgRows x, y;
+    int64_t n;
+    uint8_t *out;
+    int64_t out_pitch;
+    int out_sh;
+    uint8_t *bad;
+};
+
+template <class T>
+__global__ void __launch_bounds__(256) k_cg_product(CgArgs a) {
+    const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (c >= a.n) return;
+    IdaCube x, y;
+    const uint32_t fx = cg_load<T>(a.x.at + cubie_off(c, a.x.pitch, a.x.sh, T::SLOTS), a.x.pitch, x);
+    const uint32_t fy = cg_load<T>(a.y.at + cubie_off(c, a.y.pitch, a.y.sh, T::SLOTS), a.y.pitch, y);
+    IdaCube o = cg_mul<T>(x, y);
+    if ((fx | fy) & kCgBadByte) {
+        o = cg_identity();
+        *a.bad = 1;
+    }
+    cg_store<T>(a.out + cubie_off(c, a.out_pitch, a.out_sh, T::SLOTS), a.out_pitch, o);             // after both loads: out may be x or y
+}
+
+template <class T>
+__global__ void __launch_bounds__(256) k_cg_inverse(CgArgs a) {
+    const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (c >= a.n) return;
+    IdaCube x;
+    const uint32_t fx = cg_load<T>(a.x.at + cubie_off(c, a.x.pitch, a.x.sh, T::SLOTS), a.x.pitch, x);
+    IdaCube o = cg_inv<T>(x);
+    if (fx) {
+        o = cg_identity();
+        *a.bad = 1;
+    }
+    cg_store<T>(a.out + cubie_off(c, a.out_pitch, a.out_sh, T::SLOTS), a.out_pitch, o);
+}
+
+// THE RULE's generator: the walk generator's state, its whole 64-bit output, a draw by the high half of a 64 x 64 product
+struct CgRng : WalkRng {
+    __device__ __forceinline__ uint64_t next64() {
+        const uint64_t r = s0 + s1;
+        (void)action(1u);                                                     // the state step
+        return r;
+    }
+    __device__ __forceinline__ uint32_t draw(uint32_t m) { return (uint32_t)__umul64hi(next64(), (uint64_t)m); }
+};
+
+template <class T>
+__global__ void __launch_bounds__(256) k_cg_random(uint64_t seed, uint64_t stream_id, int64_t first, int64_t n, uint8_t *out, int64_t pitch, int sh) {
+    const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (c >= n) return;
+    CgRng g;
+    g.seed(seed, stream_id, (uint64_t)(first + c));
+    uint32_t cp = 0x76543210u, odd = 0, sum = 0, co = 0;                      // nibble q: the piece | the ori of corner slot q
+    sfor<T::NC - 1>([&](auto kc) {
+        constexpr uint32_t i = T::NC - 1 - decltype(kc)::value;
+        const uint32_t j = g.draw(i + 1u), d = ((cp >> (4u * i)) ^ (cp >> (4u * j))) & 15u;
+        cp ^= (d << (4u * i)) | (d << (4u * j));
+        odd ^= (uint32_t)(j != i);
+    });
+    sfor<T::NC - 1>([&](auto qc) {
+        const uint32_t t = g.draw(3u);
+        sum += t;
+        co |= t << (4u * decltype(qc)::value);
+    });
+    co |= ((3u - sum % 3u) % 3u) << (4u * (T::NC - 1));           // the last twist makes the sum 0 mod 3
+    IdaCube x = cg_identity();
+    x.c0 = x.c1 = 0u;
+    sfor<8>([&](auto qc) {
+        constexpr uint32_t q = decltype(qc)::value;
+        const uint32_t v = (((cp >> (4u * q)) & 15u) | (((co >> (4u * q)) & 3u) << 4)) << (8u * (q & 3u));
+        if (q < 4u) x.c0 |= v;
+        else x.c1 |= v;
+    });
+    if constexpr (T::NE != 0) {
+        uint64_t ep = 0xBA9876543210ull;
+        uint32_t eodd = 0;
+        sfor<11>([&](auto kc) {
+            constexpr uint32_t i = 11u - decltype(kc)::value;
+            const uint32_t j = g.draw(i + 1u);
+            const uint64_t d = ((ep >> (4u * i)) ^ (ep >> (4u * j))) & 15ull;
+            ep ^= (d << (4u * i)) | (d << (4u * j));
+            eodd ^= (uint32_t)(j != i);
+        });
+        const uint64_t r = g.next64();
+        uint32_t w[3] = {0u, 0u, 0u};
+        sfor<12>([&](auto qc) {
+            constexpr uint32_t q = decltype(qc)::value;
+            const uint32_t flip = q < 11u ? (uint32_t)(r >> (63u - q)) & 1u : (uint32_t)__popcll(r >> 53) & 1u;
+            w[q >> 2] |= (2u * ((uint32_t)(ep >> (4u * q)) & 15u) + flip) << (8u * (q & 3u));
+        });
+        if (odd != eodd) w[2] = __builtin_amdgcn_perm(0u, w[2], 0x02030100u);                      // slots 10 and 11 change places
+        x.e0 = w[0], x.e1 = w[1], x.e2 = w[2];
+    }
+    cg_store<T>(out + cubie_off(c, pitch, sh, T::SLOTS), pitch, x);
+}
+
+// One lane per column: the entries below A go to the top of out's column, each ^ 1, in order; the rest of the column is A; then the
+// top is reversed in place.  Every row a lane writes it has read before, so out may be the actions themselves.
+__global__ void __launch_bounds__(256) k_cg_invert_actions(const uint8_t *actions, int64_t rows, int64_t n, int64_t act_pitch, uint32_t A,
+                                                           uint8_t *out, int64_t out_pitch, uint8_t *bad) {
+    const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (c >= n) return;
+    int64_t k = 0;
+    uint32_t above = 0;
+    for (int64_t r = 0; r < rows; ++r) {
+        const uint32_t a = actions[r * act_pitch + c];
+        above |= (uint32_t)(a > A);
+        if (a < A) out[k++ * out_pitch + c] = (uint8_t)(a ^ 1u);
+    }
+    for (int64_t r = k; r < rows; ++r) out[r * out_pitch + c] = (uint8_t)A;
+    for (int64_t lo = 0, hi = k - 1; lo < hi; ++lo, --hi) {
+        const uint8_t u = out[lo * out_pitch + c], v = out[hi * out_pitch + c];
+        out[lo * out_pitch + c] = v;
+        out[hi * out_pitch + c] = u;
+    }
+    if (above) *bad = 1;
+}
+
+// the bytes a tiled cubie operand spans, from its first byte to one past cube n - 1's last row
+inline int64_t cg_extent(int64_t n, int64_t pitch, int slots) {
+    const int64_t t = tiles_of(n, pitch) - 1;
+    return t * slots * pitch + (slots - 1) * pitch + (n - t * pitch);
+}
+inline bool cg_overlap(const void *p, int64_t pb, const void *q, int64_t qb) {
+    const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
+    return a < b + (uintptr_t)qb && b < a + (uintptr_t)pb;
+}
+
+// a cubie operand of a cg_* call: present, 16-byte aligned, a valid tiling for n cubes
+int cg_rows_arg(const char *fn, const char *name, const void *p, int64_t pitch, int64_t n, int slots, int &sh) {
+    if (!p || !aligned16(p)) return fail(RC_EINVAL, "%s: %s is NULL or not 16-byte aligned", fn, name);
+    if ((sh = tile_shift(pitch, n, slots)) < 0)
+        return fail(RC_EINVAL, "%s: %s_pitch: need pitch %% 16 == 0 and pitch >= n, or a power-of-two tile >= 512", fn, name);
+    return RC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int cg_product(const uint8_t *x, int64_t x_pitch, const uint8_t *y, int64_t y_pitch, int64_t n, int cube_size, uint8_t *out, int64_t out_pitch,
+               uint8_t *bad, void *stream) {
+    RC_NEED_INIT();
+    if (cube_size != 2 && cube_size != 3) return fail(RC_EINVAL, "cg_product: cube_size must be 2 or 3");
+    if (n < 0) return fail(RC_EINVAL, "cg_product: n is negative");
+    const int slots = cube_size == 3 ? Cube3::SLOTS : Cube2::SLOTS;
+    CgArgs a{};
+    if (int rc = cg_rows_arg("cg_product", "x", x, x_pitch, n, slots, a.x.sh)) return rc;
+    if (int rc = cg_rows_arg("cg_product", "y", y, y_pitch, n, slots, a.y.sh)) return rc;
+    if (int rc = cg_rows_arg("cg_product", "out", out, out_pitch, n, slots, a.out_sh)) return rc;
+    if (!bad) return fail(RC_EINVAL, "cg_product: bad is NULL");
+    if (n == 0) return RC_OK;
+    const int64_t ob = cg_extent(n, out_pitch, slots);
+    if (!(out == x && out_pitch == x_pitch) && cg_overlap(out, ob, x, cg_extent(n, x_pitch, slots)))
+        return fail(RC_EINVAL, "cg_product: out overlaps x (out may be exactly x, with x's pitch)");
+    if (!(out == y && out_pitch == y_pitch) && cg_overlap(out, ob, y, cg_extent(n, y_pitch, slots)))
+        return fail(RC_EINVAL, "cg_product: out overlaps y (out may be exactly y, with y's pitch)");
+    if (cg_overlap(bad, 1, out, ob)) return fail(RC_EINVAL, "cg_product: bad lies inside out");
+    a.x.at = x, a.x.pitch = x_pitch, a.y.at = y, a.y.pitch = y_pitch;
+    a.n = n, a.out = out, a.out_pitch = out_pitch, a.bad = bad;
+    const int64_t blocks = ceil_div(n, 256);
+    RC_GRID(blocks);
+    return by_size(cube_size, [&](auto t) {
+        hipLaunchKernelGGL(k_cg_product<decltype(t)>, dim3((unsigned)blocks), dim3(256), 0, S(stream), a);
+        RC_HIP(RC_EHIP, hipGetLastError());
+        return RC_OK;
+    });
+}
+
+int cg_inverse(const uint8_t *x, int64_t x_pitch, int64_t n, int cube_size, uint8_t *out, int64_t out_pitch, uint8_t *bad, void *stream) {
+    RC_NEED_INIT();
+    if (cube_size != 2 && cube_size != 3) return fail(RC_EINVAL, "cg_inverse: cube_size must be 2 or 3");
+    if (n < 0) return fail(RC_EINVAL, "cg_inverse: n is negative");
+    const int slots = cube_size == 3 ? Cube3::SLOTS : Cube2::SLOTS;
+    CgArgs a{};
+    if (int rc = cg_rows_arg("cg_inverse", "x", x, x_pitch, n, slots, a.x.sh)) return rc;
+    if (int rc = cg_rows_arg("cg_inverse", "out", out, out_pitch, n, slots, a.out_sh)) return rc;
+    if (!bad) return fail(RC_EINVAL, "cg_inverse: bad is NULL");
+    if (n == 0) return RC_OK;
+    const int64_t ob = cg_extent(n, out_pitch, slots);
+    if (!(out == x && out_pitch == x_pitch) && cg_overlap(out, ob, x, cg_extent(n, x_pitch, slots)))
+        return fail(RC_EINVAL, "cg_inverse: out overlaps x (out may be exactly x, with x's pitch)");
+    if (cg_overlap(bad, 1, out, ob)) return fail(RC_EINVAL, "cg_inverse: bad lies inside out");
+    a.x.at = x, a.x.pitch = x_pitch;
+    a.n = n, a.out = out, a.out_pitch = out_pitch, a.bad = bad;
+    const int64_t blocks = ceil_div(n, 256);
+    RC_GRID(blocks);
+    return by_size(cube_size, [&](auto t) {
+        hipLaunchKernelGGL(k_cg_inverse<decltype(t)>, dim3((unsigned)blocks), dim3(256), 0, S(stream), a);
+        RC_HIP(RC_EHIP, hipGetLastError());
+        return RC_OK;
+    });
+}
+
+int cg_random(uint64_t seed, uint64_t stream_id, int64_t first, int64_t n, int cube_size, uint8_t *out, int64_t out_pitch, void *stream) {
+    RC_NEED_INIT();
+    if (cube_size != 2 && cube_size != 3) return fail(RC_EINVAL, "cg_random: cube_size must be 2 or 3");
+    if (n < 0) return fail(RC_EINVAL, "cg_random: n is negative");
+    if (first < 0 || first > INT64_MAX - n) return fail(RC_EINVAL, "cg_random: first is negative, or first + n overflows");
+    int sh;
+    if (int rc = cg_rows_arg("cg_random", "out", out, out_pitch, n, cube_size == 3 ? Cube3::SLOTS : Cube2::SLOTS, sh)) return rc;
+    if (n == 0) return RC_OK;
+    const int64_t blocks = ceil_div(n, 256);
+    RC_GRID(blocks);
+    return by_size(cube_size, [&](auto t) {
+        hipLaunchKernelGGL(k_cg_random<decltype(t)>, dim3((unsigned)blocks), dim3(256), 0, S(stream), seed, stream_id, first, n, out, out_pitch, sh);
+        RC_HIP(RC_EHIP, hipGetLastError());
+        return RC_OK;
+    });
+}
+
+int cg_invert_actions(const uint8_t *actions, int64_t rows, int64_t n, int64_t act_pitch, int cube_size, uint8_t *out, int64_t out_pitch,
+                      uint8_t *bad, void *stream) {
+    RC_NEED_INIT();
+    const auto no = [](const char *what) { return fail(RC_EINVAL, "cg_invert_actions: %s", what); };
+    if (cube_size != 2 && cube_size != 3) return no("cube_size must be 2 or 3");
+    if (rows < 0) return no("rows is negative");
+    if (n < 0) return no("n is negative");
+    if (!actions || !aligned16(actions)) return no("actions is NULL or not 16-byte aligned");
+    if (act_pitch < n || act_pitch <= 0 || (act_pitch & 15) != 0) return no("act_pitch: need act_pitch % 16 == 0 and act_pitch >= max(n, 16)");
+    if (!out || !aligned16(out)) return no("out is NULL or not 16-byte aligned");
+    if (out_pitch < n || out_pitch <= 0 || (out_pitch & 15) != 0) return no("out_pitch: need out_pitch % 16 == 0 and out_pitch >= max(n, 16)");
+    if (rows > INT64_MAX / act_pitch || rows > INT64_MAX / out_pitch) return no("rows: rows * pitch overflows");
+    if (!bad) return no("bad is NULL");
+    if (n == 0 || rows == 0) return RC_OK;
+    const int64_t ab = (rows - 1) * act_pitch + n, ob = (rows - 1) * out_pitch + n;
+    if (!(out == actions && out_pitch == act_pitch) && cg_overlap(out, ob, actions, ab))
+        return no("out overlaps actions (out may be exactly actions, with act_pitch)");
+    if (cg_overlap(bad, 1, out, ob)) return no("bad lies inside out");
+    const int64_t blocks = ceil_div(n, 256);
+    RC_GRID(blocks);
+    hipLaunchKernelGGL(k_cg_invert_actions, dim3((unsigned)blocks), dim3(256), 0, S(stream), actions, rows, n, act_pitch,
+                       (uint32_t)(cube_size == 3 ? Cube3::A : Cube2::A), out, out_pitch, bad);
+    RC_HIP(RC_EHIP, hipGetLastError());
+    return RC_OK;
 }
 
 }  // extern "C"

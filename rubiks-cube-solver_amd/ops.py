@@ -370,6 +370,92 @@ def from_cubies(cub, n, cube_size, cubie_pitch=None, out=None, pitch=None, bad=N
     return out
 
 
+def _group_flag(bad, device, what):
+    return torch.zeros(1, dtype=torch.uint8, device=device) if bad is None else _vec(bad, 1, torch.uint8, what)
+
+
+def group_product(x, y, n, cube_size, x_pitch=None, y_pitch=None, out=None, out_pitch=None, bad=None):
+    """x o y, "x then y", cube by cube (cg_product, include/rubikhip.h "Cube group"): slot q of the result holds what x has in slot
+    piece(y[q]), turned by ori(y[q]).  x, y, out: cubie buffers uint8 [tiles, SLOTS, pitch] with pitches of their own (pitch None: the
+    tensor's last dimension); out defaults to a fresh buffer shaped like x and may be x or y themselves.  Any bytes that name a
+    (piece, ori) are multiplied as given.  A byte that names none cannot raise on the device: that cube comes out as the identity and
+    a flag is set.  bad: that flag, a uint8 device tensor [1] the caller zeroes and reads (nothing synchronises); None: a flag of the
+    call's own, read back at once (a synchronisation) and raised as ValueError.  Returns out."""
+    from . import _group_lib
+    _, _, SL = _size(cube_size)
+    p_x, p_y = _state_arg(x, SL, n, x_pitch, "group_product x"), _state_arg(y, SL, n, y_pitch, "group_product y")
+    if y.device != x.device:
+        raise RubikHipError("group_product: x and y are on different devices")
+    if out is None:
+        out, out_pitch = torch.empty_like(x), x_pitch
+    p_out = _state_arg(out, SL, n, out_pitch, "group_product out")
+    flag = _group_flag(bad, x.device, "group_product bad")
+    _lib.init(x.device)
+    check(_group_lib.group_lib().cg_product(ptr(x), p_x, ptr(y), p_y, n, cube_size, ptr(out), p_out, ptr(flag), stream_ptr(x.device)))
+    if bad is None and int(flag):
+        raise ValueError("group_product: a cubie byte names no (piece, orientation)")
+    return out
+
+
+def group_inverse(x, n, cube_size, x_pitch=None, out=None, out_pitch=None, bad=None):
+    """The inverse of every cube (cg_inverse): out[piece(x[q])] = (q, -ori(x[q])).  x, out, bad as in group_product; out may be x
+    itself.  A byte that names no (piece, ori), or a piece that occurs twice, gives the identity and sets the flag.  Returns out."""
+    from . import _group_lib
+    _, _, SL = _size(cube_size)
+    p_x = _state_arg(x, SL, n, x_pitch, "group_inverse x")
+    if out is None:
+        out, out_pitch = torch.empty_like(x), x_pitch
+    p_out = _state_arg(out, SL, n, out_pitch, "group_inverse out")
+    flag = _group_flag(bad, x.device, "group_inverse bad")
+    _lib.init(x.device)
+    check(_group_lib.group_lib().cg_inverse(ptr(x), p_x, n, cube_size, ptr(out), p_out, ptr(flag), stream_ptr(x.device)))
+    if bad is None and int(flag):
+        raise ValueError("group_inverse: the cubie rows of a cube are no permutation of the pieces")
+    return out
+
+
+def random_cubies(n, cube_size, device, seed=0, stream_id=0, first=0, out=None, out_pitch=None):
+    """n cubes drawn uniformly from the group (cg_random): cube i is a function of (seed, stream_id, first + i) alone, so one stream
+    can be cut into chunks or shards by `first`.  out: a cubie buffer (default: a fresh one, pad columns zero).  Returns out."""
+    from . import _group_lib
+    _, _, SL = _size(cube_size)
+    if out is None:
+        tiles, pitch = _tile_shape(n, out_pitch)
+        out = torch.zeros((tiles, SL, pitch), dtype=torch.uint8, device=device)
+    p_out = _state_arg(out, SL, n, out_pitch, "random_cubies out")
+    if first < 0:
+        raise ValueError("random_cubies: first must be >= 0")
+    mask = (1 << 64) - 1
+    _lib.init(out.device)
+    check(_group_lib.group_lib().cg_random(int(seed) & mask, int(stream_id) & mask, int(first), n, cube_size, ptr(out), p_out, stream_ptr(out.device)))
+    return out
+
+
+def invert_actions(actions, n, cube_size, out=None, bad=None):
+    """The inverse of n action lists (cg_invert_actions): actions uint8 [L, pitch] on the device, one list per column, A the no-op.
+    Column c of out receives the column's other entries in reverse order, each ^ 1, then no-ops.  out defaults to a fresh tensor
+    shaped like actions (pad columns: the no-op) and may be actions itself.  An entry above A counts as the no-op and sets the flag
+    (bad as in group_product; raised as IndexError when the flag is the call's own).  Returns out."""
+    from . import _group_lib
+    _, A, _ = _size(cube_size)
+    for t, what in ((actions, "actions"), (out, "out")):
+        if t is None:
+            continue
+        if t.dtype != torch.uint8 or not t.is_cuda or not t.is_contiguous() or t.dim() != 2 or t.shape[1] < n or t.shape[1] % 16:
+            raise RubikHipError(f"invert_actions {what}: need a contiguous uint8 HIP tensor [L, pitch], pitch >= n, pitch % 16 == 0")
+    if out is None:
+        out = torch.full_like(actions, A)
+    elif out.shape[0] != actions.shape[0]:
+        raise RubikHipError("invert_actions out: need as many rows as actions has")
+    flag = _group_flag(bad, actions.device, "invert_actions bad")
+    _lib.init(actions.device)
+    check(_group_lib.group_lib().cg_invert_actions(ptr(actions), actions.shape[0], n, actions.shape[1], cube_size, ptr(out), out.shape[1],
+                                                   ptr(flag), stream_ptr(actions.device)))
+    if bad is None and int(flag):
+        raise IndexError("invert_actions: action out of range")
+    return out
+
+
 def search_pack(leaf_code, child_code, child_solved, n, cube_size, leaf_out, child_out, solved_out):
     """The results of one expansion launch, laid out per root for the host trees of a lockstep search (rc_search_pack):
     leaf_code [tiles, SLOTS, pitch], child_code [A, tiles, SLOTS, pitch], child_solved [A, tiles * pitch]  ->

@@ -943,3 +943,89 @@ def two_phase_frames(tables, chain, env, *, candidates=64, phase1_limit=16, phas
                candidate=torch.where(solved, cand, torch.full_like(cand, -1)), phase1_length=torch.where(solved, p1, torch.full_like(p1, -1)),
                chain_length=ch["length"], nodes=nodes, status=one.status[:n].clone())
     return res, dict(one=one, two=two, descent=descent, limit2=limit2[:, :n], chain=ch)
+
+
+# ------------------------------------------------------------------------------------------------------------------- cube group
+# include/rubikhip.h "Cube group", DESIGN.md "Cube group": what the solvers gain from products and inverses of whole cubes.
+def _goal_cubies(env, goal, who):
+    SL = ops.N_SLOTS[env.cube_size]
+    if hasattr(goal, "stickers"):
+        if (goal.num_envs, goal.cube_size, goal.device) != (env.num_envs, env.cube_size, env.device):
+            raise ValueError(f"{who}: the goal env must have the same num_envs, cube_size and device")
+        return goal.cubies()
+    if isinstance(goal, torch.Tensor) and goal.dim() == 3 and goal.shape[1] == SL and goal.dtype == torch.uint8:
+        return goal.to(env.device)
+    raise ValueError(f"{who}: goal must be a VecCubeEnv or a tiled uint8 cubie tensor [tiles, {SL}, pitch]")
+
+
+def relative_to(env, goal):
+    """A new env whose cube i is goal_i^-1 o x_i: any solver's answer for it, played on x_i, ends at goal_i instead of at solved.
+    goal: a VecCubeEnv of the same size and device, or a tiled cubie tensor.  env and goal are left as they are; a goal or a cube
+    that is no permutation of the pieces raises ValueError."""
+    n, cs = env.num_envs, env.cube_size
+    g = _goal_cubies(env, goal, "relative_to")
+    inv = ops.group_inverse(g, n, cs)
+    out = env.clone()
+    out.from_cubies(ops.group_product(inv, env.cubies(), n, cs))
+    return out
+
+
+def invert_actions(actions, cube_size=3):
+    """The inverse of a solver's `actions` uint8 [L, N] (padded with the no-op at the end): per column the moves in reverse order, each
+    replaced by its inverse a ^ 1, padded again at the end -- a solution turned into a scramble, or the answer for the inverse cube
+    mapped back (one cg_invert_actions launch).  Returns uint8 [L, N]."""
+    if not isinstance(actions, torch.Tensor) or actions.dtype != torch.uint8 or actions.dim() != 2 or not actions.is_cuda:
+        raise ValueError("invert_actions: actions is a uint8 HIP tensor [L, N]")
+    L, n = actions.shape
+    buf = torch.full((L, _lib.pitch_for(n, 16)), get_env_config(cube_size)[1], dtype=torch.uint8, device=actions.device)
+    buf[:, :n] = actions
+    return ops.invert_actions(buf, n, cube_size, out=buf)[:, :n].contiguous()
+
+
+def _rows_to(actions, rows, noop=12):
+    L, n = actions.shape
+    if L >= rows:
+        return actions[:rows]
+    return torch.cat([actions, torch.full((rows - L, n), noop, dtype=torch.uint8, device=actions.device)])
+
+
+def two_phase_solve_both(tables, chain, env, **kw):
+    """two_phase_solve on every cube AND on its inverse (Kociemba's standard trick: the two searches see different cubes): the inverse
+    cube's answer, inverted by invert_actions, solves the cube itself; per cube the shorter one wins, the plain one among equals, so
+    `length` is never above two_phase_solve's.  kw: two_phase_solve's keywords.  The env is left as it is.
+    Returns two_phase_solve's keys, each taken from the winning side (nodes: the sum of both sides, the work done), and side uint8
+    [N]: 0 plain, 1 inverse.  An illegal cube is side 0 and unsolved, as in two_phase_solve."""
+    _cube3_env(env, "two_phase_solve_both")
+    n, dev = env.num_envs, env.stickers.device
+    plain = two_phase_solve(tables, chain, env, **kw)
+    c = ops.cubies(env.stickers, n, 3)
+    flag = torch.zeros(1, dtype=torch.uint8, device=dev)          # set for cubes that are no cube; those stay on the plain side
+    other = env.clone()
+    other.stickers.copy_(ops.from_cubies(ops.group_inverse(c["cubies"], n, 3, bad=flag), n, 3, out=torch.empty_like(env.stickers)))
+    inv = two_phase_solve(tables, chain, other, **kw)
+    big = torch.full_like(plain["length"], 2 ** 30)
+    use = (c["status"][:n] == 0) & inv["solved"] & (torch.where(inv["solved"], inv["length"], big) < torch.where(plain["solved"], plain["length"], big))
+    out = {}
+    for k, a in plain.items():
+        b = inv[k]
+        if k == "actions":
+            rows = max(a.shape[0], b.shape[0])
+            out[k] = torch.where(use[None, :], _rows_to(invert_actions(b), rows), _rows_to(a, rows))
+        elif k == "nodes":
+            out[k] = a + b
+        else:
+            out[k] = torch.where(use, b, a)
+    out["actions"] = out["actions"][:max(1, int(out["length"].max())) if n else 1].contiguous()
+    out["side"] = use.to(torch.uint8)
+    return out
+
+
+def random_state_scramble(tables, chain, n, seed, device="cuda", **kw):
+    """n random-state scrambles, the way a competition scrambler makes them: n cubes drawn uniformly from the group (cg_random, seed),
+    solved by two_phase_solve (kw: its keywords), the answers inverted.  Returns dict(cubies: the drawn cubes' tiled cubie tensor,
+    actions uint8 [L, n]: played from solved they give exactly those cubes, length int32 [n])."""
+    from .vec_env import VecCubeEnv
+    env = VecCubeEnv(n, device=device, cube_size=3, obs=None)
+    env.reset_uniform(seed)
+    res = two_phase_solve(tables, chain, env, **kw)
+    return dict(cubies=env.cubies(), actions=invert_actions(res["actions"]), length=res["length"])

@@ -275,6 +275,46 @@ class VecCubeEnv:
         self._new_episodes()
         return self._observe()
 
+    def _set_cubies(self, cub, bad, what):
+        """The tail of compose / invert / reset_uniform: the flag raised with the env untouched, else the stickers of the cubie rows."""
+        if bad is not None and int(bad):
+            raise ValueError(f"{what}: a cube's cubie rows name no (piece, orientation), or are no permutation of the pieces")
+        self.stickers.copy_(ops.from_cubies(cub, self.num_envs, self.cube_size, out=torch.empty_like(self.stickers)))
+        self._new_episodes()
+        return self._observe()
+
+    def compose(self, other):
+        """Cube i becomes x_i o y_i, "this cube, then other's" (include/rubikhip.h "Cube group"): the cube reached from x_i by any move
+        sequence that takes solved to y_i.  other: a VecCubeEnv of the same size and device, or a tiled cubie tensor as cubies()
+        returns it.  Assemblies need not be legal; a byte that names no (piece, orientation) raises ValueError and the env keeps its
+        cubes.  Starts new episodes like from_cubies(); returns the observation."""
+        n, SL = self.num_envs, ops.N_SLOTS[self.cube_size]
+        if isinstance(other, VecCubeEnv):
+            if (other.num_envs, other.cube_size, other.device) != (n, self.cube_size, self.device):
+                raise ValueError("compose: the other env must have the same num_envs, cube_size and device")
+            y = other.cubies()
+        elif isinstance(other, torch.Tensor) and other.dim() == 3 and other.shape[1] == SL and other.dtype == torch.uint8:
+            y = other.to(self.device)
+        else:
+            raise ValueError(f"compose: other must be a VecCubeEnv or a tiled uint8 cubie tensor [tiles, {SL}, pitch]")
+        bad = torch.zeros(1, dtype=torch.uint8, device=self.device)
+        x = self.cubies()
+        return self._set_cubies(ops.group_product(x, y, n, self.cube_size, out=x, bad=bad), bad, "compose")
+
+    def invert(self):
+        """Every cube becomes its inverse: the cube whose solutions are this cube's scrambles.  A sticker state whose slots are no
+        permutation of the pieces raises ValueError and the env keeps its cubes.  Starts new episodes; returns the observation."""
+        bad = torch.zeros(1, dtype=torch.uint8, device=self.device)
+        x = self.cubies()
+        return self._set_cubies(ops.group_inverse(x, self.num_envs, self.cube_size, out=x, bad=bad), bad, "invert")
+
+    def reset_uniform(self, seed, stream_id=0, first=0):
+        """Every cube drawn uniformly from the group (cg_random): cube i is a function of (seed, stream_id, first + i) alone.  Starts new
+        episodes like reset(); returns the observation."""
+        cub = ops.random_cubies(self.num_envs, self.cube_size, self.device, seed=seed, stream_id=stream_id, first=first,
+                                out_pitch=self.stickers.shape[2])
+        return self._set_cubies(cub, None, "reset_uniform")
+
     def expand(self, children=False, codes=True, pitch=None):
         """All A children of every cube (cube_env.py:212-236, mcts.py:96-101).
         Returns dict(child_solved [A, Wp], child_code [A, tiles, SLOTS, pitch], children [A, tiles, S, pitch]);
